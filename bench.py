@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W            (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W      (N > 1, one rank per GPU)
+    options: --full (every section of the line below, minutes), --dump-outputs DIR (what the last timed step computed)
 
 Workload (BASELINE.json configs[1]): linearised cartpole n=4, m=1, horizon N=10, fixed initial state
 (results_linear_system.py:120), p_loss = 0.3, batch 4096 (x_k, ref) pairs PER GPU (weak scaling).  The pairs are the
@@ -17,6 +18,8 @@ Metric: QP solves per second (= MPC steps per second), whole job.  The same JSON
   roofline      FP64 flops of the interior-point iterations actually executed (iters per instance come back from the
                 device; F_it of SURVEY.md 8(d)) over the average kernel duration from HIP events on the solve stream,
                 against the MI355X FP64 peak; kernel name from the library (tmpc_kernel_name);
+and, with --full only (a plain run sets up, warms up, times the K steps and prints the line; the sections below take minutes),
+  roofline.launch_ms_by_order   one extra launch per batch order, timed on its own;
   cpu_baseline  the CPU oracle (oracle/tmpc_oracle.c, OpenMP over the batch) timed on this box's host cores on a
                 bounded sample of the same workload;
   extras        closed loop on the device (cold and warm-started), BASELINE configs[2] (N = 20 extended controller,
@@ -27,12 +30,16 @@ Metric: QP solves per second (= MPC steps per second), whole job.  The same JSON
                 pointers, copies included -- and for the CPU oracle on one thread;
   closed_loop_small   the reference's own experiment size (results_linear_system.py:64,147-149: N = 20, 10 loss rates x 20
                 runs x 250 steps) through the device-resident loop, wall seconds (one fused launch, and a launch pair per step);
-  ranks_seen / per_rank_ms   (multi-GPU) an all-reduce of ones and every rank's own timed region and average kernel time.
-Order of a one-GPU run: set-up, one solve + the statistics gather (loads torch's kernels), the extras, THEN the W warm-up steps and
-the K timed steps.  The first torch kernel of a process costs tens of milliseconds of host time; placed between the warm-up steps and
-the timed ones (round 2) it let the card idle, and its clocks need some fifty launches to come back: 4 % on the average kernel
-time of K = 20 timed steps (scripts/gpu_ramp.py).  The timed region itself is unchanged: exactly K steps after exactly W, bracketed by
-barrier + synchronize, with the statistics gather inside.
+  pipelined     two handles taking turns over the same batches (every rank).
+ranks_seen / per_rank_ms   (multi-GPU, every run) an all-reduce of ones and every rank's own timed region and average kernel time.
+Order of a one-GPU run: set-up, one solve + the statistics gather (loads torch's kernels), the extras (--full) or PRELOAD launches of
+the headline solve (plain run), THEN the W warm-up steps and the K timed steps.  The first torch kernel of a process costs tens of
+milliseconds of host time; placed between the warm-up steps and the timed ones (round 2) it let the card idle, and its clocks need
+some fifty launches to come back: 4 % on the average kernel time of K = 20 timed steps (scripts/gpu_ramp.py).  The extras or the
+preload keep the card busy up to the warm-up steps (`preload` in the line says which; --no-extras leaves both out).  The timed region
+itself is unchanged: exactly K steps after exactly W, bracketed by barrier + synchronize, with the statistics gather inside.
+--dump-outputs DIR writes, after the timed region, what its last step handed back: u_nom, x_nom0, xu_ss, status and iters of that
+step's batch in the order of the 4096 harvested states (float64), and the gathered statistics table (gathered_status / _iters).
 Nothing here reads tests/ : the controller set-up lives in the package (workloads.make_controller).
 """
 import argparse
@@ -49,6 +56,7 @@ sys.path.insert(0, ROOT)
 
 FP64_PEAK_TFLOPS = 78.6      # MI355X FP64 vector = FP64 matrix peak (AMD datasheet)
 HBM_PEAK_GBPS = 8000.0       # MI355X_MICROARCH.md
+PRELOAD = 256                # headline launches ahead of the warm-up steps in a plain run (see the docstring)
 
 
 def flops_per_iteration(nv, nc):
@@ -182,12 +190,22 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=4096, help="QP instances per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-closed-loop", action="store_true", help="skip the closed-loop extra (profiling runs: keeps the kernel statistics to the timed steps)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config-3 / config-5 / offline-LP extras")
+    ap.add_argument("--full", action="store_true",
+                    help="every section of the line: CPU baselines, closed loops, configs 3 and 5, offline LPs, pipelined handles, "
+                         "launch time by batch order (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-closed-loop", action="store_true", help="with --full: skip the closed-loop extra (profiling runs: keeps the kernel statistics to the timed steps)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the config-3 / config-5 / offline-LP / pipelined extras (--full) "
+                                                             "or the preload launches (plain run)")
     ap.add_argument("--only", choices=["config3", "config5"], default=None,
-                    help="profiling runs: time ONLY this extra's solve calls (rocprofv3 kernel statistics then belong to it)")
+                    help="with --full, profiling runs: time ONLY this extra's solve calls (rocprofv3 kernel statistics then belong to it)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only and not args.full:
+        ap.error("--only times a section of the --full line: add --full")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -292,9 +310,10 @@ def main():
     # on which instances happen to come last (0.53 ... 0.76 ms over random orders of these very states).  Eight seeded random
     # orders of the same 4096 states are kept in HBM and the steps go round them, so `value` is the mean over orders.
     NORD = 8
-    batches = []
+    batches, perms = [], []
     for k in range(NORD):
         perm = np.random.default_rng(2000 + 16 * rank + k).permutation(B)
+        perms.append(perm)
         batches.append(DeviceBatch(torch, dev, X[perm], R[perm], None, N, nu))
     batch = batches[0]
     torch.cuda.synchronize()
@@ -465,7 +484,15 @@ def main():
     _native.synchronize(h)
     gather_stats()
     fence()
-    extras_out = extras()
+    extras_out = {}
+    if args.full:
+        extras_out = extras()
+    elif not args.no_extras:
+        # the plain run's stand-in for the extras: its own kernel, back to back, so that the warm-up steps start from a card
+        # past its clock ramp as they do after the extras (some fifty launches; these are ~0.1 s)
+        for i in range(PRELOAD):
+            batches[i % NORD].solve(_native, h)
+        _native.synchronize(h)
     torch.cuda.synchronize()
 
     for i in range(args.warmup):
@@ -501,17 +528,26 @@ def main():
         if ranks_seen != world:
             print(f"bench.py: the all-reduce saw {ranks_seen} ranks, expected {world}", file=sys.stderr)
             sys.exit(4)
-    # spread of the launch time over the eight batch orders (outside the timed region: one launch each, HIP events)
-    _native.synchronize(h)
-    _native.kernel_ms_total(h, reset=True)
-    order_ms = []
-    for k in range(NORD):
-        batches[k].solve(_native, h)
-        _native.synchronize(h)
-        ms_k, n_k = _native.kernel_ms_total(h, reset=True)
-        order_ms.append(ms_k / max(n_k, 1))
     stats_np = stats_all.cpu().numpy()
     status_all, iters_all = stats_np[:, 0], stats_np[:, 1]
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, rows put back into the order of X / R (the same for every --steps)
+        last, inv = batches[(args.steps - 1) % NORD], np.argsort(perms[(args.steps - 1) % NORD])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("u_nom", last.u), ("x_nom0", last.x0), ("xu_ss", last.ss), ("status", last.st), ("iters", last.it)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy().astype(np.float64)[inv])
+        np.save(os.path.join(args.dump_outputs, "gathered_status.npy"), status_all.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "gathered_iters.npy"), iters_all.astype(np.float64))
+    # spread of the launch time over the eight batch orders (outside the timed region: one launch each, HIP events)
+    order_ms = []
+    if args.full:
+        _native.synchronize(h)
+        _native.kernel_ms_total(h, reset=True)
+        for k in range(NORD):
+            batches[k].solve(_native, h)
+            _native.synchronize(h)
+            ms_k, n_k = _native.kernel_ms_total(h, reset=True)
+            order_ms.append(ms_k / max(n_k, 1))
 
     if rank == 0:
         value = world * B * args.steps / elapsed
@@ -520,9 +556,10 @@ def main():
         bytes_solve = 8 * (2 * nx) + 8 * (N * nu + nx + nx + nu) + 8      # inputs + the outputs this call writes + status/iters
         roof["traffic"] = measured_traffic(roof["kernel"])
         roof["traffic_source"] = TRAFFIC_PROFILE
-        roof["launch_ms_by_order"] = {"min": min(order_ms), "max": max(order_ms), "mean": float(np.mean(order_ms)),
-                                       "note": "one launch per batch order, same 4096 states (two instances per resident wave: the "
-                                               "launch ends with its slowest wave)"}
+        if order_ms:
+            roof["launch_ms_by_order"] = {"min": min(order_ms), "max": max(order_ms), "mean": float(np.mean(order_ms)),
+                                           "note": "one launch per batch order, same 4096 states (two instances per resident wave: the "
+                                                   "launch ends with its slowest wave)"}
         roof["note"] = ("bound is FP64 arithmetic (vector ALU + the FP64 MFMA normal-matrix pass; 78.6 TFLOP/s is the peak of "
                         "either), not HBM: algorithmic HBM bytes are %d B/solve" % bytes_solve)
         roof["hbm"] = {"achieved": bytes_solve * B / (avg_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -545,11 +582,12 @@ def main():
                             "note": "every rank's own timed region / K and average solve-kernel duration (HIP events); "
                                     "ms_per_step above is the slowest rank's"},
             # what the card ran between the set-up and the W warm-up steps (the headline depends on it by 2-4 %: clock ramp,
-            # scripts/gpu_ramp.py): "extras" = seconds of the other sections' launches, "none" = the set-up's idle time
-            "preload": ("none" if args.no_extras and (args.no_closed_loop or world > 1) else
-                        "extras" if not args.no_extras else "closed_loop"),
+            # scripts/gpu_ramp.py): "extras" = seconds of the other sections' launches, "solves" = PRELOAD launches of the
+            # headline solve, "none" = the set-up's idle time
+            "preload": ("none" if args.no_extras and (args.no_closed_loop or world > 1 or not args.full) else
+                        "closed_loop" if args.no_extras else "extras" if args.full else "solves"),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle.oracle import Oracle
             orc = Oracle(mpc._problem_dict())
             cores = host_cores()
