@@ -28,7 +28,9 @@ extern "C" {
 /* 1: first cut; 2: projected terminal rows of the packet-received problem (HTP, hTP, rTP); 3: tmpc_lp_batch, TMPC_STATUS_UNBOUNDED;
  * 4: terminal_equality, tmpc_kernel_name; 5: an iterate that hits the iteration cap keeps TMPC_STATUS_MAX_ITER whatever its
  * constraint violation (INFEASIBLE only with a Farkas-type certificate), host-only handles report their kernel path,
- * tmpc_debug_dump_layout (tmpc_debug_dump_lp_layout was added later without a bump: a new export, nothing else changed) */
+ * tmpc_debug_dump_layout (tmpc_debug_dump_lp_layout was added later without a bump: a new export, nothing else changed).
+ * Added without a bump: the regulator QPs (tmpc_regulator_problem, tmpc_create_regulator, tmpc_reg_run) -- new exports; tmpc_problem
+ * and every tracking handle behave as before (a regulator handle accepts ref == NULL in the solve calls, see below) */
 #define TMPC_ABI_VERSION 5
 
 /* error codes (function return values) */
@@ -121,6 +123,80 @@ const char *tmpc_last_error(const tmpc_handle *h);
 int tmpc_create(const tmpc_problem *p, int device, tmpc_handle **out);
 
 void tmpc_destroy(tmpc_handle *h);
+
+/*
+ * The regulator QPs -- the root of the reference's class chain: RegulatorMPC (RegulatorMPC.py:45-91, "bring the state to the
+ * origin") and, with `tube` set, the tube MPC of Mayne, Seron and Rakovic 2005, TubeRegulatorMPC (TubeRegulatorMPC.py:109-143).
+ *
+ *   model     x+ = A x + B u                      A: nx*nx   B: nx*nu
+ *   weights   Q: nx*nx  R: nu*nu  stage cost x'Qx + u'Ru, i = 0 .. N-1
+ *             P: nx*nx  terminal weight x_N'P x_N  (tube only; the plain regulator has none, NULL allowed)
+ *   gain      K: nu*nx  ancillary gain of u = u_nom_0 - K (x - x_nom_0) (the LQR gain, u = -K x); tmpc_reg_run applies it.
+ *             Tube: required.  Plain: not read (x_nom_0 = x), NULL allowed
+ *   sets      {Hx x <= hx}   rx rows on x_0 .. x_{N-1}   (tube: the tightened Xc)   rx = 0: no state constraint (X = None)
+ *             {Hu u <= hu}   ru rows on u_0 .. u_{N-1}   (tube: the tightened Uc)   ru = 0: no input constraint (U = None)
+ *             {Hf x <= hf}   rf rows on x_N, terminal set Xf (tube only; rf = 0: none)
+ *             {HZ e <= hZ}   rZ rows, the tube cross-section Z: HZ (x_k - x_0) <= hZ (tube only, rZ > 0 required)
+ *   tube      0: plain regulator, z = [u_0 .. u_{N-1}] with x_0 = x_k (the rows Hx x_0 <= hx then depend on x_k only and are
+ *                checked once per instance: a state outside X is INFEASIBLE)
+ *             1: tube regulator, z = [u_0 .. u_{N-1} | x_0] with x_0 free
+ *   tol, max_iter: as in tmpc_problem.
+ * A row count > 0 needs both of its arrays.
+ */
+typedef struct tmpc_regulator_problem {
+    int32_t nx, nu, N;
+    int32_t rx, ru, rf, rZ;
+    int32_t tube;
+    int32_t max_iter;
+    double  tol;
+    const double *A, *B, *Q, *R, *P, *K;
+    const double *Hx, *hx, *Hu, *hu, *Hf, *hf, *HZ, *hZ;
+} tmpc_regulator_problem;
+
+/*
+ * Replaces RegulatorMPC.generate_optimization_problem / TubeRegulatorMPC.generate_optimization_problem: condenses the QP
+ * (min 1/2 z'Hz + (F1 x_k)'z  s.t.  G z <= g0 + E x_k; F2 = 0, no steady-state block) and returns an ordinary handle: the
+ * solve calls, tmpc_set_kernel_path, tmpc_kernel_name, tmpc_get_dims / _condensed / _factoring and tmpc_destroy take it as
+ * they take a tracking handle (device < 0: host-only, as in tmpc_create).  Same limits as tmpc_create (0 < nx <= 16).
+ * In tmpc_solve_batch[_device] on a regulator handle:  ref may be NULL and is ignored; xu_ss must be NULL; variant must be
+ * NULL; x_nom0 receives x_0 (the decision variable of the tube regulator, x_k for the plain one); x_nom the predicted
+ * trajectory x_0 .. x_N.  tmpc_mc_run / tmpc_mc_replay refuse a regulator handle (its loop is tmpc_reg_run).
+ */
+int tmpc_create_regulator(const tmpc_regulator_problem *p, int device, tmpc_handle **out);
+
+/*
+ * Device-resident closed loop of a regulator handle -- the loop of the reference's Example_of_Tube_Regulator_MPC.py (and of
+ * Example_of_Regulator_MPC.py with K = 0, w = 0) -- for B independent trajectories and T time steps.  Per step, on the
+ * handle's stream: one solve launch over all trajectories, then one launch of the step kernel (csrc/tmpc_reg.hip), which per
+ * trajectory applies  u_t = u_nom_0 - K (x_t - x_nom_0)  (plain: u_t = u_nom_0), updates  x_{t+1} = A x_t + B u_t + w_t,
+ * accumulates the statistics and writes the next solve's x_k in place.  Nothing returns to the host until the statistics.
+ *
+ *   in   x0     B*nx
+ *        w      B*T*nx disturbances, or NULL: drawn on the device as set by tmpc_mc_set_device_rng (w_t of trajectory b is
+ *               the w of tmpc_mc_run's stream for (seed, first_trajectory + b, t); montecarlo.draw_realisations_philox is the
+ *               host twin); NULL without the device generator: no disturbance
+ *        HX,hX  rX x nx, rX   check set for x_t (normally the un-tightened X); rX = 0: no check
+ *        HU,hU  rU x nu, rU   check set for u_t (normally the un-tightened U); rU = 0: no check
+ *        HZ,hZ  rZ x nx, rZ   tube cross-section for x_t - x_nom_0,t; rZ = 0: no check
+ *        capture index of the trajectory whose x (T+1)*nx, x_nom0 T*nx, u T*nu are copied to cap_x / cap_xn / cap_u
+ *               (-1 or any NULL pointer: none)
+ *   out  (any may be NULL), per trajectory:
+ *        cost        sum_t x_t'Q x_t + u_t'R u_t
+ *        x_viol      steps with x_t outside {HX x <= hX} (by more than 1e-7, polytope's abs_tol)
+ *        u_viol      steps with u_t outside {HU u <= hU}
+ *        tube_viol   steps with x_t - x_nom0_t outside Z
+ *        not_optimal solves with status != TMPC_STATUS_OPTIMAL
+ *        fail_step   first step whose solve has status >= TMPC_STATUS_INFEASIBLE, -1 if none; from that step on the
+ *                    trajectory is frozen (x stays, nothing accumulates)
+ *        x_final     B*nx
+ *        iters_sum   interior-point iterations of the trajectory's solves
+ * All pointers are HOST pointers; the call returns when the results are in place.
+ */
+int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const double *w,
+                 const double *HX, const double *hX, int32_t rX, const double *HU, const double *hU, int32_t rU,
+                 const double *HZ, const double *hZ, int32_t rZ,
+                 double *cost, int32_t *x_viol, int32_t *u_viol, int32_t *tube_viol, int32_t *not_optimal, int32_t *fail_step,
+                 double *x_final, int32_t *iters_sum, int64_t capture, double *cap_x, double *cap_xn, double *cap_u);
 
 /*
  * Replaces solve_optimization_problem(x_init, ref[, gamma_t])

@@ -31,6 +31,16 @@ class TmpcProblem(C.Structure):
                 + [(n, _dp) for n in _PTR_FIELDS] + [("rTP", C.c_int32), ("terminal_equality", C.c_int32)])
 
 
+_REG_INT_FIELDS = ["nx", "nu", "N", "rx", "ru", "rf", "rZ", "tube", "max_iter"]
+_REG_PTR_FIELDS = ["A", "B", "Q", "R", "P", "K", "Hx", "hx", "Hu", "hu", "Hf", "hf", "HZ", "hZ"]
+
+
+class TmpcRegulatorProblem(C.Structure):
+    """Field-for-field include/tmpc.h: tmpc_regulator_problem."""
+    _fields_ = ([(n, C.c_int32) for n in _REG_INT_FIELDS] + [("tol", C.c_double)]
+                + [(n, _dp) for n in _REG_PTR_FIELDS])
+
+
 _lib = None
 
 
@@ -131,6 +141,12 @@ def lib():
         L.tmpc_get_factoring.restype = C.c_int
         L.tmpc_get_condensed.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
         L.tmpc_get_condensed.restype = C.c_int
+        L.tmpc_create_regulator.argtypes = [C.POINTER(TmpcRegulatorProblem), C.c_int, C.POINTER(C.c_void_p)]
+        L.tmpc_create_regulator.restype = C.c_int
+        L.tmpc_reg_run.argtypes = ([C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 2
+                                   + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 8 + [C.c_int64]
+                                   + [C.c_void_p] * 3)
+        L.tmpc_reg_run.restype = C.c_int
         _lib = L
     return _lib
 
@@ -179,9 +195,48 @@ def pack_problem(d: dict):
     return p, keep
 
 
+def pack_regulator_problem(d: dict):
+    """dict (RegulatorMPC._regulator_dict) -> (TmpcRegulatorProblem, keep-alive list).  Absent sets (None) get 0 rows."""
+    p = TmpcRegulatorProblem()
+    keep = []
+    nx, nu = int(d["nx"]), int(d["nu"])
+    p.nx, p.nu, p.N = nx, nu, int(d["N"])
+    p.tube = int(d.get("tube", 0))
+    p.max_iter = int(d.get("max_iter", 0))
+    p.tol = float(d.get("tol", 0.0))
+    square = {"A": (nx, nx), "B": (nx, nu), "Q": (nx, nx), "R": (nu, nu), "P": (nx, nx), "K": (nu, nx)}
+    widths = {"Hx": nx, "Hu": nu, "Hf": nx, "HZ": nx}
+    rows = {}
+    for name in _REG_PTR_FIELDS:
+        v = d.get(name)
+        if v is None:
+            setattr(p, name, _dp())
+            continue
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+        if name in square:
+            if a.size != square[name][0] * square[name][1]:
+                raise ValueError(f"{name} has {a.size} entries, expected shape {square[name]}")
+            a = np.ascontiguousarray(a.reshape(square[name]))
+        elif name in widths:
+            if a.ndim != 2 or a.shape[1] != widths[name]:
+                raise ValueError(f"{name} must have {widths[name]} columns, got shape {a.shape}")
+            rows[name] = a.shape[0]
+        else:
+            a = np.ascontiguousarray(a.reshape(-1))
+            rows[name] = a.shape[0]
+        keep.append(a)
+        setattr(p, name, a.ctypes.data_as(_dp))
+    for hk, Hk in (("hx", "Hx"), ("hu", "Hu"), ("hf", "Hf"), ("hZ", "HZ")):
+        if rows.get(hk, 0) != rows.get(Hk, 0):
+            raise ValueError(f"{Hk} has {rows.get(Hk, 0)} rows but {hk} has {rows.get(hk, 0)} entries")
+    p.rx, p.ru, p.rf, p.rZ = rows.get("Hx", 0), rows.get("Hu", 0), rows.get("Hf", 0), rows.get("HZ", 0)
+    return p, keep
+
+
 class Handle:
-    def __init__(self, ptr, nx, nu, N, nvariants):
+    def __init__(self, ptr, nx, nu, N, nvariants, regulator: bool = False):
         self.ptr, self.nx, self.nu, self.N, self.nvariants = ptr, nx, nu, N, nvariants
+        self.regulator = regulator
 
     def error(self) -> str:
         return lib().tmpc_last_error(self.ptr).decode()
@@ -195,6 +250,17 @@ def create(problem: dict, device: int = 0) -> Handle:
     if rc != 0:
         raise RuntimeError(f"tmpc_create failed ({rc}): {L.tmpc_last_error(None).decode()}")
     return Handle(h, p.nx, p.nu, p.N, 2 if p.extended else 1)
+
+
+def create_regulator(problem: dict, device: int = 0) -> Handle:
+    """include/tmpc.h: tmpc_create_regulator (device < 0: host-only handle, for tmpc_get_condensed)."""
+    L = lib()
+    p, _keep = pack_regulator_problem(problem)
+    h = C.c_void_p()
+    rc = L.tmpc_create_regulator(C.byref(p), int(device), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_create_regulator failed ({rc}): {L.tmpc_last_error(None).decode()}")
+    return Handle(h, p.nx, p.nu, p.N, 1, regulator=True)
 
 
 def destroy(h: Handle):
@@ -258,6 +324,22 @@ def solve_batch(h: Handle, x, r, variant=None, want_traj: bool = True, timing: b
         if lib().tmpc_get_solve_ticks(h.ptr, B, ticks.ctypes.data) != 0:
             raise RuntimeError(h.error())
         out["solve_time"] = ticks * TICK_SECONDS
+    return out
+
+
+def solve_regulator_batch(h: Handle, x, want_traj: bool = True) -> dict:
+    """tmpc_solve_batch on a regulator handle: x (B, nx) -> u_nom (B, N, nu), x_nom0 (B, nx) (x_0: a decision variable of
+    the tube regulator, x_k for the plain one), x_nom (B, N+1, nx), status, iters; NaN rows where status >= INFEASIBLE."""
+    B = x.shape[0]
+    if lib().tmpc_set_solve_timing(h.ptr, 0) != 0:
+        raise RuntimeError(h.error())
+    nx, nu, N = h.nx, h.nu, h.N
+    out = dict(u_nom=np.empty((B, N, nu)), x_nom0=np.empty((B, nx)), x_nom=np.empty((B, N + 1, nx)) if want_traj else None,
+               status=np.empty(B, np.int32), iters=np.empty(B, np.int32))
+    rc = lib().tmpc_solve_batch(h.ptr, B, x.ctypes.data, None, None, out["u_nom"].ctypes.data, out["x_nom0"].ctypes.data, None,
+                                out["x_nom"].ctypes.data if want_traj else None, out["status"].ctypes.data, out["iters"].ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"tmpc_solve_batch failed ({rc}): {h.error()}")
     return out
 
 
@@ -403,6 +485,53 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     out["tracking_error"] = np.sqrt(out["err2"]) / T
     out["consistent_estimate_error"] = float(out["consistent"].max()) if B else 0.0
     out["iters_mean"] = float(out["iters_sum"].sum()) / max(B * T, 1)            # interior-point iterations per solve
+    return out
+
+
+def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=None, capture=None) -> dict:
+    """include/tmpc.h: tmpc_reg_run -- the closed loop of a regulator handle on the device.  x0 (B, nx); w (B, T, nx) or None;
+    device_rng = (seed, first_trajectory, w_bound): w drawn on the device (tmpc_mc_set_device_rng; the w of
+    montecarlo.draw_realisations_philox); neither: no disturbance.  X, U, Z: check sets (polytopes) or None.  capture: index of
+    a trajectory whose x_traj (T+1, nx), x_nom_traj (T, nx), u_traj (T, nu) are returned."""
+    c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))      # noqa: E731
+    x0 = c(x0).reshape(-1, h.nx)
+    B, T = x0.shape[0], int(T)
+    if w is not None:
+        w = c(w)
+        if w.shape != (B, T, h.nx):
+            raise ValueError(f"reg_run: w must be (B, T, nx) = {(B, T, h.nx)}, got {w.shape}")
+        rc = lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None)
+    elif device_rng is not None:
+        seed, first, w_bound = device_rng
+        wb = c(w_bound).reshape(h.nx)
+        rc = lib().tmpc_mc_set_device_rng(h.ptr, 1, int(seed), int(first), wb.ctypes.data)
+    else:
+        rc = lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None)
+    if rc != 0:
+        raise RuntimeError(h.error())
+    sets = []
+    for P, dim in ((X, h.nx), (U, h.nu), (Z, h.nx)):
+        if P is None:
+            sets += [None, None, 0]
+        else:
+            HA, hb = c(P.A), c(P.b).reshape(-1)
+            if HA.ndim != 2 or HA.shape[1] != dim or hb.size != HA.shape[0]:
+                raise ValueError("reg_run: a check set has the wrong dimension")
+            sets += [HA, hb, HA.shape[0]]
+    out = dict(cost=np.empty(B), x_viol=np.empty(B, np.int32), u_viol=np.empty(B, np.int32), tube_viol=np.empty(B, np.int32),
+               not_optimal=np.empty(B, np.int32), fail_step=np.empty(B, np.int32), x_final=np.empty((B, h.nx)),
+               iters_sum=np.empty(B, np.int32))
+    cap = -1 if capture is None else int(capture)
+    cx, cxn, cu = (np.empty((T + 1, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))) if cap >= 0 else (None, None, None)
+    ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+    args = [ptr(a) if isinstance(a, np.ndarray) or a is None else a for a in sets]
+    rc = lib().tmpc_reg_run(h.ptr, B, T, ptr(x0), ptr(w), *args, ptr(out["cost"]), ptr(out["x_viol"]), ptr(out["u_viol"]),
+                            ptr(out["tube_viol"]), ptr(out["not_optimal"]), ptr(out["fail_step"]), ptr(out["x_final"]),
+                            ptr(out["iters_sum"]), cap, ptr(cx), ptr(cxn), ptr(cu))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_reg_run failed ({rc}): {h.error()}")
+    if cap >= 0:
+        out["x_traj"], out["x_nom_traj"], out["u_traj"] = cx, cxn, cu
     return out
 
 

@@ -90,6 +90,12 @@ struct tmpc_handle {
     std::vector<double> mc_w_bound;
     int64_t mc_phys_B = 0;
     int64_t mc_tick_B = 0;
+    // regulator handles (tmpc_create_regulator): no reference input -- the solves read `ref` from a zero buffer (F2 = 0)
+    bool regulator = false;
+    int reg_tube = 0;
+    std::vector<double> hQ, hR;
+    double *reg_zero = nullptr;
+    int64_t reg_zero_cap = 0;
     std::string err;
 };
 
@@ -311,7 +317,9 @@ int upload_block(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     std::vector<int> grow;
     for (int r = 0; r < c.nc; ++r)
         if (!paired || c.mirror[r] > r) grow.push_back(r);
-    const int ng = static_cast<int>(grow.size()), ngp = (ng + 63) / 64 * 64;
+    // (a QP without inequality rows -- the unconstrained regulator -- keeps one chunk of 64 padding rows, g = 0 and h = 1: they
+    // never bind, the kernel's row loops and its workspace stay those of any other problem)
+    const int ng = static_cast<int>(grow.size()), ngp = std::max(64, (ng + 63) / 64 * 64);
     const int mir = paired ? ngp : 0, ncp = paired ? 2 * ngp : ngp;
     // Staircase of the condensed constraints: the rows of stage k act on u_0 .. u_k only, so the leading rows of G are
     // zero beyond a few 16-column tiles.  The general rows are ordered by the number of tiles they reach (stable), and the
@@ -499,6 +507,20 @@ int ensure_staging(tmpc_handle *h, int64_t B) {
     return TMPC_OK;
 }
 
+// Regulator handles: B x nx zeros in device memory, handed to the solve kernels as their reference (the condensed QP has F2 = 0, but
+// 0 * garbage is not 0 when the garbage is a NaN)
+int ensure_reg_zero(tmpc_handle *h, int64_t B) {
+    if (B <= h->reg_zero_cap) return TMPC_OK;
+    if (h->stream) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->reg_zero) (void)hipFree(h->reg_zero);
+    h->reg_zero = nullptr; h->reg_zero_cap = 0;
+    const size_t bytes = static_cast<size_t>(B) * h->nx * sizeof(double);
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->reg_zero), bytes));
+    HIP_TRY(h, hipMemset(h->reg_zero, 0, bytes));
+    h->reg_zero_cap = B;
+    return TMPC_OK;
+}
+
 // The next pair of timing events of the handle's pool (tmpc_last_kernel_ms / tmpc_kernel_ms_total read them); records the first one.
 // Beyond 4096 pairs the last one is reused.
 int begin_timed_launch(tmpc_handle *h) {
@@ -604,6 +626,56 @@ thread_local LpArena g_lp_arena;
 size_t lp_round(size_t bytes) { return (bytes + 255) / 256 * 256; }
 }  // namespace
 
+namespace {
+// Uploads the condensed variant(s) of a new handle to HIP device `device` (stream, work counters, timing events, kernel layouts),
+// or, for device < 0, lays out the host-only copies; shared by tmpc_create and tmpc_create_regulator.  `p` carries what the
+// layouts read beyond the condensed QP (A, B, tol, max_iter).
+int setup_handle(tmpc_handle *h, const tmpc_problem &pp, int device) {
+    const tmpc_problem *p = &pp;
+    int rc = TMPC_OK;
+    if (rc == TMPC_OK && device >= 0) {
+        hipError_t e = hipSetDevice(device);
+        hipDeviceProp_t prop;
+        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
+        if (e != hipSuccess) {
+            h->err = std::string("tmpc_create: no usable HIP device: ") + hipGetErrorString(e);
+            rc = TMPC_E_DEVICE;
+        } else {
+            h->n_cu = prop.multiProcessorCount;
+            auto setup = [&]() -> int {
+                HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+                h->wc.size = 4096;
+                HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->wc.ring), h->wc.size * sizeof(unsigned long long)));
+                HIP_TRY(h, hipMemset(h->wc.ring, 0, h->wc.size * sizeof(unsigned long long)));
+                for (int i = 0; i < 256; ++i) {       // timing events are created up front, not in the solve path
+                    hipEvent_t a = nullptr, b = nullptr;
+                    HIP_TRY(h, hipEventCreate(&a));
+                    HIP_TRY(h, hipEventCreate(&b));
+                    h->pool.emplace_back(a, b);
+                }
+                for (int k = 0; k < h->nvariants; ++k) {
+                    int r2 = upload_variant(h, h->v[k], *p);
+                    if (r2) return r2;
+                }
+                return TMPC_OK;
+            };
+            rc = setup();
+        }
+    }
+    if (rc == TMPC_OK && device < 0) {
+        // host-only handle: the layouts are laid out for the debug dumps only.  A problem no kernel covers (nv > 128) still
+        // gets its handle -- tmpc_get_condensed and the oracle-side tests use it -- and the dump calls answer UNSUPPORTED
+        // (wave_ok = false, tiles = 0).
+        for (int k = 0; k < h->nvariants && rc == TMPC_OK; ++k) {
+            rc = upload_variant(h, h->v[k], *p);
+            if (rc == TMPC_E_UNSUPPORTED) { rc = TMPC_OK; h->err.clear(); }
+        }
+    }
+    return rc;
+}
+
+}  // namespace
+
 extern "C" {
 
 int tmpc_abi_version(void) { return TMPC_ABI_VERSION; }
@@ -631,46 +703,53 @@ int tmpc_create(const tmpc_problem *p, int device, tmpc_handle **out) {
             const std::string msg = tmpc::condense(*p, k, h->v[k].c);
             if (!msg.empty()) { h->err = "tmpc_create: " + msg; rc = TMPC_E_INVALID; }
         }
-        if (rc == TMPC_OK && device >= 0) {
-            hipError_t e = hipSetDevice(device);
-            hipDeviceProp_t prop;
-            if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-            if (e != hipSuccess) {
-                h->err = std::string("tmpc_create: no usable HIP device: ") + hipGetErrorString(e);
-                rc = TMPC_E_DEVICE;
-            } else {
-                h->n_cu = prop.multiProcessorCount;
-                auto setup = [&]() -> int {
-                    HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-                    h->wc.size = 4096;
-                    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->wc.ring), h->wc.size * sizeof(unsigned long long)));
-                    HIP_TRY(h, hipMemset(h->wc.ring, 0, h->wc.size * sizeof(unsigned long long)));
-                    for (int i = 0; i < 256; ++i) {       // timing events are created up front, not in the solve path
-                        hipEvent_t a = nullptr, b = nullptr;
-                        HIP_TRY(h, hipEventCreate(&a));
-                        HIP_TRY(h, hipEventCreate(&b));
-                        h->pool.emplace_back(a, b);
-                    }
-                    for (int k = 0; k < h->nvariants; ++k) {
-                        int r2 = upload_variant(h, h->v[k], *p);
-                        if (r2) return r2;
-                    }
-                    return TMPC_OK;
-                };
-                rc = setup();
-            }
-        }
-        if (rc == TMPC_OK && device < 0) {
-            // host-only handle: the layouts are laid out for the debug dumps only.  A problem no kernel covers (nv > 128) still
-            // gets its handle -- tmpc_get_condensed and the oracle-side tests use it -- and the dump calls answer UNSUPPORTED
-            // (wave_ok = false, tiles = 0).
-            for (int k = 0; k < h->nvariants && rc == TMPC_OK; ++k) {
-                rc = upload_variant(h, h->v[k], *p);
-                if (rc == TMPC_E_UNSUPPORTED) { rc = TMPC_OK; h->err.clear(); }
-            }
-        }
+        if (rc == TMPC_OK) rc = setup_handle(h, *p, device);
     } catch (const std::exception &ex) {
         h->err = std::string("tmpc_create: ") + ex.what();
+        rc = TMPC_E_NOMEM;
+    }
+    if (rc != TMPC_OK) {
+        g_create_error = h->err;
+        tmpc_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return TMPC_OK;
+}
+
+int tmpc_create_regulator(const tmpc_regulator_problem *p, int device, tmpc_handle **out) {
+    if (!p || !out) { g_create_error = "tmpc_create_regulator: NULL argument"; return TMPC_E_INVALID; }
+    *out = nullptr;
+    if (p->nx <= 0 || p->nu <= 0 || p->N <= 0 || p->nx > 16) {
+        g_create_error = "tmpc_create_regulator: need 0 < nx <= 16, nu > 0, N > 0";
+        return TMPC_E_INVALID;
+    }
+    tmpc_handle *h = new (std::nothrow) tmpc_handle();
+    if (!h) { g_create_error = "out of memory"; return TMPC_E_NOMEM; }
+    h->device = device; h->nx = p->nx; h->nu = p->nu; h->N = p->N;
+    h->regulator = true;
+    h->reg_tube = p->tube ? 1 : 0;
+    h->nvariants = 1;
+    int rc = TMPC_OK;
+    try {
+        const std::string msg = tmpc::condense_regulator(*p, h->v[0].c);
+        if (!msg.empty()) { h->err = "tmpc_create_regulator: " + msg; rc = TMPC_E_INVALID; }
+        if (rc == TMPC_OK) {
+            const size_t nx = p->nx, nu = p->nu;
+            h->hA.assign(p->A, p->A + nx * nx);
+            h->hB.assign(p->B, p->B + nx * nu);
+            h->hQ.assign(p->Q, p->Q + nx * nx);
+            h->hR.assign(p->R, p->R + nu * nu);
+            if (p->K) h->hK.assign(p->K, p->K + nu * nx);
+            // what the kernel layouts read beyond the condensed QP
+            tmpc_problem q{};
+            q.nx = p->nx; q.nu = p->nu; q.N = p->N;
+            q.max_iter = p->max_iter; q.tol = p->tol;
+            q.A = p->A; q.B = p->B;
+            rc = setup_handle(h, q, device);
+        }
+    } catch (const std::exception &ex) {
+        h->err = std::string("tmpc_create_regulator: ") + ex.what();
         rc = TMPC_E_NOMEM;
     }
     if (rc != TMPC_OK) {
@@ -694,7 +773,7 @@ void tmpc_destroy(tmpc_handle *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_staging(h);
     {
-        void *wsp[] = {h->blk_ws, h->mc_arena, h->wc.ring, h->d_ticks, h->save_buf};
+        void *wsp[] = {h->blk_ws, h->mc_arena, h->wc.ring, h->d_ticks, h->save_buf, h->reg_zero};
         for (void *q2 : wsp) if (q2) (void)hipFree(q2);
     }
     for (int k = 0; k < 2; ++k)
@@ -707,17 +786,24 @@ void tmpc_destroy(tmpc_handle *h) {
 int tmpc_solve_batch_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
                             double *u_nom, double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters) {
     if (!h) return TMPC_E_INVALID;
-    if (B < 0 || !x_k || !ref || !u_nom || !status || !iters) { h->err = "tmpc_solve_batch_device: NULL argument"; return TMPC_E_INVALID; }
+    if (B < 0 || !x_k || (!ref && !h->regulator) || !u_nom || !status || !iters) { h->err = "tmpc_solve_batch_device: NULL argument"; return TMPC_E_INVALID; }
+    if (h->regulator && (xu_ss || variant)) { h->err = "tmpc_solve_batch_device: a regulator handle has no steady state and one problem (xu_ss, variant must be NULL)"; return TMPC_E_INVALID; }
     if (B == 0) return TMPC_OK;
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
     HIP_TRY(h, hipSetDevice(h->device));
+    if (h->regulator) {
+        const int rz = ensure_reg_zero(h, B);
+        if (rz) return rz;
+        ref = h->reg_zero;
+    }
     return enqueue(h, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters);
 }
 
 int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
                      double *u_nom, double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters) {
     if (!h) return TMPC_E_INVALID;
-    if (B < 0 || !x_k || !ref || !u_nom || !status || !iters) { h->err = "tmpc_solve_batch: NULL argument"; return TMPC_E_INVALID; }
+    if (B < 0 || !x_k || (!ref && !h->regulator) || !u_nom || !status || !iters) { h->err = "tmpc_solve_batch: NULL argument"; return TMPC_E_INVALID; }
+    if (h->regulator && (xu_ss || variant)) { h->err = "tmpc_solve_batch: a regulator handle has no steady state and one problem (xu_ss, variant must be NULL)"; return TMPC_E_INVALID; }
     if (B == 0) return TMPC_OK;
     if (variant)
         for (int64_t i = 0; i < B; ++i)
@@ -726,16 +812,18 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double 
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_staging(h, B);
     if (rc) return rc;
+    if (h->regulator && (rc = ensure_reg_zero(h, B))) return rc;
+    double *const d_ref = h->regulator ? h->reg_zero : h->d_r;      // (regulator: ref is ignored)
     const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(B);
     if (h->stage_pin != nullptr) {
         // through the pinned mirror: one DMA in, one out
         char *pin_in = h->stage_pin, *pin_out = h->stage_pin + h->stage_in_bytes;
         std::memcpy(pin_in, x_k, b * nx * sizeof(double));
-        std::memcpy(pin_in + h->off_r, ref, b * nx * sizeof(double));
+        if (!h->regulator) std::memcpy(pin_in + h->off_r, ref, b * nx * sizeof(double));
         size_t in_bytes = h->off_r + b * nx * sizeof(double);
         if (variant) { std::memcpy(pin_in + h->off_var, variant, b); in_bytes = h->off_var + b; }
         HIP_TRY(h, hipMemcpyAsync(h->stage_dev, pin_in, in_bytes, hipMemcpyHostToDevice, h->stream));
-        rc = enqueue(h, B, h->d_x, h->d_r, variant ? h->d_var : nullptr, h->d_u, h->d_x0, h->d_ss, x_nom ? h->d_xn : nullptr,
+        rc = enqueue(h, B, h->d_x, d_ref, variant ? h->d_var : nullptr, h->d_u, h->d_x0, h->d_ss, x_nom ? h->d_xn : nullptr,
                      h->d_st, h->d_it);
         if (rc) return rc;
         const size_t out_bytes = x_nom ? h->off_xn + b * (N + 1) * nx * sizeof(double) : h->off_it + b * sizeof(int32_t);
@@ -750,9 +838,9 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double 
         return TMPC_OK;
     }
     HIP_TRY(h, hipMemcpyAsync(h->d_x, x_k, b * nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_r, ref, b * nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!h->regulator) HIP_TRY(h, hipMemcpyAsync(h->d_r, ref, b * nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (variant) HIP_TRY(h, hipMemcpyAsync(h->d_var, variant, b, hipMemcpyHostToDevice, h->stream));
-    rc = enqueue(h, B, h->d_x, h->d_r, variant ? h->d_var : nullptr, h->d_u, h->d_x0, h->d_ss, x_nom ? h->d_xn : nullptr,
+    rc = enqueue(h, B, h->d_x, d_ref, variant ? h->d_var : nullptr, h->d_u, h->d_x0, h->d_ss, x_nom ? h->d_xn : nullptr,
                  h->d_st, h->d_it);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(u_nom, h->d_u, b * N * nu * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -970,6 +1058,7 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
     if (!h) return TMPC_E_INVALID;
     const bool host_draws = rp != nullptr || !h->mc_rng_on;
     if (B < 0 || T < 0 || !p_loss || !ref || (host_draws && (!th_u || !ga_u || !w)) || (rZ > 0 && (!HZ || !hZ))) { h->err = "tmpc_mc_run: NULL argument"; return TMPC_E_INVALID; }
+    if (h->regulator) { h->err = "tmpc_mc_run: a regulator handle runs its loop with tmpc_reg_run"; return TMPC_E_INVALID; }
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
     if (extended && h->nvariants < 2) { h->err = "tmpc_mc_run: extended loop needs a problem created with extended = 1"; return TMPC_E_INVALID; }
     if (h->hK.empty() || h->hKanc.empty()) { h->err = "tmpc_mc_run: the problem description carries no gains K / K_anc"; return TMPC_E_INVALID; }
@@ -1250,6 +1339,125 @@ int tmpc_mc_replay(tmpc_handle *h, int64_t B, int32_t T, int extended, const dou
     McReplay rp{U_pkt, xn0_pkt, trace_f, trace_i};
     return mc_run_impl(h, B, T, extended, pl.data(), ref.data(), th.data(), ga.data(), w, x0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
                        nullptr, nullptr, nullptr, &rp);
+}
+
+int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const double *w,
+                 const double *HX, const double *hX, int32_t rX, const double *HU, const double *hU, int32_t rU,
+                 const double *HZ, const double *hZ, int32_t rZ,
+                 double *cost, int32_t *x_viol, int32_t *u_viol, int32_t *tube_viol, int32_t *not_optimal, int32_t *fail_step,
+                 double *x_final, int32_t *iters_sum, int64_t capture, double *cap_x, double *cap_xn, double *cap_u) {
+    if (!h) return TMPC_E_INVALID;
+    if (!h->regulator) { h->err = "tmpc_reg_run: needs a regulator handle (tmpc_create_regulator); tracking handles run tmpc_mc_run"; return TMPC_E_INVALID; }
+    if (B < 0 || T < 0 || !x0 || rX < 0 || rU < 0 || rZ < 0 || (rX > 0 && (!HX || !hX)) || (rU > 0 && (!HU || !hU)) || (rZ > 0 && (!HZ || !hZ))) {
+        h->err = "tmpc_reg_run: NULL argument or negative count";
+        return TMPC_E_INVALID;
+    }
+    if (h->reg_tube && h->hK.empty()) { h->err = "tmpc_reg_run: the tube regulator needs its gain K"; return TMPC_E_INVALID; }
+    if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
+    if (h->nu > 16) { h->err = "tmpc_reg_run: nu <= 16"; return TMPC_E_UNSUPPORTED; }
+    if (B == 0 || T == 0) return TMPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_staging(h, B);
+    if (rc) return rc;
+    if ((rc = ensure_reg_zero(h, B))) return rc;
+    const size_t nx = h->nx, nu = h->nu, b = static_cast<size_t>(B), t_ = static_cast<size_t>(T);
+    const bool host_w = w != nullptr, want_cap = capture >= 0 && capture < B && cap_x && cap_xn && cap_u;
+    // the state lives in the closed loop's grow-only arena (tmpc_mc_run's records there are gone from here on)
+    auto r256 = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t need = r256(8 * nx * nx) * 2 + r256(8 * nx * nu) + r256(8 * nu * nu) + r256(8 * nu * nx) + r256(8 * nx) +
+                        r256(8 * static_cast<size_t>(rX) * (nx + 1)) + r256(8 * static_cast<size_t>(rU) * (nu + 1)) +
+                        r256(8 * static_cast<size_t>(rZ) * (nx + 1)) + 6 * 256 + r256(8 * b * nx) + r256(8 * b) + 6 * r256(4 * b) +
+                        (host_w ? r256(8 * b * t_ * nx) : 0) + (want_cap ? r256(8 * (t_ + 1) * nx) + r256(8 * t_ * nx) + r256(8 * t_ * nu) : 0);
+    h->mc_cap_dev = nullptr; h->mc_cap_T = 0;
+    h->mc_err2_phys = nullptr; h->mc_phys_B = 0;
+    h->mc_tick_sum = h->mc_tick_max = nullptr; h->mc_tick_B = 0;
+    if (need > h->mc_arena_bytes) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->mc_arena) (void)hipFree(h->mc_arena);
+        h->mc_arena = nullptr;
+        h->mc_arena_bytes = 0;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->mc_arena), need));
+        h->mc_arena_bytes = need;
+    }
+    size_t arena_off = 0;
+    auto dalloc = [&](size_t bytes, void **o) -> int {
+        const size_t sz = r256(bytes ? bytes : 8);
+        if (arena_off + sz > h->mc_arena_bytes) { h->err = "tmpc_reg_run: internal arena too small"; return TMPC_E_NOMEM; }
+        *o = h->mc_arena + arena_off;
+        arena_off += sz;
+        return TMPC_OK;
+    };
+    auto up = [&](const void *src, size_t bytes, const double **o) -> int {
+        void *q = nullptr;
+        int r2 = dalloc(bytes, &q);
+        if (r2) return r2;
+        if (bytes) HIP_TRY(h, hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream));
+        *o = static_cast<const double *>(q);
+        return TMPC_OK;
+    };
+    auto run = [&]() -> int {
+        tmpc::RegModel m{};
+        tmpc::RegState st{};
+        m.nx = h->nx; m.nu = h->nu; m.N = h->N; m.tube = h->reg_tube;
+        m.rX = rX; m.rU = rU; m.rZ = rZ;
+        int r2;
+        if ((r2 = up(h->hA.data(), 8 * nx * nx, &m.A))) return r2;
+        if ((r2 = up(h->hB.data(), 8 * nx * nu, &m.B))) return r2;
+        if ((r2 = up(h->hQ.data(), 8 * nx * nx, &m.Q))) return r2;
+        if ((r2 = up(h->hR.data(), 8 * nu * nu, &m.R))) return r2;
+        if ((r2 = up(h->hK.data(), 8 * h->hK.size(), &m.K))) return r2;
+        if ((r2 = up(HX, 8 * static_cast<size_t>(rX) * nx, &m.HX))) return r2;
+        if ((r2 = up(hX, 8 * static_cast<size_t>(rX), &m.hX))) return r2;
+        if ((r2 = up(HU, 8 * static_cast<size_t>(rU) * nu, &m.HU))) return r2;
+        if ((r2 = up(hU, 8 * static_cast<size_t>(rU), &m.hU))) return r2;
+        if ((r2 = up(HZ, 8 * static_cast<size_t>(rZ) * nx, &m.HZ))) return r2;
+        if ((r2 = up(hZ, 8 * static_cast<size_t>(rZ), &m.hZ))) return r2;
+        if ((r2 = dalloc(8 * b * nx, reinterpret_cast<void **>(&st.x)))) return r2;
+        HIP_TRY(h, hipMemcpyAsync(st.x, x0, 8 * b * nx, hipMemcpyHostToDevice, h->stream));
+        if ((r2 = dalloc(8 * b, reinterpret_cast<void **>(&st.cost)))) return r2;
+        HIP_TRY(h, hipMemsetAsync(st.cost, 0, 8 * b, h->stream));
+        int32_t **counters[] = {&st.x_viol, &st.u_viol, &st.tube_viol, &st.not_optimal, &st.fail_step, &st.iters_sum};
+        for (int32_t **c : counters) {
+            if ((r2 = dalloc(4 * b, reinterpret_cast<void **>(c)))) return r2;
+            HIP_TRY(h, hipMemsetAsync(*c, c == &st.fail_step ? 0xFF : 0, 4 * b, h->stream));      // (0xFF bytes: fail_step = -1)
+        }
+        if (host_w) {
+            if ((r2 = up(w, 8 * b * t_ * nx, &st.w))) return r2;
+        } else if (h->mc_rng_on) {
+            st.rng_on = 1;
+            st.rng_seed = h->mc_rng_seed;
+            st.rng_first = h->mc_rng_first;
+            if ((r2 = up(h->mc_w_bound.data(), 8 * nx, &st.w_bound))) return r2;
+        }
+        st.cap_index = -1;
+        if (want_cap) {
+            if ((r2 = dalloc(8 * (t_ + 1) * nx, reinterpret_cast<void **>(&st.cap_x)))) return r2;
+            if ((r2 = dalloc(8 * t_ * nx, reinterpret_cast<void **>(&st.cap_xn)))) return r2;
+            if ((r2 = dalloc(8 * t_ * nu, reinterpret_cast<void **>(&st.cap_u)))) return r2;
+            HIP_TRY(h, hipMemcpyAsync(st.cap_x, x0 + static_cast<size_t>(capture) * nx, 8 * nx, hipMemcpyHostToDevice, h->stream));
+            st.cap_index = capture;
+        }
+        // per step: the solve launch over all trajectories (x_k = the state, in place), then the step kernel
+        for (int t = 0; t < T; ++t) {
+            if ((r2 = enqueue(h, B, st.x, h->reg_zero, nullptr, h->d_u, h->d_x0, nullptr, nullptr, h->d_st, h->d_it))) return r2;
+            HIP_TRY(h, tmpc::launch_reg_step(m, st, t, T, B, h->d_u, h->d_x0, h->d_st, h->d_it, h->stream));
+        }
+        if (cost) HIP_TRY(h, hipMemcpyAsync(cost, st.cost, 8 * b, hipMemcpyDeviceToHost, h->stream));
+        int32_t *outs[] = {x_viol, u_viol, tube_viol, not_optimal, fail_step, iters_sum};
+        for (int k = 0; k < 6; ++k)
+            if (outs[k]) HIP_TRY(h, hipMemcpyAsync(outs[k], *counters[k], 4 * b, hipMemcpyDeviceToHost, h->stream));
+        if (x_final) HIP_TRY(h, hipMemcpyAsync(x_final, st.x, 8 * b * nx, hipMemcpyDeviceToHost, h->stream));
+        if (want_cap) {
+            HIP_TRY(h, hipMemcpyAsync(cap_x, st.cap_x, 8 * (t_ + 1) * nx, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(cap_xn, st.cap_xn, 8 * t_ * nx, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(cap_u, st.cap_u, 8 * t_ * nu, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return TMPC_OK;
+    };
+    rc = run();
+    if (rc != TMPC_OK) (void)hipStreamSynchronize(h->stream);
+    return rc;
 }
 
 int tmpc_synchronize(tmpc_handle *h) {

@@ -68,4 +68,11 @@ struct Condensed {
 // success, otherwise an error message.
 std::string condense(const tmpc_problem &p, int variant, Condensed &out);
 
+// The regulator QPs (include/tmpc.h: tmpc_regulator_problem): nth = 0, F2 = 0, z = [u_0 .. u_{N-1}] (plain, x_0 = x_k) or
+// [u_0 .. u_{N-1} | x_0] (tube).  u stays first and x_0 behind it, as in the tracking layout: the kernels read their outputs
+// from z_full at 0 (u) and off_x0.  Same row handling as condense() (rows on x_k alone become parameter rows; one block of
+// many rows of small rank -- the initial-state rows HZ (x_k - x_0), or the terminal rows Hf x_N, both of rank nx -- may be
+// kept factored).  Returns "" on success, otherwise an error message.
+std::string condense_regulator(const tmpc_regulator_problem &p, Condensed &out);
+
 }  // namespace tmpc

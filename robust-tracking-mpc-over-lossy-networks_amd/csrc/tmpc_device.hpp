@@ -195,6 +195,30 @@ hipError_t launch_solve_mc_step(const DeviceQP &qp, const KernelShape &shape, in
 // resident waves of the persistent grid of a shape (work items in flight): the host's choice between one fused launch and T launches
 int resident_waves(const KernelShape &shape, int n_cu);
 
+// Closed loop of the regulator handles (tmpc_reg.hip, include/tmpc.h: tmpc_reg_run): one step kernel launch per time step behind
+// the solve launch; a wave per trajectory.
+struct RegModel {
+    int nx, nu, N, tube;
+    int rX, rU, rZ;                      // rows of the three check sets (0: no check)
+    const double *A, *B, *Q, *R, *K;     // model, weights, ancillary gain (K: tube only)
+    const double *HX, *hX, *HU, *hU, *HZ, *hZ;
+};
+struct RegState {                        // [trajectory]-major device arrays
+    double *x;                           // plant state = the next solve's x_k                          [B][nx]
+    double *cost;                        // sum_t x'Qx + u'Ru                                           [B]
+    int32_t *x_viol, *u_viol, *tube_viol, *not_optimal, *fail_step, *iters_sum;     //                  [B]
+    const double *w;                     // host-given disturbances [B][T][nx], or nullptr
+    // device generator (tmpc_mc_set_device_rng; w == nullptr): the disturbance of tmpc_mc_run's stream, see McState
+    int rng_on;
+    unsigned long long rng_seed;
+    long long rng_first;
+    const double *w_bound;               // [nx]
+    long long cap_index;                 // recorded trajectory (-1: none)
+    double *cap_x, *cap_xn, *cap_u;      // [T+1][nx], [T][nx], [T][nu]
+};
+hipError_t launch_reg_step(const RegModel &m, const RegState &st, int t, int T, int64_t B, const double *u_nom, const double *x_nom0,
+                           const int32_t *status, const int32_t *iters, hipStream_t stream);
+
 // LP kernel (tmpc_lp.hip): rows scaled to unit norm, h scaled by hm so that max |h| = 1
 struct LpDevice {
     int d, nr, nrp;       // dimension, rows, row stride (multiple of 64)
