@@ -4,9 +4,10 @@ code."""
 from __future__ import annotations
 
 import numpy as np
+from scipy.optimize import linprog, nnls
 
 import common  # noqa: F401  (sys.path)
-from LinearMPCOverNetworks import workloads
+from LinearMPCOverNetworks import _native, workloads
 from LinearMPCOverNetworks.polytope_lite import Polytope
 from LinearMPCOverNetworks.RegulatorMPC import RegulatorMPC
 from LinearMPCOverNetworks.TubeRegulatorMPC import TubeRegulatorMPC
@@ -111,3 +112,73 @@ class SparseQP:
         base = self.rows(z, xk)
         J = np.stack([self.rows(z + e, xk) - base for e in np.eye(self.nv)], axis=1) if base.size else np.zeros((0, self.nv))
         return np.abs(J).max(axis=1, initial=0.0) > 1e-12 if base.size else np.zeros(0, bool)
+
+
+# ------------------------------------------------------------- checks of the solves and of the closed loop (the GPU tests)
+def row_jacobian(sp):
+    """The rows are affine in z: rows(z, x_k) = J z + rows(0, x_k)."""
+    xk = np.zeros(sp.nx)
+    base = sp.rows(np.zeros(sp.nv), xk)
+    return np.stack([sp.rows(e, xk) - base for e in np.eye(sp.nv)], axis=1)
+
+
+def feasible(sp, J, xk):
+    """Is the sparse QP feasible at x_k?  (an LP in z over its rows)"""
+    base = sp.rows(np.zeros(sp.nv), xk)
+    r = linprog(np.zeros(sp.nv), A_ub=J, b_ub=-base, bounds=[(None, None)] * sp.nv, method="highs")
+    return r.status == 0
+
+
+def kkt(sp, J, z, xk):
+    """(max primal violation, stationarity residual) of z on the sparse QP, multipliers by NNLS on the near-active rows."""
+    base = sp.rows(np.zeros(sp.nv), xk)
+    s = sp.rows(z, xk)
+    g = sp.cost_gradient(z, xk)
+    act = s >= -1e-7 * (1 + np.abs(base)) if s.size else np.zeros(0, bool)
+    if act.any():
+        lam, _ = nnls(J[act].T, -g)
+        res = g + J[act].T @ lam
+    else:
+        res = g
+    viol = float(np.max(s, initial=-np.inf)) if s.size else 0.0
+    return viol, float(np.max(np.abs(res))) / (1.0 + float(np.max(np.abs(g))))
+
+
+def host_loop(m, x0, w, sets, K):
+    """The loop of Example_of_Tube_Regulator_MPC.py in numpy around per-step batch solves (tmpc_solve_batch)."""
+    B, T, nx = w.shape
+    x = x0.copy()
+    res = dict(cost=np.zeros(B), x_viol=np.zeros(B, np.int32), u_viol=np.zeros(B, np.int32), tube_viol=np.zeros(B, np.int32),
+               not_optimal=np.zeros(B, np.int32), fail_step=np.full(B, -1, np.int32), iters_sum=np.zeros(B, np.int32))
+    xs, xns, us = [x[0].copy()], [], []
+    viol = lambda P, v: np.any(v @ P.A.T - P.b > 1e-7, axis=1)      # noqa: E731
+    for t in range(T):
+        out = _native.solve_regulator_batch(m._handle, np.ascontiguousarray(x), want_traj=False)
+        alive = res["fail_step"] < 0
+        st = out["status"]
+        res["iters_sum"] += np.where(alive, out["iters"], 0)
+        res["not_optimal"] += (alive & (st != 0))
+        newly = alive & (st >= 2)
+        res["fail_step"][newly] = t
+        go = alive & ~newly
+        xn = out["x_nom0"]
+        u = out["u_nom"][:, 0, :] - ((x - xn) @ K.T if K is not None else 0.0)
+        res["cost"] += np.where(go, np.einsum("bi,ij,bj->b", x, m._Q, x) + np.einsum("bi,ij,bj->b", u, m._R, u), 0.0)
+        for key, P, v in (("x_viol", sets.get("X"), x), ("u_viol", sets.get("U"), u), ("tube_viol", sets.get("Z"), x - xn)):
+            if P is not None:
+                res[key] += go & viol(P, v)
+        xp = x @ m._A.T + u @ m._B.T + w[:, t]
+        x = np.where(go[:, None], xp, x)
+        xs.append(x[0].copy()); xns.append(xn[0].copy()); us.append(u[0].copy())
+    res["x_final"] = x
+    res["x_traj"], res["x_nom_traj"], res["u_traj"] = np.array(xs), np.array(xns), np.array(us)
+    return res
+
+
+def compare_loops(dev, host):
+    assert np.all(np.abs(dev["x_final"] - host["x_final"]) <= 1e-12 * (1 + np.abs(host["x_final"])))
+    assert np.all(np.abs(dev["cost"] - host["cost"]) <= 1e-12 * (1 + np.abs(host["cost"])))
+    for k in ("x_viol", "u_viol", "tube_viol", "not_optimal", "fail_step", "iters_sum"):
+        assert np.array_equal(dev[k], host[k]), k
+    for k in ("x_traj", "x_nom_traj", "u_traj"):
+        assert np.allclose(dev[k], host[k], rtol=1e-12, atol=1e-12, equal_nan=True), k

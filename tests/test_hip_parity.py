@@ -324,7 +324,23 @@ def test_config5_synthetic_n12_m4_N30(hip_lib, oracle_lib):
     np.testing.assert_allclose(out["x_nom"][ok], ref["x_nom"][ok], atol=1e-8, rtol=0)
 
 
-@pytest.mark.parametrize("name,fixed,horizons", [("cartpole", True, (3, 6, 9, 12, 15)),
+def _w(*shape):
+    return "tmpc::solve_kernel<" + ",".join(map(str, shape)) + ">"
+
+
+# what each sweep reaches: (workload, fixed x_0, horizons) -> kernel instantiations
+SWEEP_KERNELS = {
+    ("cartpole", True, (3, 6, 9, 11, 12, 15)): {"tmpc::solve_block_kernel<1>", _w(11, 1, 0, 5, 4, 0, 8), _w(12, 1, 0, 5, 4, 0, 8),
+                                                _w(22, 2, 0, 5, 4, 0, 4)},
+    ("cartpole", True, (17, 20, 23, 26)): {_w(22, 2, 0, 5, 4, 0, 4), _w(24, 2, 0, 5, 4, 0, 4), "tmpc::solve_block_kernel<2>"},
+    ("double_integrator", False, (3, 5, 8, 11, 14)): {_w(8, 0, 2, 0, 0, 0, 8), _w(12, 0, 2, 0, 0, 0, 8), _w(16, 0, 4, 0, 0, 0, 4),
+                                                      "tmpc::solve_block_kernel<2>"},
+    ("double_integrator_darup", False, (4, 7, 10)): {_w(8, 0, 2, 0, 0, 0, 8), _w(12, 0, 2, 0, 0, 0, 8), _w(16, 0, 2, 0, 0, 0, 4)},
+    ("double_integrator", True, (4, 9, 13)): {_w(8, 0, 2, 0, 0, 0, 8), _w(12, 0, 2, 0, 0, 0, 8), _w(16, 0, 2, 0, 0, 0, 4)},
+}
+
+
+@pytest.mark.parametrize("name,fixed,horizons", [("cartpole", True, (3, 6, 9, 11, 12, 15)),
                                                   ("cartpole", True, (17, 20, 23, 26)),
                                                   ("double_integrator", False, (3, 5, 8, 11, 14)),
                                                   ("double_integrator_darup", False, (4, 7, 10)),
@@ -337,7 +353,8 @@ def test_horizon_sweep_covers_the_kernel_shapes(hip_lib, oracle_lib, name, fixed
     for N in horizons:
         mpc, w = common.make_mpc(name, N, fixed, create=True)
         nv, nc, _ = hip_lib.get_dims(mpc._handle)
-        seen.add((mpc.get_kernel_path(), nv))
+        seen.add(hip_lib.kernel_name(mpc._handle))
+        assert mpc.get_kernel_path() == ("block" if "block" in hip_lib.kernel_name(mpc._handle) else "wave")
         nx = w["A"].shape[0]
         if name == "cartpole":
             idx = rng.integers(0, len(S), 48)
@@ -354,7 +371,7 @@ def test_horizon_sweep_covers_the_kernel_shapes(hip_lib, oracle_lib, name, fixed
         np.testing.assert_allclose(out["u_nom"][ok], ref["u_nom"][ok], atol=ATOL_U, rtol=0, err_msg=f"N={N}")
         np.testing.assert_allclose(out["xu_ss"][ok], ref["xu_ss"][ok], atol=ATOL_SS, rtol=0, err_msg=f"N={N}")
         np.testing.assert_allclose(out["x_nom"][ok], ref["x_nom"][ok], atol=1e-8, rtol=0, err_msg=f"N={N}")
-    assert len(seen) >= 2
+    assert seen == SWEEP_KERNELS[(name, fixed, horizons)], sorted(seen)
 
 
 @pytest.mark.gpu

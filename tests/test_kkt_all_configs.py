@@ -19,61 +19,11 @@ import numpy as np
 import pytest
 
 import common
-from oracle import qp_sparse
+from certificates import boundary_states, certify
 
 pytestmark = pytest.mark.gpu
 
 S = np.load(os.path.join(common.GOLDEN, "cartpole_N10_states.npy"))
-TOL_STAT, TOL_FEAS = 1e-7, 1e-9
-# north_star's parity band is 1e-6 on u*_0; the residual-based certificate above scales with |q| (1e6 for the cart-pole)
-# and lets a 1e-6 shift of u_0 through, so every answer is also measured against the exact minimiser on its certified
-# active set (qp_sparse.minimiser_distance: a linear solve, no interior-point or refinement code involved)
-TOL_U0 = 1e-8
-
-
-def boundary_states(rng, hx_box, n, lo=0.9):
-    """States with one coordinate at lo..1.0 of the tightened box, the others anywhere inside."""
-    X = rng.uniform(-1, 1, (n, len(hx_box))) * hx_box
-    k = rng.integers(0, len(hx_box), n)
-    X[np.arange(n), k] = rng.choice([-1.0, 1.0], n) * rng.uniform(lo, 1.0, n) * hx_box[k]
-    return X
-
-
-def certify(mpc, X, R, variant=None, min_optimal=128, literal_check=None):
-    """Solves the batch on the GPU and certifies every answer; returns (n_optimal, n_infeasible)."""
-    p = mpc._problem_dict()
-    out = mpc._solve(X, R, variant)
-    var = np.zeros(len(X), np.uint8) if variant is None else np.broadcast_to(np.asarray(variant, np.uint8), (len(X),))
-    tpl = {v: qp_sparse.SparseTemplate(p, int(v)) for v in np.unique(var)}
-    st = out["status"]
-    assert np.all((st == 0) | (st == 2)), np.bincount(st)
-    worst = dict(r_stat=0.0, r_eq=0.0, r_ineq=0.0, du0=0.0)
-    n_inf = 0
-    for k in range(len(X)):
-        qp = tpl[var[k]].instance(X[k], R[k])
-        if st[k] == 2:
-            tight = dict(qp)
-            tight["h"] = qp["h"] - 1e-6 * np.maximum(1.0, np.abs(qp["h"]))       # borderline instances may go either way
-            assert qp_sparse.lp_infeasible(tight), f"instance {k}: library says infeasible, HiGHS finds a strictly feasible point"
-            assert np.all(np.isnan(out["u_nom"][k]))
-            n_inf += 1
-            continue
-        v = qp_sparse.pack(qp, out["x_nom"][k], out["u_nom"][k], out["x_ss"][k], out["u_ss"][k])
-        c = qp_sparse.kkt_certificate_fast(qp, v)
-        lam_scale = max(1.0, float(np.abs(c["lam"]).max())) if len(c["lam"]) else 1.0
-        assert c["r_eq"] < TOL_FEAS and c["r_ineq"] < TOL_FEAS and c["r_stat"] < TOL_STAT and c["min_lam"] >= -1e-9 * lam_scale, (k, c)
-        for key in ("r_stat", "r_eq", "r_ineq"):
-            worst[key] = max(worst[key], c[key])
-        d = qp_sparse.minimiser_distance(qp, v, active=c["active"])
-        assert d["certified"], (k, {a: d[a] for a in ("r_ineq", "min_mu", "r_stat", "resolution", "n_active")})
-        assert d["du0"] <= TOL_U0, (k, d["du0"], c["n_active"])
-        worst["du0"] = max(worst["du0"], d["du0"])
-        if literal_check is not None and var[k] == 1:
-            literal_check(out["x_ss"][k], out["u_ss"][k])
-    n_opt = int((st == 0).sum())
-    assert n_opt >= min_optimal, (n_opt, n_inf)
-    print(f"certified {n_opt} optimal (worst {worst}), {n_inf} infeasible by LP")
-    return n_opt, n_inf
 
 
 @pytest.mark.parametrize("N", [5, 10])

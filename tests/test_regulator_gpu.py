@@ -3,10 +3,8 @@ recursion, KKT certificates of the constrained solves on the sparse QP, wave = b
 against a host loop of per-step solves, and the tube guarantee of Mayne et al. over a Monte Carlo."""
 import numpy as np
 import pytest
-from scipy.optimize import linprog, nnls
 
 import regulator_problems as rp
-from LinearMPCOverNetworks import _native
 from LinearMPCOverNetworks.montecarlo import draw_realisations_philox
 
 pytestmark = pytest.mark.gpu
@@ -48,35 +46,6 @@ def test_unconstrained_regulator_is_the_riccati_solution(hip_lib):
         m._close()
 
 
-def _row_jacobian(sp):
-    """The rows are affine in z: rows(z, x_k) = J z + rows(0, x_k)."""
-    xk = np.zeros(sp.nx)
-    base = sp.rows(np.zeros(sp.nv), xk)
-    return np.stack([sp.rows(e, xk) - base for e in np.eye(sp.nv)], axis=1)
-
-
-def _feasible(sp, J, xk):
-    """Is the sparse QP feasible at x_k?  (an LP in z over its rows)"""
-    base = sp.rows(np.zeros(sp.nv), xk)
-    r = linprog(np.zeros(sp.nv), A_ub=J, b_ub=-base, bounds=[(None, None)] * sp.nv, method="highs")
-    return r.status == 0
-
-
-def _kkt(sp, J, z, xk):
-    """(max primal violation, stationarity residual) of z on the sparse QP, multipliers by NNLS on the near-active rows."""
-    base = sp.rows(np.zeros(sp.nv), xk)
-    s = sp.rows(z, xk)
-    g = sp.cost_gradient(z, xk)
-    act = s >= -1e-7 * (1 + np.abs(base)) if s.size else np.zeros(0, bool)
-    if act.any():
-        lam, _ = nnls(J[act].T, -g)
-        res = g + J[act].T @ lam
-    else:
-        res = g
-    viol = float(np.max(s, initial=-np.inf)) if s.size else 0.0
-    return viol, float(np.max(np.abs(res))) / (1.0 + float(np.max(np.abs(g))))
-
-
 def _states(kind, n, rng):
     if kind == "mayne_tube":
         return np.c_[rng.uniform(-9.0, 5.0, n), rng.uniform(-3.5, 2.5, n)]
@@ -94,15 +63,15 @@ def test_constrained_solves_carry_a_kkt_certificate(kind, hip_lib, mayne):
         z = out["u_nom"].reshape(len(xk), -1)
         if sp.tube:
             z = np.c_[z, out["x_nom0"]]
-        J = _row_jacobian(sp)
+        J = rp.row_jacobian(sp)
         patterns = set()
         for b in range(len(xk)):
-            feas = _feasible(sp, J, xk[b])
+            feas = rp.feasible(sp, J, xk[b])
             if not feas:
                 assert st[b] == 2 and np.all(np.isnan(out["u_nom"][b])), (b, xk[b], st[b])
                 continue
             assert st[b] == 0, (b, xk[b], st[b])
-            viol, stat = _kkt(sp, J, z[b], xk[b])
+            viol, stat = rp.kkt(sp, J, z[b], xk[b])
             assert viol <= 1e-9, (b, viol)
             assert stat <= 1e-8, (b, stat)
             patterns.add(tuple(np.flatnonzero(sp.rows(z[b], xk[b]) > -1e-7)))
@@ -155,46 +124,6 @@ def test_infeasible_states(hip_lib, mayne):
     assert x_mpc.shape == (2, 10) and u_mpc.shape == (1, 9)
 
 
-def _host_loop(m, x0, w, sets, K):
-    """The loop of Example_of_Tube_Regulator_MPC.py in numpy around per-step batch solves (tmpc_solve_batch)."""
-    B, T, nx = w.shape
-    x = x0.copy()
-    res = dict(cost=np.zeros(B), x_viol=np.zeros(B, np.int32), u_viol=np.zeros(B, np.int32), tube_viol=np.zeros(B, np.int32),
-               not_optimal=np.zeros(B, np.int32), fail_step=np.full(B, -1, np.int32), iters_sum=np.zeros(B, np.int32))
-    xs, xns, us = [x[0].copy()], [], []
-    viol = lambda P, v: np.any(v @ P.A.T - P.b > 1e-7, axis=1)      # noqa: E731
-    for t in range(T):
-        out = _native.solve_regulator_batch(m._handle, np.ascontiguousarray(x), want_traj=False)
-        alive = res["fail_step"] < 0
-        st = out["status"]
-        res["iters_sum"] += np.where(alive, out["iters"], 0)
-        res["not_optimal"] += (alive & (st != 0))
-        newly = alive & (st >= 2)
-        res["fail_step"][newly] = t
-        go = alive & ~newly
-        xn = out["x_nom0"]
-        u = out["u_nom"][:, 0, :] - ((x - xn) @ K.T if K is not None else 0.0)
-        res["cost"] += np.where(go, np.einsum("bi,ij,bj->b", x, m._Q, x) + np.einsum("bi,ij,bj->b", u, m._R, u), 0.0)
-        for key, P, v in (("x_viol", sets.get("X"), x), ("u_viol", sets.get("U"), u), ("tube_viol", sets.get("Z"), x - xn)):
-            if P is not None:
-                res[key] += go & viol(P, v)
-        xp = x @ m._A.T + u @ m._B.T + w[:, t]
-        x = np.where(go[:, None], xp, x)
-        xs.append(x[0].copy()); xns.append(xn[0].copy()); us.append(u[0].copy())
-    res["x_final"] = x
-    res["x_traj"], res["x_nom_traj"], res["u_traj"] = np.array(xs), np.array(xns), np.array(us)
-    return res
-
-
-def _compare(dev, host):
-    assert np.all(np.abs(dev["x_final"] - host["x_final"]) <= 1e-12 * (1 + np.abs(host["x_final"])))
-    assert np.all(np.abs(dev["cost"] - host["cost"]) <= 1e-12 * (1 + np.abs(host["cost"])))
-    for k in ("x_viol", "u_viol", "tube_viol", "not_optimal", "fail_step", "iters_sum"):
-        assert np.array_equal(dev[k], host[k]), k
-    for k in ("x_traj", "x_nom_traj", "u_traj"):
-        assert np.allclose(dev[k], host[k], rtol=1e-12, atol=1e-12, equal_nan=True), k
-
-
 def _mayne_starts(mayne, n, seed):
     rng = np.random.default_rng(seed)
     cand = np.c_[rng.uniform(-8.0, 4.0, 4 * n), rng.uniform(-3.0, 2.0, 4 * n)]
@@ -211,13 +140,13 @@ def test_device_loop_equals_host_loop_tube(hip_lib, mayne):
     w = np.random.default_rng(22).uniform(-0.1, 0.1, (B, T, 2))
     sets = {"X": mayne._X, "U": mayne._U, "Z": mayne._Z}
     dev = mayne.run_closed_loop(x0, T, w=w, capture=0)
-    host = _host_loop(mayne, x0, w, sets, mayne.get_controller_gain())
-    _compare(dev, host)
+    host = rp.host_loop(mayne, x0, w, sets, mayne.get_controller_gain())
+    rp.compare_loops(dev, host)
     # the device generator against its host twin
     _, _, wp = draw_realisations_philox(B, T, [0.1, 0.1], seed=77, first=1000)
     dev = mayne.run_closed_loop(x0, T, seed=77, first_trajectory=1000, capture=0)
-    host = _host_loop(mayne, x0, wp, sets, mayne.get_controller_gain())
-    _compare(dev, host)
+    host = rp.host_loop(mayne, x0, wp, sets, mayne.get_controller_gain())
+    rp.compare_loops(dev, host)
 
 
 def test_device_loop_equals_host_loop_plain(hip_lib):
@@ -228,9 +157,9 @@ def test_device_loop_equals_host_loop_plain(hip_lib):
         x0 = np.c_[rng.uniform(-9.0, 9.0, B), rng.uniform(-2.5, 2.5, B)]      # some start outside X: they fail at step 0
         w = rng.uniform(-0.05, 0.05, (B, T, 2))
         dev = m.run_closed_loop(x0, T, w=w, capture=0)
-        host = _host_loop(m, x0, w, {"X": m._X, "U": m._U}, None)
+        host = rp.host_loop(m, x0, w, {"X": m._X, "U": m._U}, None)
         assert np.any(host["fail_step"] >= 0) and np.any(host["fail_step"] < 0)
-        _compare(dev, host)
+        rp.compare_loops(dev, host)
     finally:
         m._close()
 
