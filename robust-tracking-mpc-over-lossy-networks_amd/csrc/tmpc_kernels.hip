@@ -53,7 +53,6 @@ namespace tmpc {
 namespace {
 
 using wv::WAVE;
-using wv::dpp_mov_d;
 using wv::fast_rcp;
 using wv::readlane_d;
 using wv::lanes_backsub_lane;
@@ -129,31 +128,13 @@ __device__ __forceinline__ void static_for(F &&f) {
     [&]<int... I>(std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, N>{});
 }
 
-// Sum each of acc[0..CNT) over the 64 lanes and leave the totals in out[0..CNT) (LDS).  Round: RR (<= 16) entries are
-// written as rows of a [RR][RED_STRIDE] LDS tile (lane l at column l + l/16); lane l then adds the 16-lane quarter (l & 3)
-// of entry (l >> 2) -- conflict free for RED_STRIDE = 68 -- and the four quarters, which sit in one quad, meet through two
-// DPP quad permutes.
-template <int CNT, int RR>
-__device__ __forceinline__ void wave_reduce_to_lds(const double (&acc)[CNT], double *red, double *out, int lane) {
-    const int e = lane >> 2, qd = lane & 3;
-    const int er = (RR < 16 && e >= RR) ? 0 : e;
-    const int wcol = lane + (lane >> 4);
-#pragma unroll
-    for (int c0 = 0; c0 < CNT; c0 += RR) {
-#pragma unroll
-        for (int k = 0; k < RR; ++k)
-            if (c0 + k < CNT) red[k * RED_STRIDE + wcol] = acc[c0 + k];
-        wave_lds_fence();
-        // (four partial sums: a chain of four dependent additions instead of sixteen)
-        double t4[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int j = 0; j < 16; ++j) t4[j & 3] += red[er * RED_STRIDE + qd * 17 + j];
-        double t = (t4[0] + t4[1]) + (t4[2] + t4[3]);
-        t += dpp_mov_d<0xB1>(t);
-        t += dpp_mov_d<0x4E>(t);
-        if (qd == 0 && e < RR && c0 + e < CNT) out[c0 + e] = t;
-        wave_lds_fence();
-    }
+// Sums over the wave of the iteration's per-lane accumulators (sweeps A and B, the dual residual): wv::swap_reduce_to_lds --
+// two halvings in registers by the cross-half swaps of gfx950, then one round of the [RR][RED_STRIDE] transposition tile for
+// ceil(CNT / 4) values per lane (two for the 52 values of sweep B at NV = 26).  Every shape takes it: none spills with it.
+template <class SH, int CNT>
+__device__ __forceinline__ void wave_sums_to_lds(const double (&acc)[CNT], double *red, double *out, int lane) {
+    static_assert(RED_STRIDE == wv::RED_STRIDE, "one tile layout");
+    wv::swap_reduce_to_lds<CNT, SH::RR>(acc, red, out, lane);
 }
 
 // packed lower triangle, column-major: (i,j), i >= j, at col_off(j) + i - j
@@ -370,10 +351,10 @@ __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const d
 // The FACTORED functionals: KC-wide left factor, so W = Hc' D Hc has only KT entries; one pass.
 template <class SH>
 __device__ __forceinline__ void sweep_a_factored(const double *Hct, const double (&s)[SH::RS], const double (&lam)[SH::RS],
-                                                 const double *rpw, double (&rs)[SH::RS], double &gap_l, double &rpn_l,
+                                                 const double *rpw, double (&rs)[SH::RS], double &gap_l, double &rpn_l, double obj_l,
                                                  double *red, double *csums, int lane) {
     constexpr int KC = SH::KC, KT = SH::KT, NCCP = SH::NCCP;
-    double acc[KT + KC + 1];   // initialised by the first slot's products; the last entry carries the wave's complementarity gap
+    double acc[KT + KC + 2];   // initialised by the first slot's products; the last two entries carry the wave's complementarity gap and objective
     static_for<SH::FC>([&](auto kc_) {
         constexpr int kc = decltype(kc_)::value;
         const int r = lane + kc * WAVE;
@@ -402,10 +383,11 @@ __device__ __forceinline__ void sweep_a_factored(const double *Hct, const double
             acc[KT + a] = kc == 0 ? hc[a] * t : fma(hc[a], t, acc[KT + a]);
         }
     });
-    // (the gap of ALL row sides of the lane rides along: a free place of the second round instead of a wave reduction of its
-    // own -- eight DPP moves, eight v_readlane and a dependent chain of a hundred and fifty cycles)
+    // (the gap of ALL row sides of the lane and the lane's term of the objective ride along instead of wave reductions of their
+    // own -- eight DPP moves, eight v_readlane and a dependent chain of a hundred and fifty cycles each)
     acc[KT + KC] = gap_l;
-    wave_reduce_to_lds<KT + KC + 1, SH::RR>(acc, red, csums, lane);
+    acc[KT + KC + 1] = obj_l;
+    wave_sums_to_lds<SH, KT + KC + 2>(acc, red, csums, lane);
 }
 
 // FUSED = true: the FUSED closed loop (tmpc_fused.hip).  An item of the work counter is then a TRAJECTORY: the wave that draws it
@@ -781,12 +763,24 @@ __device__ __forceinline__ void solve_body(
                     it_done = it;
                     STAMP(9);
                     TMPC_REFRESH();
+                    // cost gradient cg = Hs z + q (lane i computes entry i) and the lane's term of the objective
+                    // 1/2 z'Hs z + q'z = sum_i z_i (1/2 (cg_i - q_i) + q_i).  Nothing here depends on sweep A: issued ahead of it,
+                    // the broadcast reads' latency runs under its work, and the terms are summed with sweep A's totals
+                    double obj_l = 0.0;
+                    if (lane < NV) {
+                        double v = 0.0;
+#pragma unroll
+                        for (int j = 0; j < NV; ++j) v += Hs[lane * SH::LDH + j] * zv[j];
+                        const double qi = qv[lane], cgi = v + qi;
+                        cgv[lane] = cgi;
+                        obj_l = zv[lane] * (0.5 * (cgi - qi) + qi);
+                    }
                     // ---- sweep A: 1/s, weights, gap, |r_p|, G'DG (dense functionals by column blocks, factored ones as W), G'(d.r_p)
                     double gap_l = 0.0, rpn_l = 0.0;
                     if constexpr (FD > 0) sweep_a_dense<SH>(Gt, qp.nks, s, lam, rpw, rs, gap_l, rpn_l, dtw, Mf, sums, lane);
                     if constexpr (KC > 0) {
                         TMPC_REFRESH();
-                        sweep_a_factored<SH>(Hct, s, lam, rpw, rs, gap_l, rpn_l, red, csums, lane);
+                        sweep_a_factored<SH>(Hct, s, lam, rpw, rs, gap_l, rpn_l, obj_l, red, csums, lane);
                         // fold the factored block into the dense totals: P = W Psi now, Psi' P when the rows of M are formed
                         for (int idx = lane; idx < KC * NV; idx += WAVE) {
                             const int a = idx / NV, j = idx - a * NV;
@@ -814,26 +808,18 @@ __device__ __forceinline__ void solve_body(
                     for (int i = 0; i < RS; ++i) lmax_l = vmax(lmax_l, lam[i]);
                     const bool rp_small = !__any(rpn_l > try_tol * hn);
                     const bool lam_big = __any(lmax_l > 1e10);
-                    double gap;
-                    if constexpr (KC > 0) gap = readlane_d(csums[KT + KC], 0);       // (summed with the factored block's totals: sweep_a_factored)
-                    else gap = wave_sum(gap_l);
+                    double gap, obj;
+                    if constexpr (KC > 0) {       // (summed with the factored block's totals: sweep_a_factored)
+                        gap = readlane_d(csums[KT + KC], 0);
+                        obj = readlane_d(csums[KT + KC + 1], 0);
+                    } else {
+                        gap = gap_l;
+                        obj = obj_l;
+                        wv::wave_sum2(gap, obj, lane);
+                    }
                     const double mu = gap / ncd;
                     STAMP(1);
                     TMPC_REFRESH();
-                    // cost gradient cg = Hs z + q (lane i computes entry i)
-                    if (lane < NV) {
-                        double v = 0.0;
-#pragma unroll
-                        for (int j = 0; j < NV; ++j) v += Hs[lane * SH::LDH + j] * zv[j];
-                        cgv[lane] = v + qv[lane];
-                    }
-                    wave_lds_fence();
-                    double obj = 0.0;
-#pragma unroll
-                    for (int j = 0; j < NV; ++j) {
-                        const double cgj = cgv[j], qj = qv[j];
-                        obj += zv[j] * (0.5 * (cgj - qj) + qj);
-                    }
                     if (!(mu == mu)) { st = TMPC_STATUS_NUMERICAL; break; }
                     const double objs = fmax(fabs(obj), 1.0);
                     STAMP(2);
@@ -854,7 +840,7 @@ __device__ __forceinline__ void solve_body(
                                 for (int j = 0; j < NV; ++j) accl[j] = fma(Gt[r * LDG + j], dl2, accl[j]);
                                 if constexpr (WPB == 8 || TMPC_FENCE_ALL) row_fence();
                             });
-                            wave_reduce_to_lds<NV, SH::RR>(accl, red, sums + NV, lane);
+                            wave_sums_to_lds<SH, NV>(accl, red, sums + NV, lane);
                         }
                         if constexpr (KC > 0) {
                             double accl[KC];
@@ -868,7 +854,7 @@ __device__ __forceinline__ void solve_body(
 #pragma unroll
                                 for (int a = 0; a < KC; ++a) accl[a] = fma(Hct[a * NCCP + r], dl2, accl[a]);
                             });
-                            wave_reduce_to_lds<KC, SH::RR>(accl, red, csums + KT + KC, lane);
+                            wave_sums_to_lds<SH, KC>(accl, red, csums + KT + KC, lane);
                             double gl = 0.0;
                             if (lane < NV) {
                                 gl = (FD > 0) ? sums[NV + lane] : 0.0;
@@ -1031,7 +1017,7 @@ __device__ __forceinline__ void solve_body(
                                 }
                                 if constexpr (WPB == 8 || TMPC_FENCE_ALL) row_fence();
                             });
-                            wave_reduce_to_lds<2 * NV, SH::RR>(accb, red, sums, lane);   // overwrites G'(d.rp), G'lam (consumed)
+                            wave_sums_to_lds<SH, 2 * NV>(accb, red, sums, lane);   // overwrites G'(d.rp), G'lam (consumed)
                         }
                         if constexpr (KC > 0) {
                             double accc[2 * KC + 2];       // (+ the two sums of the affine step's statistics: see sweep_a_factored)
@@ -1053,12 +1039,11 @@ __device__ __forceinline__ void solve_body(
                             });
                             accc[2 * KC] = sb1;
                             accc[2 * KC + 1] = sb2;
-                            wave_reduce_to_lds<2 * KC + 2, SH::RR>(accc, red, csums + KT, lane);
+                            wave_sums_to_lds<SH, 2 * KC + 2>(accc, red, csums + KT, lane);
                             sb1 = readlane_d(csums[KT + 2 * KC], 0);
                             sb2 = readlane_d(csums[KT + 2 * KC + 1], 0);
                         } else {
-                            sb1 = wave_sum(sb1);
-                            sb2 = wave_sum(sb2);
+                            wv::wave_sum2(sb1, sb2, lane);
                         }
                         rho_aff = wave_max(rho_aff);
                         if (lane < NV) {

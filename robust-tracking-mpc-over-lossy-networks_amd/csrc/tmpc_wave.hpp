@@ -1,4 +1,4 @@
-// Wave-level device helpers shared by the block kernel (tmpc_block.hip) and the LP kernel (tmpc_lp.hip): DPP / readlane
+// Wave-level device helpers shared by the kernels (tmpc_kernels.hip, tmpc_block.hip, tmpc_lp.hip): DPP / permlane / readlane
 // reductions over the 64 lanes of a gfx950 wavefront and a division-free reciprocal.
 #pragma once
 #ifdef TMPC_HOST_SIM
@@ -100,6 +100,94 @@ __device__ __forceinline__ void reduce_to_lds(const double (&acc)[CNT], double *
         t += dpp_mov_d<0xB1>(t);
         t += dpp_mov_d<0x4E>(t);
         if (qd == 0 && c0 + e < CNT) out[c0 + e] = t;
+        lds_fence();
+    }
+}
+
+// ---- wave sums in registers with the cross-half swaps of gfx950.  v_permlane32_swap_b32 x, y exchanges the upper 32 lanes of x
+// with the lower 32 lanes of y, v_permlane16_swap_b32 x, y the odd 16-lane rows of x with the even rows of y.  Followed by one
+// v_add_f64, a swap of two 64-bit values (two swaps: low and high dwords) leaves on the lanes WITHOUT bit HALF the sum of `a`
+// over lanes l and l ^ HALF, and on the lanes WITH it the same sum of `b`: two partial sums halve into one register, with no
+// LDS and no fence.  (The compiler inserts the wait states in front of a swap whose operand was just written.)
+template <int HALF>
+__device__ __forceinline__ void permlane_swap(int &x, int &y, int lane) {
+    static_assert(HALF == 32 || HALF == 16, "v_permlane32_swap / v_permlane16_swap");
+#ifdef TMPC_HOST_SIM
+    const int xo = __builtin_amdgcn_readlane(x, lane ^ HALF), yo = __builtin_amdgcn_readlane(y, lane ^ HALF);
+    const bool up = (lane & HALF) != 0;
+    x = up ? yo : x;
+    y = up ? y : xo;
+#else
+    (void)lane;
+    if constexpr (HALF == 32) {
+        const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+        x = static_cast<int>(r[0]);
+        y = static_cast<int>(r[1]);
+    } else {
+        const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+        x = static_cast<int>(r[0]);
+        y = static_cast<int>(r[1]);
+    }
+#endif
+}
+template <int HALF>
+__device__ __forceinline__ double swap_add(double a, double b, int lane) {
+    int alo = __double2loint(a), ahi = __double2hiint(a), blo = __double2loint(b), bhi = __double2hiint(b);
+    permlane_swap<HALF>(alo, blo, lane);
+    permlane_swap<HALF>(ahi, bhi, lane);
+    return __hiloint2double(ahi, alo) + __hiloint2double(bhi, blo);
+}
+
+// Totals of a and b over the wave, on every lane: one swap puts a on the lower and b on the upper 32 lanes, the rest is
+// wave_reduce's butterfly and four v_readlane -- two sums for the price of one.
+__device__ __forceinline__ void wave_sum2(double &a, double &b, int lane) {
+    double v = swap_add<32>(a, b, lane);
+    v += dpp_mov_d<0xB1>(v);
+    v += dpp_mov_d<0x4E>(v);
+    v += dpp_mov_d<0x141>(v);
+    v += dpp_mov_d<0x140>(v);
+    a = readlane_d(v, 0) + readlane_d(v, 16);
+    b = readlane_d(v, 32) + readlane_d(v, 48);
+}
+
+// Sum each of acc[0..CNT) over the 64 lanes, totals to out[0..CNT) (LDS): the contract of the transposition tile's reduction
+// with a quarter of its LDS traffic.  Level 1: entry c and entry c + H1 (H1 = ceil(CNT / 2)) share a register after a
+// v_permlane32_swap (c on lanes 0-31, c + H1 on lanes 32-63, each summed over lanes l and l ^ 32).  Level 2: register d and
+// register d + H2 (H2 = ceil(H1 / 2)) the same with v_permlane16_swap: register d then holds on its 16-lane row r the entry
+// d + (r & 1) H2 + (r >> 1) H1 as sixteen partial sums (a register without a partner pairs with zero).  Finish: the H2
+// registers go to rows of the [RR][RED_STRIDE] tile (lane l at column l + l / 16) -- H2 <= RR stores per lane where the
+// tile form needs CNT --, and lane l adds the sixteen partial sums of row (l >> 2), quarter (l & 3): a complete total, no
+// DPP step.  More than RR rows: rounds of RR.
+template <int CNT, int RR>
+__device__ __forceinline__ void swap_reduce_to_lds(const double (&acc)[CNT], double *red, double *out, int lane) {
+    constexpr int H1 = (CNT + 1) / 2, H2 = (H1 + 1) / 2;
+    double r1[H1];
+#pragma unroll
+    for (int c = 0; c < H1; ++c) r1[c] = swap_add<32>(acc[c], c + H1 < CNT ? acc[c + H1] : 0.0, lane);
+    double r2[H2];
+#pragma unroll
+    for (int d = 0; d < H2; ++d) r2[d] = swap_add<16>(r1[d], d + H2 < H1 ? r1[d + H2] : 0.0, lane);
+    // entry of register d on 16-lane row r; -1 where that place holds the zero partner's sums
+    auto entry = [](int d, int r) {
+        const int e = d + (r & 1) * H2 + (r >> 1) * H1;
+        return ((r & 1) && d + H2 >= H1) || e >= CNT ? -1 : e;
+    };
+    const int wcol = lane + (lane >> 4);
+    const int k = lane >> 2, qd = lane & 3;
+#pragma unroll
+    for (int d0 = 0; d0 < H2; d0 += RR) {
+#pragma unroll
+        for (int d = 0; d < RR; ++d)
+            if (d0 + d < H2) red[d * RED_STRIDE + wcol] = r2[d0 + d];
+        lds_fence();
+        constexpr int NR = RR < 16 ? RR : 16;
+        const int kr = k < NR && d0 + k < H2 ? k : 0;      // (lanes beyond the stored rows read row 0 and store nothing)
+        double t4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) t4[j & 3] += red[kr * RED_STRIDE + qd * 17 + j];
+        const double t = (t4[0] + t4[1]) + (t4[2] + t4[3]);
+        const int e = (k < NR && d0 + k < H2) ? entry(d0 + k, qd) : -1;
+        if (e >= 0) out[e] = t;
         lds_fence();
     }
 }
