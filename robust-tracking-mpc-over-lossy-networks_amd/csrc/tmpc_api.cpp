@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -19,6 +20,85 @@
 namespace {
 
 thread_local std::string g_create_error;
+
+// Grow-only device memory.  When a call needs more, the old block is freed -- after the work queued on `stream`, which may still
+// use it -- and one of exactly the new size allocated.  No destructor: the LP arena is thread_local and may outlive the HIP
+// runtime; tmpc_destroy releases a handle's buffers.
+struct DeviceBuffer {
+    char *p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t bytes, hipStream_t stream) {
+        if (bytes <= cap) return hipSuccess;
+        if (p && stream) {
+            const hipError_t e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return e;
+        }
+        release();
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), bytes);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// Device memory of one call, carved from a grow-only buffer: the caller lists its pieces, then carve() grows the buffer to their
+// sum (each rounded up to 256 B), writes every piece's device pointer to its slot and does the listed uploads and fills.  What
+// the previous call carved is gone from then on.
+class Arena {
+  public:
+    // `src` (host memory that outlives the copy) is uploaded into the piece; without one, `fill` >= 0 is written to every byte
+    template <class T> void piece(T **slot, size_t bytes, const void *src = nullptr, int fill = -1) {
+        pieces_.push_back({slot, [](void *s, char *p) { *static_cast<T **>(s) = reinterpret_cast<T *>(p); }, bytes, src, fill});
+    }
+    // `stream` gets the uploads and fills, and a reallocation waits for its work; nullptr: synchronous copies and fills
+    hipError_t carve(hipStream_t stream) {
+        size_t total = 0;
+        for (const Piece &q : pieces_) total += rounded(q.bytes);
+        hipError_t e = buf_.reserve(total, stream);
+        char *p = buf_.p;
+        for (size_t i = 0; i < pieces_.size() && e == hipSuccess; p += rounded(pieces_[i++].bytes)) {
+            const Piece &q = pieces_[i];
+            q.set(q.slot, p);
+            if (q.src && q.bytes)
+                e = stream ? hipMemcpyAsync(p, q.src, q.bytes, hipMemcpyHostToDevice, stream) : hipMemcpy(p, q.src, q.bytes, hipMemcpyHostToDevice);
+            else if (!q.src && q.fill >= 0)
+                e = stream ? hipMemsetAsync(p, q.fill, q.bytes, stream) : hipMemset(p, q.fill, q.bytes);
+        }
+        pieces_.clear();
+        return e;
+    }
+    void release() { buf_.release(); }
+
+  private:
+    struct Piece {
+        void *slot;
+        void (*set)(void *slot, char *p);
+        size_t bytes;
+        const void *src;
+        int fill;
+    };
+    static size_t rounded(size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) / 256 * 256; }
+    std::vector<Piece> pieces_;
+    DeviceBuffer buf_;
+};
+
+// What the last tmpc_mc_run / tmpc_reg_run left in the loop arena for the getters (nullptr / 0: nothing).  A run resets them
+// before it touches the arena, whether it gets as far as replacing them or not.
+struct LoopRecords {
+    double *cap = nullptr;       // the recorded trajectory: [cap_T][2 nx + nu]
+    int cap_T = 0;
+    long long *tick_sum = nullptr, *tick_max = nullptr;     // per-trajectory solve times
+    int64_t tick_B = 0;
+    double *err2_phys = nullptr; // physics-rate error (nonlinear plant)
+    int64_t phys_B = 0;
+    int fused = 0;               // tmpc_mc_last_fused
+};
 
 struct Variant {
     tmpc::Condensed c;
@@ -36,67 +116,57 @@ struct Variant {
 }  // namespace
 
 struct tmpc_handle {
+    // the handle: its problem(s), device, stream and the scratch of the solve launches
     int device = 0;
     int n_cu = 0;
     int nvariants = 0;
     int nx = 0, nu = 0, N = 0;
     Variant v[2];
+    // regulator handles (tmpc_create_regulator): no reference input -- the solves read `ref` from a zero buffer (F2 = 0)
+    bool regulator = false;
+    int reg_tube = 0;
+    std::vector<double> hA, hB, hK, hKanc, hQ, hR;   // host copies for the closed-loop entry points
+    int kernel_path = TMPC_PATH_AUTO;
     hipStream_t stream = nullptr;
+    tmpc::WorkCounter wc;        // work counters of the wave kernel's launches (tmpc_device.hpp)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     // event pairs of the launches since the last tmpc_kernel_ms_total(reset): per-launch device time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
     size_t pool_used = 0;
-    std::vector<double> hA, hB, hK, hKanc;   // host copies for the closed-loop entry point
-    // closed-loop state lives in one grow-only arena (25 hipMalloc / hipFree per call cost several milliseconds)
-    char *mc_arena = nullptr;
-    size_t mc_arena_bytes = 0;
-    int plant = TMPC_PLANT_LINEAR, plant_substeps = 10;
-    int actuator = TMPC_ACTUATOR_CONSISTENT;
-    tmpc::WorkCounter wc;        // work counters of the wave kernel's launches (tmpc_device.hpp)
-    long long mc_capture = -1;   // trajectory recorded by the next tmpc_mc_run (-1: none)
-    double *mc_cap_dev = nullptr; // its record in the arena: [mc_cap_T][2 nx + nu]
-    int mc_cap_T = 0;
-    int mc_warm = 0;             // closed loop: hand every solve the working set of the trajectory's previous solve of the same variant
-    int mc_fused = TMPC_MC_FUSED_AUTO;   // closed loop: one fused launch for all T steps (tmpc_mc_set_fused)
-    int mc_last_fused = 0;       // what the last tmpc_mc_run did
-    double plant_par[7] = {0, 0, 0, 0, 0, 0, 0};
-    int kernel_path = TMPC_PATH_AUTO;
-    int blk_blocks = 0;          // workgroups the block-kernel workspace is sized for
-    int blk_ncp = 0;
-    double *blk_ws = nullptr;
+    DeviceBuffer blk_ws;         // block-kernel workspace
+    int blk_blocks = 0;          // workgroups it is sized for
+    DeviceBuffer save;           // (s, lambda) of every resident wave at its hand-over to the refinement (DeviceQP::save)
+    int want_ticks = 0;          // per-solve durations (tmpc_set_solve_timing): one tick count per instance of the last call
+    DeviceBuffer ticks;
+    int64_t ticks_n = 0;
+    DeviceBuffer reg_zero;       // regulator: the zero reference
+    std::string err;
     // staging buffers for the host-pointer entry point: ONE device block, inputs [x | ref | variant] then outputs
     // [u | x0 | ss | status | iters | x_nom], and a pinned host mirror of it -- a call moves its inputs with one DMA and its
     // outputs with one (round 3: nine hipMemcpyAsync from / to pageable memory per call, 60 % of the time of a call at batch 1)
-    int64_t cap = 0;
-    char *stage_dev = nullptr, *stage_pin = nullptr;
+    DeviceBuffer stage_dev;
+    char *stage_pin = nullptr;
     size_t stage_in_bytes = 0, stage_out_bytes = 0, stage_out_core = 0;      // (core = the outputs without x_nom)
     size_t off_r = 0, off_var = 0, off_x0 = 0, off_ss = 0, off_st = 0, off_it = 0, off_xn = 0;      // offsets within the input / output parts
     double *d_x = nullptr, *d_r = nullptr, *d_u = nullptr, *d_x0 = nullptr, *d_ss = nullptr, *d_xn = nullptr;
     uint8_t *d_var = nullptr;
     int32_t *d_st = nullptr, *d_it = nullptr;
-    // (s, lambda) of every resident wave at its hand-over to the refinement (DeviceQP::save)
-    float *save_buf = nullptr;
-    size_t save_bytes = 0;
-    // per-solve durations (tmpc_set_solve_timing): one tick count per instance of the last call
-    int want_ticks = 0;
-    int64_t ticks_cap = 0, ticks_n = 0;
-    long long *d_ticks = nullptr;
-    long long *mc_tick_sum = nullptr, *mc_tick_max = nullptr;      // inside mc_arena, of the last tmpc_mc_run
-    double *mc_err2_phys = nullptr;                                 // likewise (nonlinear plant only)
-    int mc_rng_on = 0;                                              // tmpc_mc_set_device_rng
+    // closed-loop settings (tmpc_mc_set_*)
+    int plant = TMPC_PLANT_LINEAR, plant_substeps = 10;
+    double plant_par[7] = {0, 0, 0, 0, 0, 0, 0};
+    int actuator = TMPC_ACTUATOR_CONSISTENT;
+    long long mc_capture = -1;   // trajectory recorded by the next tmpc_mc_run (-1: none)
+    int mc_warm = 0;             // closed loop: hand every solve the working set of the trajectory's previous solve of the same variant
+    int mc_fused = TMPC_MC_FUSED_AUTO;   // closed loop: one fused launch for all T steps (tmpc_mc_set_fused)
+    int mc_rng_on = 0;                   // tmpc_mc_set_device_rng
     uint64_t mc_rng_seed = 0;
     int64_t mc_rng_first = 0;
     std::vector<double> mc_w_bound;
-    int64_t mc_phys_B = 0;
-    int64_t mc_tick_B = 0;
-    // regulator handles (tmpc_create_regulator): no reference input -- the solves read `ref` from a zero buffer (F2 = 0)
-    bool regulator = false;
-    int reg_tube = 0;
-    std::vector<double> hQ, hR;
-    double *reg_zero = nullptr;
-    int64_t reg_zero_cap = 0;
-    std::string err;
+    // closed-loop state: one grow-only arena (25 hipMalloc / hipFree per call cost several milliseconds), and what the last run
+    // left in it
+    Arena arena;
+    LoopRecords rec;
 };
 
 namespace {
@@ -131,6 +201,17 @@ int upload(tmpc_handle *h, Variant &v, const T *src, size_t n, const T **dst) {
     *dst = static_cast<const T *>(p);
     return TMPC_OK;
 }
+
+#ifdef TMPC_STAMPS
+// diagnostic builds: 16 zeroed time stamps per layout (tmpc_debug_stamps)
+int upload_stamps(tmpc_handle *h, Variant &v, long long **dbg) {
+    static const long long zero[16] = {};
+    const long long *p = nullptr;
+    const int rc = upload(h, v, zero, 16, &p);
+    *dbg = const_cast<long long *>(p);
+    return rc;
+}
+#endif
 
 int upload_common(tmpc_handle *h, Variant &v, const tmpc_problem &p, tmpc::DeviceQP &d, int NVP) {
     const tmpc::Condensed &c = v.c;
@@ -287,13 +368,7 @@ int upload_wave(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     if ((rc = upload(h, v, vmask.data(), vmask.size(), &d.vmask))) return rc;
     if ((rc = upload(h, v, row_of.data(), row_of.size(), &d.row_of))) return rc;
 #ifdef TMPC_STAMPS
-    {
-        void *dbgp = nullptr;
-        HIP_TRY(h, hipMalloc(&dbgp, 16 * sizeof(long long)));
-        HIP_TRY(h, hipMemset(dbgp, 0, 16 * sizeof(long long)));
-        v.dev.push_back(dbgp);
-        d.dbg = static_cast<long long *>(dbgp);
-    }
+    if ((rc = upload_stamps(h, v, &d.dbg))) return rc;
 #endif
     v.wave_ok = true;
     return TMPC_OK;
@@ -395,13 +470,7 @@ int upload_block(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     if ((rc = upload(h, v, ncols.data(), ncols.size(), &v.bq.ncols))) return rc;
     if ((rc = upload(h, v, ci.data(), ci.size(), &v.bq.ci))) return rc;
 #ifdef TMPC_STAMPS
-    {
-        void *dbgp = nullptr;
-        HIP_TRY(h, hipMalloc(&dbgp, 16 * sizeof(long long)));
-        HIP_TRY(h, hipMemset(dbgp, 0, 16 * sizeof(long long)));
-        v.dev.push_back(dbgp);
-        v.db.dbg = static_cast<long long *>(dbgp);
-    }
+    if ((rc = upload_stamps(h, v, &v.db.dbg))) return rc;
 #endif
     {
         const tmpc::BlockArgs rec{v.db, v.bq};
@@ -423,37 +492,19 @@ int upload_variant(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     return TMPC_OK;
 }
 
-// block-kernel workspace: one slice per resident workgroup
+// block-kernel workspace: one slice per resident workgroup, sized once for the largest variant (a slice is addressed with the
+// launching variant's ncp)
 int ensure_block_ws(tmpc_handle *h) {
-    int ncp = 0, occ = 64;
+    if (h->blk_ws.p) return TMPC_OK;
+    int ncp = 0, occ_max = 1;
     for (int k = 0; k < h->nvariants; ++k)
-        if (h->v[k].tiles) { ncp = std::max(ncp, h->v[k].bq.ncp); occ = std::min(occ, tmpc::block_occupancy(h->v[k].tiles)); }
-    if (ncp == 0 || h->blk_ws) return TMPC_OK;
-    int occ_max = 1;
-    for (int k = 0; k < h->nvariants; ++k)
-        if (h->v[k].tiles) occ_max = std::max(occ_max, tmpc::block_occupancy(h->v[k].tiles));
-    const int blocks = h->n_cu * occ_max;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->blk_ws),
-                         static_cast<size_t>(blocks) * tmpc::block_workspace_rows() * ncp * sizeof(double)));
-    h->blk_blocks = blocks;
-    h->blk_ncp = ncp;
+        if (h->v[k].tiles) { ncp = std::max(ncp, h->v[k].bq.ncp); occ_max = std::max(occ_max, tmpc::block_occupancy(h->v[k].tiles)); }
+    h->blk_blocks = h->n_cu * occ_max;
+    HIP_TRY(h, h->blk_ws.reserve(static_cast<size_t>(h->blk_blocks) * tmpc::block_workspace_rows() * ncp * sizeof(double), h->stream));
     return TMPC_OK;
 }
 
-bool use_block(const tmpc_handle *h, const Variant &v) {
-    if (h->kernel_path == TMPC_PATH_BLOCK) return v.tiles != 0;
-    if (h->kernel_path == TMPC_PATH_WAVE) return !v.wave_ok;
-    return !v.wave_ok;
-}
-
-void free_staging(tmpc_handle *h) {
-    if (h->stage_dev) (void)hipFree(h->stage_dev);
-    if (h->stage_pin) (void)hipHostFree(h->stage_pin);
-    h->stage_dev = h->stage_pin = nullptr;
-    h->d_x = h->d_r = h->d_u = h->d_x0 = h->d_ss = h->d_xn = nullptr;
-    h->d_var = nullptr; h->d_st = h->d_it = nullptr;
-    h->cap = 0;
-}
+bool use_block(const tmpc_handle *h, const Variant &v) { return h->kernel_path == TMPC_PATH_BLOCK ? v.tiles != 0 : !v.wave_ok; }
 
 // offsets and sub-buffers for a batch of B (tightly packed for THIS batch, whatever the capacity: the DMAs of a call move
 // exactly its bytes); returns the total
@@ -472,8 +523,8 @@ size_t layout_staging(tmpc_handle *h, int64_t B) {
     h->stage_out_core = h->off_it + up(b * sizeof(int32_t));
     h->off_xn = h->stage_out_core;
     h->stage_out_bytes = h->off_xn + up(b * (N + 1) * nx * sizeof(double));
-    if (h->stage_dev != nullptr) {
-        char *in = h->stage_dev, *out = h->stage_dev + h->stage_in_bytes;
+    if (h->stage_dev.p != nullptr) {
+        char *in = h->stage_dev.p, *out = h->stage_dev.p + h->stage_in_bytes;
         h->d_x = reinterpret_cast<double *>(in);
         h->d_r = reinterpret_cast<double *>(in + h->off_r);
         h->d_var = reinterpret_cast<uint8_t *>(in + h->off_var);
@@ -488,36 +539,29 @@ size_t layout_staging(tmpc_handle *h, int64_t B) {
 }
 
 int ensure_staging(tmpc_handle *h, int64_t B) {
-    if (B > h->cap) {
-        if (h->stream) HIP_TRY(h, hipStreamSynchronize(h->stream));
-        free_staging(h);
-        const size_t total = layout_staging(h, B);
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->stage_dev), total));
-        // the pinned mirror is a convenience, not a requirement: without it (or beyond 64 MB) the call copies from / to the
-        // caller's buffers directly
-        if (total <= (64u << 20)) {
-            if (hipHostMalloc(reinterpret_cast<void **>(&h->stage_pin), total, hipHostMallocDefault) != hipSuccess) {
-                h->stage_pin = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        h->cap = B;
+    const size_t total = layout_staging(h, B);
+    if (total <= h->stage_dev.cap) return TMPC_OK;
+    const hipError_t e = h->stage_dev.reserve(total, h->stream);       // (waits for the queued work, which may use the mirror too)
+    if (h->stage_pin) (void)hipHostFree(h->stage_pin);
+    h->stage_pin = nullptr;
+    HIP_TRY(h, e);
+    // the pinned mirror is a convenience, not a requirement: without it (or beyond 64 MB) the call copies from / to the
+    // caller's buffers directly
+    if (total <= (64u << 20) && hipHostMalloc(reinterpret_cast<void **>(&h->stage_pin), total, hipHostMallocDefault) != hipSuccess) {
+        h->stage_pin = nullptr;
+        (void)hipGetLastError();
     }
-    (void)layout_staging(h, B);
+    (void)layout_staging(h, B);             // (the sub-buffers in the new block)
     return TMPC_OK;
 }
 
 // Regulator handles: B x nx zeros in device memory, handed to the solve kernels as their reference (the condensed QP has F2 = 0, but
 // 0 * garbage is not 0 when the garbage is a NaN)
 int ensure_reg_zero(tmpc_handle *h, int64_t B) {
-    if (B <= h->reg_zero_cap) return TMPC_OK;
-    if (h->stream) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->reg_zero) (void)hipFree(h->reg_zero);
-    h->reg_zero = nullptr; h->reg_zero_cap = 0;
     const size_t bytes = static_cast<size_t>(B) * h->nx * sizeof(double);
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->reg_zero), bytes));
-    HIP_TRY(h, hipMemset(h->reg_zero, 0, bytes));
-    h->reg_zero_cap = B;
+    if (bytes <= h->reg_zero.cap) return TMPC_OK;
+    HIP_TRY(h, h->reg_zero.reserve(bytes, h->stream));
+    HIP_TRY(h, hipMemset(h->reg_zero.p, 0, bytes));
     return TMPC_OK;
 }
 
@@ -541,6 +585,33 @@ int begin_timed_launch(tmpc_handle *h) {
     return TMPC_OK;
 }
 
+// Scratch of the solve launches of the first nvar variants over B instances: the per-solve tick buffer (zeroed; with
+// tmpc_set_solve_timing on) and the wave kernel's hand-over save slots, one per resident wave (at most 8 per CU).  The variants
+// share the slots: launches on one stream do not overlap, and a launch reads only what it wrote itself.
+int prepare_wave_scratch(tmpc_handle *h, int64_t B, int nvar) {
+    long long *ticks = nullptr;
+    if (h->want_ticks) {
+        const size_t bytes = static_cast<size_t>(B) * sizeof(long long);
+        HIP_TRY(h, h->ticks.reserve(bytes, h->stream));
+        ticks = h->ticks.as<long long>();
+        h->ticks_n = B;
+        HIP_TRY(h, hipMemsetAsync(ticks, 0, bytes, h->stream));
+    }
+    size_t save = 0;
+    for (int k = 0; k < nvar; ++k) {
+        const tmpc::KernelShape &s = h->v[k].shape;
+        if (!use_block(h, h->v[k]) && !tmpc::parks_in_lds(s))
+            save = std::max(save, static_cast<size_t>(h->n_cu) * 8 * 2 * (2 * s.dp + s.ds + 2 * s.cp + s.cs) * 64 * sizeof(float));
+    }
+    HIP_TRY(h, h->save.reserve(save, h->stream));
+    for (int k = 0; k < nvar; ++k) {
+        Variant &v = h->v[k];
+        v.d.ticks = v.db.ticks = ticks;
+        if (!use_block(h, v)) v.d.save = tmpc::parks_in_lds(v.shape) ? nullptr : h->save.as<float>();
+    }
+    return TMPC_OK;
+}
+
 int enqueue(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, double *u_nom,
             double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, int32_t *const *ws = nullptr,
             bool variants_valid = false) {
@@ -548,46 +619,16 @@ int enqueue(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, con
     if (variant != nullptr && !variants_valid)      // (the closed loop's selector is its own gamma flags: always 0 or 1)
         HIP_TRY(h, tmpc::launch_mark_invalid_variants(variant, h->nvariants, B, h->nx, h->nu, h->N, u_nom, x_nom0, xu_ss, x_nom, status,
                                                       iters, h->stream));
-    long long *ticks = nullptr;
-    if (h->want_ticks) {
-        if (B > h->ticks_cap) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            if (h->d_ticks) (void)hipFree(h->d_ticks);
-            h->d_ticks = nullptr; h->ticks_cap = 0;
-            HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->d_ticks), static_cast<size_t>(B) * sizeof(long long)));
-            h->ticks_cap = B;
-        }
-        ticks = h->d_ticks;
-        h->ticks_n = B;
-        HIP_TRY(h, hipMemsetAsync(ticks, 0, static_cast<size_t>(B) * sizeof(long long), h->stream));
-    }
-    for (int k = 0; k < h->nvariants; ++k) {
-        if (k == 1 && variant == nullptr) break;        // no per-instance selector: everything is variant 0
+    const int nvar = variant != nullptr ? h->nvariants : 1;        // (no per-instance selector: everything is variant 0)
+    { const int rcs = prepare_wave_scratch(h, B, nvar); if (rcs) return rcs; }
+    for (int k = 0; k < nvar; ++k) {
         Variant &v = h->v[k];
-        v.d.ticks = ticks;
-        v.db.ticks = ticks;
         if (use_block(h, v)) {
             int rcw = ensure_block_ws(h);
             if (rcw) return rcw;
-            // the workspace slices are sized for the largest variant; a slice is addressed with this variant's ncp
-            HIP_TRY(h, tmpc::launch_block(v.db, v.bq, v.bargs, v.tiles, h->blk_ws, h->blk_blocks, k, B, x_k, ref, variant, u_nom, x_nom0,
-                                          xu_ss, x_nom, status, iters, &h->wc, h->stream));
+            HIP_TRY(h, tmpc::launch_block(v.db, v.bq, v.bargs, v.tiles, h->blk_ws.as<double>(), h->blk_blocks, k, B, x_k, ref, variant, u_nom,
+                                          x_nom0, xu_ss, x_nom, status, iters, &h->wc, h->stream));
             continue;
-        }
-        if (tmpc::parks_in_lds(v.shape)) {
-            v.d.save = nullptr;
-        } else {
-            // one save slot per resident wave (at most 8 per CU), sized for this variant's row sides
-            const size_t rs = static_cast<size_t>(2 * v.shape.dp + v.shape.ds + 2 * v.shape.cp + v.shape.cs);
-            const size_t need = static_cast<size_t>(h->n_cu) * 8 * 2 * rs * 64 * sizeof(float);
-            if (need > h->save_bytes) {
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                if (h->save_buf) (void)hipFree(h->save_buf);
-                h->save_buf = nullptr; h->save_bytes = 0;
-                HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->save_buf), need));
-                h->save_bytes = need;
-            }
-            v.d.save = h->save_buf;
         }
         HIP_TRY(h, tmpc::launch_solve(v.d, v.shape, k, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status,
                                       iters, ws ? ws[k] : nullptr, ws ? ws[k] : nullptr, &h->wc, h->n_cu, h->stream));
@@ -597,81 +638,122 @@ int enqueue(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, con
     return TMPC_OK;
 }
 
-}  // namespace
-
-// device memory of tmpc_lp_batch: one grow-only allocation per host thread, carved per call (the Gilbert-Tan recursion
-// makes hundreds of small calls; ten hipMalloc / hipFree pairs each cost more than the kernel).  Lives until the
-// process ends.
-namespace {
-struct LpArena {
-    int device = -1;
-    char *p = nullptr;
-    size_t cap = 0, off = 0;
-    hipError_t reserve(int dev, size_t bytes) {
-        off = 0;
-        if (dev == device && bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0; device = dev;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    template <class T> T *take(size_t count) {
-        T *q = reinterpret_cast<T *>(p + off);
-        off += (count * sizeof(T) + 255) / 256 * 256;
-        return q;
-    }
-};
-thread_local LpArena g_lp_arena;
-size_t lp_round(size_t bytes) { return (bytes + 255) / 256 * 256; }
-}  // namespace
-
-namespace {
 // Uploads the condensed variant(s) of a new handle to HIP device `device` (stream, work counters, timing events, kernel layouts),
-// or, for device < 0, lays out the host-only copies; shared by tmpc_create and tmpc_create_regulator.  `p` carries what the
-// layouts read beyond the condensed QP (A, B, tol, max_iter).
-int setup_handle(tmpc_handle *h, const tmpc_problem &pp, int device) {
-    const tmpc_problem *p = &pp;
-    int rc = TMPC_OK;
-    if (rc == TMPC_OK && device >= 0) {
-        hipError_t e = hipSetDevice(device);
-        hipDeviceProp_t prop;
-        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-        if (e != hipSuccess) {
-            h->err = std::string("tmpc_create: no usable HIP device: ") + hipGetErrorString(e);
-            rc = TMPC_E_DEVICE;
-        } else {
-            h->n_cu = prop.multiProcessorCount;
-            auto setup = [&]() -> int {
-                HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-                h->wc.size = 4096;
-                HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->wc.ring), h->wc.size * sizeof(unsigned long long)));
-                HIP_TRY(h, hipMemset(h->wc.ring, 0, h->wc.size * sizeof(unsigned long long)));
-                for (int i = 0; i < 256; ++i) {       // timing events are created up front, not in the solve path
-                    hipEvent_t a = nullptr, b = nullptr;
-                    HIP_TRY(h, hipEventCreate(&a));
-                    HIP_TRY(h, hipEventCreate(&b));
-                    h->pool.emplace_back(a, b);
-                }
-                for (int k = 0; k < h->nvariants; ++k) {
-                    int r2 = upload_variant(h, h->v[k], *p);
-                    if (r2) return r2;
-                }
-                return TMPC_OK;
-            };
-            rc = setup();
-        }
-    }
-    if (rc == TMPC_OK && device < 0) {
+// or, for device < 0, lays out the host-only copies.  `p` carries what the layouts read beyond the condensed QP (A, B, tol,
+// max_iter).
+int setup_handle(tmpc_handle *h, const tmpc_problem &p, int device) {
+    if (device < 0) {
         // host-only handle: the layouts are laid out for the debug dumps only.  A problem no kernel covers (nv > 128) still
         // gets its handle -- tmpc_get_condensed and the oracle-side tests use it -- and the dump calls answer UNSUPPORTED
         // (wave_ok = false, tiles = 0).
-        for (int k = 0; k < h->nvariants && rc == TMPC_OK; ++k) {
-            rc = upload_variant(h, h->v[k], *p);
-            if (rc == TMPC_E_UNSUPPORTED) { rc = TMPC_OK; h->err.clear(); }
+        for (int k = 0; k < h->nvariants; ++k) {
+            const int rc = upload_variant(h, h->v[k], p);
+            if (rc == TMPC_E_UNSUPPORTED) h->err.clear();
+            else if (rc) return rc;
         }
+        return TMPC_OK;
     }
-    return rc;
+    hipDeviceProp_t prop;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) {
+        h->err = std::string("tmpc_create: no usable HIP device: ") + hipGetErrorString(e);
+        return TMPC_E_DEVICE;
+    }
+    h->n_cu = prop.multiProcessorCount;
+    HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->wc.size = 4096;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->wc.ring), h->wc.size * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemset(h->wc.ring, 0, h->wc.size * sizeof(unsigned long long)));
+    for (int i = 0; i < 256; ++i) {       // timing events are created up front, not in the solve path
+        hipEvent_t a = nullptr, b = nullptr;
+        HIP_TRY(h, hipEventCreate(&a));
+        HIP_TRY(h, hipEventCreate(&b));
+        h->pool.emplace_back(a, b);
+    }
+    for (int k = 0; k < h->nvariants; ++k)
+        if (const int rc = upload_variant(h, h->v[k], p)) return rc;
+    return TMPC_OK;
+}
+
+// tmpc_create / tmpc_create_regulator: the dimension check, a new handle, `condense` (fills in the handle's problem and sets the
+// problem the kernel layouts read; returns what is wrong with it, or "") and the device set-up.  On failure the handle is
+// destroyed and the message kept for tmpc_last_error(NULL).
+template <class Condense>
+int create_handle(const char *who, int nx, int nu, int N, int device, tmpc_handle **out, Condense condense) {
+    *out = nullptr;
+    if (nx <= 0 || nu <= 0 || N <= 0 || nx > 16) {
+        g_create_error = std::string(who) + ": need 0 < nx <= 16, nu > 0, N > 0";
+        return TMPC_E_INVALID;
+    }
+    tmpc_handle *h = new (std::nothrow) tmpc_handle();
+    if (!h) { g_create_error = "out of memory"; return TMPC_E_NOMEM; }
+    h->device = device; h->nx = nx; h->nu = nu; h->N = N;
+    int rc = TMPC_E_INVALID;
+    try {
+        tmpc_problem q{};
+        const std::string msg = condense(h, q);
+        if (msg.empty()) rc = setup_handle(h, q, device);
+        else h->err = std::string(who) + ": " + msg;
+    } catch (const std::exception &ex) {
+        h->err = std::string(who) + ": " + ex.what();
+        rc = TMPC_E_NOMEM;
+    }
+    if (rc != TMPC_OK) {
+        g_create_error = h->err;
+        tmpc_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return TMPC_OK;
+}
+
+// Argument checks of tmpc_solve_batch and tmpc_solve_batch_device, in the order they are reported; `variant_range`: the ids are
+// host memory and checked here.  TMPC_OK with B = 0: nothing to do.
+int check_solve(tmpc_handle *h, const char *who, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
+                const double *u_nom, const double *xu_ss, const int32_t *status, const int32_t *iters, bool variant_range) {
+    if (!h) return TMPC_E_INVALID;
+    if (B < 0 || !x_k || (!ref && !h->regulator) || !u_nom || !status || !iters) { h->err = std::string(who) + ": NULL argument"; return TMPC_E_INVALID; }
+    if (h->regulator && (xu_ss || variant)) {
+        h->err = std::string(who) + ": a regulator handle has no steady state and one problem (xu_ss, variant must be NULL)";
+        return TMPC_E_INVALID;
+    }
+    if (B == 0) return TMPC_OK;
+    if (variant_range && variant)
+        for (int64_t i = 0; i < B; ++i)
+            if (variant[i] >= h->nvariants) { h->err = std::string(who) + ": variant id out of range"; return TMPC_E_INVALID; }
+    if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    return TMPC_OK;
+}
+
+// A layout dump (tmpc_debug_dump_layout / _block_layout): the tag, the header, then every array the layout points to, in the
+// order given: byte count, bytes (0: null pointer)
+int write_dump(const char *path, const Variant &v, std::initializer_list<std::pair<const void *, size_t>> header,
+               std::initializer_list<const void *> arrays) {
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return TMPC_E_INVALID;
+    const int32_t tag[2] = {tmpc::DUMP_TAG, tmpc::DUMP_FORMAT};
+    std::fwrite(tag, 4, 2, f);
+    for (const auto &[p, n] : header) std::fwrite(p, 1, n, f);
+    for (const void *q : arrays) {
+        uint64_t n = 0;
+        if (q)
+            for (size_t i = 0; i < v.dev.size(); ++i)
+                if (v.dev[i] == q) { n = v.dev_bytes[i]; break; }
+        std::fwrite(&n, 8, 1, f);
+        if (n) std::fwrite(q, 1, n, f);
+    }
+    std::fclose(f);
+    return TMPC_OK;
+}
+
+// Common start of the closed loops: what the last run left in the arena is unreadable from here on (tmpc_mc_get_capture /
+// _solve_ticks / _physics_error must not read a freed or half-written arena); the staging block's outputs take the solves'.
+int begin_loop(tmpc_handle *h, int64_t B) {
+    h->rec = LoopRecords{};
+    HIP_TRY(h, hipSetDevice(h->device));
+    return ensure_staging(h, B);
 }
 
 }  // namespace
@@ -684,81 +766,39 @@ const char *tmpc_last_error(const tmpc_handle *h) { return h ? h->err.c_str() : 
 
 int tmpc_create(const tmpc_problem *p, int device, tmpc_handle **out) {
     if (!p || !out) { g_create_error = "tmpc_create: NULL argument"; return TMPC_E_INVALID; }
-    *out = nullptr;
-    if (p->nx <= 0 || p->nu <= 0 || p->N <= 0 || p->nx > 16) {
-        g_create_error = "tmpc_create: need 0 < nx <= 16, nu > 0, N > 0";
-        return TMPC_E_INVALID;
-    }
-    tmpc_handle *h = new (std::nothrow) tmpc_handle();
-    if (!h) { g_create_error = "out of memory"; return TMPC_E_NOMEM; }
-    h->device = device; h->nx = p->nx; h->nu = p->nu; h->N = p->N;
-    h->hA.assign(p->A ? p->A : nullptr, p->A ? p->A + p->nx * p->nx : nullptr);
-    h->hB.assign(p->B ? p->B : nullptr, p->B ? p->B + p->nx * p->nu : nullptr);
-    if (p->K) h->hK.assign(p->K, p->K + p->nu * p->nx);
-    if (p->K_anc) h->hKanc.assign(p->K_anc, p->K_anc + p->nu * p->nx);
-    h->nvariants = p->extended ? 2 : 1;
-    int rc = TMPC_OK;
-    try {
-        for (int k = 0; k < h->nvariants && rc == TMPC_OK; ++k) {
-            const std::string msg = tmpc::condense(*p, k, h->v[k].c);
-            if (!msg.empty()) { h->err = "tmpc_create: " + msg; rc = TMPC_E_INVALID; }
-        }
-        if (rc == TMPC_OK) rc = setup_handle(h, *p, device);
-    } catch (const std::exception &ex) {
-        h->err = std::string("tmpc_create: ") + ex.what();
-        rc = TMPC_E_NOMEM;
-    }
-    if (rc != TMPC_OK) {
-        g_create_error = h->err;
-        tmpc_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return TMPC_OK;
+    return create_handle("tmpc_create", p->nx, p->nu, p->N, device, out, [p](tmpc_handle *h, tmpc_problem &q) {
+        h->hA.assign(p->A ? p->A : nullptr, p->A ? p->A + p->nx * p->nx : nullptr);
+        h->hB.assign(p->B ? p->B : nullptr, p->B ? p->B + p->nx * p->nu : nullptr);
+        if (p->K) h->hK.assign(p->K, p->K + p->nu * p->nx);
+        if (p->K_anc) h->hKanc.assign(p->K_anc, p->K_anc + p->nu * p->nx);
+        h->nvariants = p->extended ? 2 : 1;
+        q = *p;
+        std::string msg;
+        for (int k = 0; k < h->nvariants && msg.empty(); ++k) msg = tmpc::condense(*p, k, h->v[k].c);
+        return msg;
+    });
 }
 
 int tmpc_create_regulator(const tmpc_regulator_problem *p, int device, tmpc_handle **out) {
     if (!p || !out) { g_create_error = "tmpc_create_regulator: NULL argument"; return TMPC_E_INVALID; }
-    *out = nullptr;
-    if (p->nx <= 0 || p->nu <= 0 || p->N <= 0 || p->nx > 16) {
-        g_create_error = "tmpc_create_regulator: need 0 < nx <= 16, nu > 0, N > 0";
-        return TMPC_E_INVALID;
-    }
-    tmpc_handle *h = new (std::nothrow) tmpc_handle();
-    if (!h) { g_create_error = "out of memory"; return TMPC_E_NOMEM; }
-    h->device = device; h->nx = p->nx; h->nu = p->nu; h->N = p->N;
-    h->regulator = true;
-    h->reg_tube = p->tube ? 1 : 0;
-    h->nvariants = 1;
-    int rc = TMPC_OK;
-    try {
+    return create_handle("tmpc_create_regulator", p->nx, p->nu, p->N, device, out, [p](tmpc_handle *h, tmpc_problem &q) {
+        h->regulator = true;
+        h->reg_tube = p->tube ? 1 : 0;
+        h->nvariants = 1;
         const std::string msg = tmpc::condense_regulator(*p, h->v[0].c);
-        if (!msg.empty()) { h->err = "tmpc_create_regulator: " + msg; rc = TMPC_E_INVALID; }
-        if (rc == TMPC_OK) {
-            const size_t nx = p->nx, nu = p->nu;
-            h->hA.assign(p->A, p->A + nx * nx);
-            h->hB.assign(p->B, p->B + nx * nu);
-            h->hQ.assign(p->Q, p->Q + nx * nx);
-            h->hR.assign(p->R, p->R + nu * nu);
-            if (p->K) h->hK.assign(p->K, p->K + nu * nx);
-            // what the kernel layouts read beyond the condensed QP
-            tmpc_problem q{};
-            q.nx = p->nx; q.nu = p->nu; q.N = p->N;
-            q.max_iter = p->max_iter; q.tol = p->tol;
-            q.A = p->A; q.B = p->B;
-            rc = setup_handle(h, q, device);
-        }
-    } catch (const std::exception &ex) {
-        h->err = std::string("tmpc_create_regulator: ") + ex.what();
-        rc = TMPC_E_NOMEM;
-    }
-    if (rc != TMPC_OK) {
-        g_create_error = h->err;
-        tmpc_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return TMPC_OK;
+        if (!msg.empty()) return msg;
+        const size_t nx = p->nx, nu = p->nu;
+        h->hA.assign(p->A, p->A + nx * nx);
+        h->hB.assign(p->B, p->B + nx * nu);
+        h->hQ.assign(p->Q, p->Q + nx * nx);
+        h->hR.assign(p->R, p->R + nu * nu);
+        if (p->K) h->hK.assign(p->K, p->K + nu * nx);
+        // what the kernel layouts read beyond the condensed QP
+        q.nx = p->nx; q.nu = p->nu; q.N = p->N;
+        q.max_iter = p->max_iter; q.tol = p->tol;
+        q.A = p->A; q.B = p->B;
+        return msg;
+    });
 }
 
 void tmpc_destroy(tmpc_handle *h) {
@@ -771,11 +811,10 @@ void tmpc_destroy(tmpc_handle *h) {
     }
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    free_staging(h);
-    {
-        void *wsp[] = {h->blk_ws, h->mc_arena, h->wc.ring, h->d_ticks, h->save_buf, h->reg_zero};
-        for (void *q2 : wsp) if (q2) (void)hipFree(q2);
-    }
+    for (DeviceBuffer *b : {&h->blk_ws, &h->save, &h->ticks, &h->reg_zero, &h->stage_dev}) b->release();
+    h->arena.release();
+    if (h->stage_pin) (void)hipHostFree(h->stage_pin);
+    if (h->wc.ring) (void)hipFree(h->wc.ring);
     for (int k = 0; k < 2; ++k)
         for (void *p : h->v[k].dev) (void)hipFree(p);
     for (auto &pr : h->pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -785,70 +824,54 @@ void tmpc_destroy(tmpc_handle *h) {
 
 int tmpc_solve_batch_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
                             double *u_nom, double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters) {
-    if (!h) return TMPC_E_INVALID;
-    if (B < 0 || !x_k || (!ref && !h->regulator) || !u_nom || !status || !iters) { h->err = "tmpc_solve_batch_device: NULL argument"; return TMPC_E_INVALID; }
-    if (h->regulator && (xu_ss || variant)) { h->err = "tmpc_solve_batch_device: a regulator handle has no steady state and one problem (xu_ss, variant must be NULL)"; return TMPC_E_INVALID; }
-    if (B == 0) return TMPC_OK;
-    if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (const int rc = check_solve(h, "tmpc_solve_batch_device", B, x_k, ref, variant, u_nom, xu_ss, status, iters, false); rc || B == 0) return rc;
     if (h->regulator) {
         const int rz = ensure_reg_zero(h, B);
         if (rz) return rz;
-        ref = h->reg_zero;
+        ref = h->reg_zero.as<double>();
     }
     return enqueue(h, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters);
 }
 
 int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
                      double *u_nom, double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters) {
-    if (!h) return TMPC_E_INVALID;
-    if (B < 0 || !x_k || (!ref && !h->regulator) || !u_nom || !status || !iters) { h->err = "tmpc_solve_batch: NULL argument"; return TMPC_E_INVALID; }
-    if (h->regulator && (xu_ss || variant)) { h->err = "tmpc_solve_batch: a regulator handle has no steady state and one problem (xu_ss, variant must be NULL)"; return TMPC_E_INVALID; }
-    if (B == 0) return TMPC_OK;
-    if (variant)
-        for (int64_t i = 0; i < B; ++i)
-            if (variant[i] >= h->nvariants) { h->err = "tmpc_solve_batch: variant id out of range"; return TMPC_E_INVALID; }
-    if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_staging(h, B);
-    if (rc) return rc;
+    int rc = check_solve(h, "tmpc_solve_batch", B, x_k, ref, variant, u_nom, xu_ss, status, iters, true);
+    if (rc || B == 0) return rc;
+    if ((rc = ensure_staging(h, B))) return rc;
     if (h->regulator && (rc = ensure_reg_zero(h, B))) return rc;
-    double *const d_ref = h->regulator ? h->reg_zero : h->d_r;      // (regulator: ref is ignored)
     const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(B);
+    // the caller's arrays and their offsets in the input / output part of the staging block (host NULL: not given / not wanted)
+    const struct { size_t off; const void *host; size_t bytes; } in[] = {
+        {0, x_k, b * nx * sizeof(double)}, {h->off_r, h->regulator ? nullptr : ref, b * nx * sizeof(double)}, {h->off_var, variant, b}};
+    const struct { size_t off; void *host; size_t bytes; } out[] = {
+        {0, u_nom, b * N * nu * sizeof(double)}, {h->off_x0, x_nom0, b * nx * sizeof(double)}, {h->off_ss, xu_ss, b * (nx + nu) * sizeof(double)},
+        {h->off_st, status, b * sizeof(int32_t)}, {h->off_it, iters, b * sizeof(int32_t)}, {h->off_xn, x_nom, b * (N + 1) * nx * sizeof(double)}};
+    char *const dev_in = h->stage_dev.p, *const dev_out = dev_in + h->stage_in_bytes;
+    auto launch = [&]() {
+        return enqueue(h, B, h->d_x, h->regulator ? h->reg_zero.as<double>() : h->d_r, variant ? h->d_var : nullptr, h->d_u, h->d_x0,
+                       h->d_ss, x_nom ? h->d_xn : nullptr, h->d_st, h->d_it);
+    };
     if (h->stage_pin != nullptr) {
-        // through the pinned mirror: one DMA in, one out
-        char *pin_in = h->stage_pin, *pin_out = h->stage_pin + h->stage_in_bytes;
-        std::memcpy(pin_in, x_k, b * nx * sizeof(double));
-        if (!h->regulator) std::memcpy(pin_in + h->off_r, ref, b * nx * sizeof(double));
-        size_t in_bytes = h->off_r + b * nx * sizeof(double);
-        if (variant) { std::memcpy(pin_in + h->off_var, variant, b); in_bytes = h->off_var + b; }
-        HIP_TRY(h, hipMemcpyAsync(h->stage_dev, pin_in, in_bytes, hipMemcpyHostToDevice, h->stream));
-        rc = enqueue(h, B, h->d_x, d_ref, variant ? h->d_var : nullptr, h->d_u, h->d_x0, h->d_ss, x_nom ? h->d_xn : nullptr,
-                     h->d_st, h->d_it);
-        if (rc) return rc;
-        const size_t out_bytes = x_nom ? h->off_xn + b * (N + 1) * nx * sizeof(double) : h->off_it + b * sizeof(int32_t);
-        HIP_TRY(h, hipMemcpyAsync(pin_out, h->stage_dev + h->stage_in_bytes, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        // through the pinned mirror: one DMA in, one out, each up to the last array given
+        char *const pin_in = h->stage_pin, *const pin_out = h->stage_pin + h->stage_in_bytes;
+        size_t in_bytes = 0, out_bytes = 0;
+        for (const auto &a : in)
+            if (a.host) { std::memcpy(pin_in + a.off, a.host, a.bytes); in_bytes = a.off + a.bytes; }
+        for (const auto &a : out)
+            if (a.host) out_bytes = a.off + a.bytes;
+        HIP_TRY(h, hipMemcpyAsync(dev_in, pin_in, in_bytes, hipMemcpyHostToDevice, h->stream));
+        if ((rc = launch())) return rc;
+        HIP_TRY(h, hipMemcpyAsync(pin_out, dev_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        std::memcpy(u_nom, pin_out, b * N * nu * sizeof(double));
-        if (x_nom0) std::memcpy(x_nom0, pin_out + h->off_x0, b * nx * sizeof(double));
-        if (xu_ss) std::memcpy(xu_ss, pin_out + h->off_ss, b * (nx + nu) * sizeof(double));
-        std::memcpy(status, pin_out + h->off_st, b * sizeof(int32_t));
-        std::memcpy(iters, pin_out + h->off_it, b * sizeof(int32_t));
-        if (x_nom) std::memcpy(x_nom, pin_out + h->off_xn, b * (N + 1) * nx * sizeof(double));
+        for (const auto &a : out)
+            if (a.host) std::memcpy(a.host, pin_out + a.off, a.bytes);
         return TMPC_OK;
     }
-    HIP_TRY(h, hipMemcpyAsync(h->d_x, x_k, b * nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (!h->regulator) HIP_TRY(h, hipMemcpyAsync(h->d_r, ref, b * nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (variant) HIP_TRY(h, hipMemcpyAsync(h->d_var, variant, b, hipMemcpyHostToDevice, h->stream));
-    rc = enqueue(h, B, h->d_x, d_ref, variant ? h->d_var : nullptr, h->d_u, h->d_x0, h->d_ss, x_nom ? h->d_xn : nullptr,
-                 h->d_st, h->d_it);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(u_nom, h->d_u, b * N * nu * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (x_nom0) HIP_TRY(h, hipMemcpyAsync(x_nom0, h->d_x0, b * nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (xu_ss) HIP_TRY(h, hipMemcpyAsync(xu_ss, h->d_ss, b * (nx + nu) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (x_nom) HIP_TRY(h, hipMemcpyAsync(x_nom, h->d_xn, b * (N + 1) * nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(status, h->d_st, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(iters, h->d_it, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    for (const auto &a : in)
+        if (a.host) HIP_TRY(h, hipMemcpyAsync(dev_in + a.off, a.host, a.bytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = launch())) return rc;
+    for (const auto &a : out)
+        if (a.host) HIP_TRY(h, hipMemcpyAsync(a.host, dev_out + a.off, a.bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return TMPC_OK;
 }
@@ -874,28 +897,11 @@ int tmpc_debug_dump_layout(const tmpc_handle *h, int variant, const char *path) 
     if (h->device >= 0) return TMPC_E_UNSUPPORTED;            // the arrays of a device handle live in HBM
     const Variant &v = h->v[variant];
     if (!v.wave_ok) return TMPC_E_UNSUPPORTED;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return TMPC_E_INVALID;
     const int32_t shp[6] = {v.shape.nvp, v.shape.dp, v.shape.ds, v.shape.kcp, v.shape.cp, v.shape.cs};
     const uint64_t qp_bytes = sizeof(tmpc::DeviceQP);
-    const int32_t tag[2] = {tmpc::DUMP_TAG, tmpc::DUMP_FORMAT};
-    std::fwrite(tag, 4, 2, f);
-    std::fwrite(shp, 4, 6, f);
-    std::fwrite(&qp_bytes, 8, 1, f);
-    std::fwrite(&v.d, sizeof(tmpc::DeviceQP), 1, f);
-    // every array the structure points to, in the order of its fields: byte count, bytes (0: null pointer)
-    const void *ptrs[] = {v.d.Gt, v.d.Hct, v.d.Psi, v.d.Hs, v.d.Hinv, v.d.F1s, v.d.F2s, v.d.g0p, v.d.Esp, v.d.vmask, v.d.row_of,
-                          v.d.gp0, v.d.Ep, v.d.Dv, v.d.Tzs, v.d.Txf, v.d.Mth, v.d.A, v.d.B, v.d.cip};
-    for (const void *q : ptrs) {
-        uint64_t n = 0;
-        if (q)
-            for (size_t i = 0; i < v.dev.size(); ++i)
-                if (v.dev[i] == q) { n = v.dev_bytes[i]; break; }
-        std::fwrite(&n, 8, 1, f);
-        if (n) std::fwrite(q, 1, n, f);
-    }
-    std::fclose(f);
-    return TMPC_OK;
+    return write_dump(path, v, {{shp, sizeof shp}, {&qp_bytes, sizeof qp_bytes}, {&v.d, sizeof v.d}},
+                      {v.d.Gt, v.d.Hct, v.d.Psi, v.d.Hs, v.d.Hinv, v.d.F1s, v.d.F2s, v.d.g0p, v.d.Esp, v.d.vmask, v.d.row_of,
+                       v.d.gp0, v.d.Ep, v.d.Dv, v.d.Tzs, v.d.Txf, v.d.Mth, v.d.A, v.d.B, v.d.cip});
 }
 
 int tmpc_debug_dump_block_layout(const tmpc_handle *h, int variant, const char *path) {
@@ -903,28 +909,11 @@ int tmpc_debug_dump_block_layout(const tmpc_handle *h, int variant, const char *
     if (h->device >= 0) return TMPC_E_UNSUPPORTED;
     const Variant &v = h->v[variant];
     if (v.tiles == 0) return TMPC_E_UNSUPPORTED;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return TMPC_E_INVALID;
     const int32_t hd[2] = {v.tiles, tmpc::block_workspace_rows()};
     const uint64_t sz[2] = {sizeof(tmpc::DeviceQP), sizeof(tmpc::BlockQP)};
-    const int32_t tag[2] = {tmpc::DUMP_TAG, tmpc::DUMP_FORMAT};
-    std::fwrite(tag, 4, 2, f);
-    std::fwrite(hd, 4, 2, f);
-    std::fwrite(sz, 8, 2, f);
-    std::fwrite(&v.db, sizeof(tmpc::DeviceQP), 1, f);
-    std::fwrite(&v.bq, sizeof(tmpc::BlockQP), 1, f);
-    const void *ptrs[] = {v.db.Hs, v.db.Hinv, v.db.F1s, v.db.F2s, v.db.gp0, v.db.Ep, v.db.Dv, v.db.Tzs, v.db.Txf, v.db.Mth, v.db.A, v.db.B,
-                          v.bq.Grm, v.bq.Gcm, v.bq.GHrm, v.bq.g0, v.bq.Es, v.bq.ncols, v.bq.Gw == v.bq.Grm ? nullptr : v.bq.Gw, v.bq.ci};
-    for (const void *q : ptrs) {
-        uint64_t n = 0;
-        if (q)
-            for (size_t i = 0; i < v.dev.size(); ++i)
-                if (v.dev[i] == q) { n = v.dev_bytes[i]; break; }
-        std::fwrite(&n, 8, 1, f);
-        if (n) std::fwrite(q, 1, n, f);
-    }
-    std::fclose(f);
-    return TMPC_OK;
+    return write_dump(path, v, {{hd, sizeof hd}, {sz, sizeof sz}, {&v.db, sizeof v.db}, {&v.bq, sizeof v.bq}},
+                      {v.db.Hs, v.db.Hinv, v.db.F1s, v.db.F2s, v.db.gp0, v.db.Ep, v.db.Dv, v.db.Tzs, v.db.Txf, v.db.Mth, v.db.A, v.db.B,
+                       v.bq.Grm, v.bq.Gcm, v.bq.GHrm, v.bq.g0, v.bq.Es, v.bq.ncols, v.bq.Gw == v.bq.Grm ? nullptr : v.bq.Gw, v.bq.ci});
 }
 
 const char *tmpc_kernel_name(const tmpc_handle *h, int variant) {
@@ -964,11 +953,11 @@ int tmpc_mc_set_capture(tmpc_handle *h, int64_t index) {
 
 int tmpc_mc_get_capture(tmpc_handle *h, int32_t T, double *x_traj, double *x_nom_traj, double *u_traj) {
     if (!h) return TMPC_E_INVALID;
-    if (!h->mc_cap_dev || T != h->mc_cap_T) { h->err = "tmpc_mc_get_capture: no trajectory of this length was recorded by the last tmpc_mc_run"; return TMPC_E_INVALID; }
+    if (!h->rec.cap || T != h->rec.cap_T) { h->err = "tmpc_mc_get_capture: no trajectory of this length was recorded by the last tmpc_mc_run"; return TMPC_E_INVALID; }
     const size_t nx = h->nx, nu = h->nu, w = 2 * nx + nu;
     std::vector<double> buf(static_cast<size_t>(T) * w);
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpy(buf.data(), h->mc_cap_dev, buf.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(buf.data(), h->rec.cap, buf.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int t = 0; t < T; ++t) {
         for (size_t i = 0; i < nx; ++i) {
             if (x_traj) x_traj[t * nx + i] = buf[t * w + i];
@@ -988,21 +977,21 @@ int tmpc_set_solve_timing(tmpc_handle *h, int on) {
 
 int tmpc_get_solve_ticks(tmpc_handle *h, int64_t B, int64_t *ticks) {
     if (!h || !ticks) return TMPC_E_INVALID;
-    if (!h->want_ticks || B != h->ticks_n || !h->d_ticks) { h->err = "tmpc_get_solve_ticks: no solve of this batch size was timed (tmpc_set_solve_timing)"; return TMPC_E_INVALID; }
+    if (!h->want_ticks || B != h->ticks_n || !h->ticks.p) { h->err = "tmpc_get_solve_ticks: no solve of this batch size was timed (tmpc_set_solve_timing)"; return TMPC_E_INVALID; }
     static_assert(sizeof(long long) == sizeof(int64_t), "tick counts are 64-bit");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(ticks, h->d_ticks, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(ticks, h->ticks.p, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
 
 int tmpc_mc_get_solve_ticks(tmpc_handle *h, int64_t B, int64_t *ticks_sum, int64_t *ticks_max) {
     if (!h) return TMPC_E_INVALID;
-    if (!h->mc_tick_sum || B != h->mc_tick_B) { h->err = "tmpc_mc_get_solve_ticks: the last tmpc_mc_run was not timed (tmpc_set_solve_timing) or had another batch size"; return TMPC_E_INVALID; }
+    if (!h->rec.tick_sum || B != h->rec.tick_B) { h->err = "tmpc_mc_get_solve_ticks: the last tmpc_mc_run was not timed (tmpc_set_solve_timing) or had another batch size"; return TMPC_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (ticks_sum) HIP_TRY(h, hipMemcpy(ticks_sum, h->mc_tick_sum, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (ticks_max) HIP_TRY(h, hipMemcpy(ticks_max, h->mc_tick_max, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (ticks_sum) HIP_TRY(h, hipMemcpy(ticks_sum, h->rec.tick_sum, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (ticks_max) HIP_TRY(h, hipMemcpy(ticks_max, h->rec.tick_max, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
 
@@ -1019,10 +1008,10 @@ int tmpc_mc_set_device_rng(tmpc_handle *h, int on, uint64_t seed, int64_t first_
 
 int tmpc_mc_get_physics_error(tmpc_handle *h, int64_t B, double *err2_phys) {
     if (!h || !err2_phys) return TMPC_E_INVALID;
-    if (!h->mc_err2_phys || B != h->mc_phys_B) { h->err = "tmpc_mc_get_physics_error: the last tmpc_mc_run had the linear plant or another batch size"; return TMPC_E_INVALID; }
+    if (!h->rec.err2_phys || B != h->rec.phys_B) { h->err = "tmpc_mc_get_physics_error: the last tmpc_mc_run had the linear plant or another batch size"; return TMPC_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(err2_phys, h->mc_err2_phys, static_cast<size_t>(B) * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(err2_phys, h->rec.err2_phys, static_cast<size_t>(B) * sizeof(double), hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
 
@@ -1039,7 +1028,7 @@ int tmpc_mc_set_fused(tmpc_handle *h, int mode) {
     return TMPC_OK;
 }
 
-int tmpc_mc_last_fused(const tmpc_handle *h) { return h ? h->mc_last_fused : 0; }
+int tmpc_mc_last_fused(const tmpc_handle *h) { return h ? h->rec.fused : 0; }
 
 }  // extern "C"
 
@@ -1064,240 +1053,135 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
     if (h->hK.empty() || h->hKanc.empty()) { h->err = "tmpc_mc_run: the problem description carries no gains K / K_anc"; return TMPC_E_INVALID; }
     if (h->nu > 16) { h->err = "tmpc_mc_run: nu <= 16"; return TMPC_E_UNSUPPORTED; }
     if (B == 0 || T == 0) return TMPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_staging(h, B);
+    int rc = begin_loop(h, B);
     if (rc) return rc;
     const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(B), t_ = static_cast<size_t>(T);
-    // upper bound of what the carve-outs below need (each rounded up to 256 B)
-    const size_t need = 256 * 54 + sizeof(tmpc::McFused) + 8 * t_ + b + 8 * (4 * nx * nx + 4 * nu * nx + static_cast<size_t>(rZ) * (nx + 1) + b * (2 + (host_draws ? 2 * t_ + t_ * nx : 0)) + nx) +
-                        8 * b * (6 * nx + (N + 1) * nu + nu + 5) + 4 * b * 8 + 2 * b + 2 * 4 * b * tmpc::WS_STRIDE + 8 * t_ * (2 * nx + nu) +
-                        (rp ? b * t_ * (8 * ((N + 1) * nu + nx) + 8 * (3 * nx + nu) + 4 * 3) : 0);
-    // what the previous run left in the arena is gone from here on, whether this run gets as far as replacing it or not
-    // (tmpc_mc_get_capture / _solve_ticks / _physics_error must not read a freed or half-written arena)
-    h->mc_cap_dev = nullptr; h->mc_cap_T = 0;
-    h->mc_err2_phys = nullptr; h->mc_phys_B = 0;
-    h->mc_tick_sum = h->mc_tick_max = nullptr; h->mc_tick_B = 0;
-    if (need > h->mc_arena_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->mc_arena) (void)hipFree(h->mc_arena);
-        h->mc_arena = nullptr;
-        h->mc_arena_bytes = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->mc_arena), need));
-        h->mc_arena_bytes = need;
+    // ONE launch for the whole sweep where the controller has one problem and it runs on the wave kernel: a wave keeps its
+    // trajectory for all T steps, solve and state machines alternating inside the kernel (tmpc_fused.hip).  The work item of
+    // that launch is a trajectory, T solves long: with B a little above a multiple of the resident waves the last round
+    // of trajectories would run on a nearly empty card, so TMPC_MC_FUSED_AUTO fuses when the rounds are at least 85 % full
+    // (or there is a single round) and otherwise keeps the launch per time step, whose work item is one solve.
+    bool fuse = !rp && !extended && h->mc_fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]);
+    if (fuse && h->mc_fused == TMPC_MC_FUSED_AUTO) {
+        const int64_t slots = tmpc::resident_waves(h->v[0].shape, h->n_cu);
+        const int64_t rounds = slots > 0 ? (B + slots - 1) / slots : 0;
+        fuse = rounds == 1 || (rounds > 0 && static_cast<double>(B) >= 0.85 * static_cast<double>(rounds * slots));
     }
-    size_t arena_off = 0;
-    auto dalloc = [&](size_t bytes, void **out) -> int {
-        const size_t sz = ((bytes ? bytes : 8) + 255) / 256 * 256;
-        if (arena_off + sz > h->mc_arena_bytes) { h->err = "tmpc_mc_run: internal arena too small"; return TMPC_E_NOMEM; }
-        *out = h->mc_arena + arena_off;
-        arena_off += sz;
-        return TMPC_OK;
-    };
-    auto up = [&](const void *src, size_t bytes, const void **out) -> int {
-        void *q2 = nullptr;
-        int r2 = dalloc(bytes, &q2);
-        if (r2) return r2;
-        HIP_TRY(h, hipMemcpyAsync(q2, src, bytes, hipMemcpyHostToDevice, h->stream));
-        *out = q2;
-        return TMPC_OK;
-    };
+    // the extended controller (two problems, two kernel shapes): per time step ONE launch per problem with the state machines of
+    // its trajectories inside (closed_loop_step_kernel) -- two launches per step where the plain per-step loop has three
+    // (TMPC_MC_FUSED_AUTO: from one round of resident waves on -- below that a step is the latency of its launches, and the state
+    // machines inside BOTH of them lengthen it: 200 trajectories at N = 20 0.0345 s with three launches per step, 0.0367 s with two)
+    bool step_fuse = !rp && extended && h->mc_fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]) && !use_block(h, h->v[1]);
+    if (step_fuse && h->mc_fused == TMPC_MC_FUSED_AUTO) step_fuse = B >= tmpc::resident_waves(h->v[1].shape, h->n_cu);
+    // the fused kernels' record {model, state, T, reference}: uploaded once the state is carved; lives until the final synchronise
+    tmpc::McFused mf{};
     auto run = [&]() -> int {
         tmpc::McModel m{};
         tmpc::McState st{};
         m.nx = h->nx; m.nu = h->nu; m.N = h->N; m.extended = extended ? 1 : 0; m.rZ = rZ;
         m.plant = h->plant; m.substeps = h->plant_substeps; m.smart = h->actuator == TMPC_ACTUATOR_SMART ? 1 : 0;
         for (int i = 0; i < 7; ++i) m.par[i] = h->plant_par[i];
-        int r2;
-        if ((r2 = up(h->hA.data(), nx * nx * 8, reinterpret_cast<const void **>(&m.A)))) return r2;
-        if ((r2 = up(h->hB.data(), nx * nu * 8, reinterpret_cast<const void **>(&m.B)))) return r2;
-        if ((r2 = up(h->hK.data(), nu * nx * 8, reinterpret_cast<const void **>(&m.K)))) return r2;
-        if ((r2 = up(h->hKanc.data(), nu * nx * 8, reinterpret_cast<const void **>(&m.K_anc)))) return r2;
-        if ((r2 = up(HZ, static_cast<size_t>(rZ) * nx * 8, reinterpret_cast<const void **>(&m.HZ)))) return r2;
-        if ((r2 = up(hZ, static_cast<size_t>(rZ) * 8, reinterpret_cast<const void **>(&m.hZ)))) return r2;
-        if ((r2 = up(p_loss, b * 8, reinterpret_cast<const void **>(&st.p_loss)))) return r2;
+        Arena &a = h->arena;
+        a.piece(&m.A, nx * nx * 8, h->hA.data());
+        a.piece(&m.B, nx * nu * 8, h->hB.data());
+        a.piece(&m.K, nu * nx * 8, h->hK.data());
+        a.piece(&m.K_anc, nu * nx * 8, h->hKanc.data());
+        a.piece(&m.HZ, static_cast<size_t>(rZ) * nx * 8, HZ);
+        a.piece(&m.hZ, static_cast<size_t>(rZ) * 8, hZ);
+        a.piece(&st.p_loss, b * 8, p_loss);
         if (host_draws) {
-            if ((r2 = up(th_u, b * t_ * 8, reinterpret_cast<const void **>(&st.th_u)))) return r2;
-            if ((r2 = up(ga_u, b * t_ * 8, reinterpret_cast<const void **>(&st.ga_u)))) return r2;
-            if ((r2 = up(w, b * t_ * nx * 8, reinterpret_cast<const void **>(&st.w)))) return r2;
+            a.piece(&st.th_u, b * t_ * 8, th_u);
+            a.piece(&st.ga_u, b * t_ * 8, ga_u);
+            a.piece(&st.w, b * t_ * nx * 8, w);
         } else {
             st.rng_on = 1;
             st.rng_seed = h->mc_rng_seed;
             st.rng_first = h->mc_rng_first;
-            if ((r2 = up(h->mc_w_bound.data(), nx * 8, reinterpret_cast<const void **>(&st.w_bound)))) return r2;
+            a.piece(&st.w_bound, nx * 8, h->mc_w_bound.data());
         }
-        struct { void **p; size_t bytes; int fill; } arrays[] = {
-            {reinterpret_cast<void **>(&st.x), b * nx * 8, 0}, {reinterpret_cast<void **>(&st.x_hat), b * nx * 8, 0},
-            {reinterpret_cast<void **>(&st.x_nom), b * nx * 8, 0}, {reinterpret_cast<void **>(&st.Ubuf), b * (N + 1) * nu * 8, 0},
-            {reinterpret_cast<void **>(&st.u_latest0), b * nu * 8, 0}, {reinterpret_cast<void **>(&st.x_nom0_latest), b * nx * 8, 0},
-            {reinterpret_cast<void **>(&st.ref_k), b * nx * 8, 0},
-            {reinterpret_cast<void **>(&st.err2), b * 8, 0},
-            {reinterpret_cast<void **>(&st.consistent), b * 8, 0}, {reinterpret_cast<void **>(&st.q_est), b * 4, 0},
-            {reinterpret_cast<void **>(&st.q_act), b * 4, 0}, {reinterpret_cast<void **>(&st.s), b * 4, 0},
-            {reinterpret_cast<void **>(&st.Theta), b * 4, 0}, {reinterpret_cast<void **>(&st.last_lost), b * 4, 0xFF},
-            {reinterpret_cast<void **>(&st.tube_viol), b * 4, 0}, {reinterpret_cast<void **>(&st.not_optimal), b * 4, 0},
-            {reinterpret_cast<void **>(&st.iters_sum), b * 4, 0},
-            {reinterpret_cast<void **>(&st.gamma), b, 1}, {reinterpret_cast<void **>(&st.dead), b, 0}};
-        for (auto &a : arrays) {
-            if ((r2 = dalloc(a.bytes, a.p))) return r2;
-            HIP_TRY(h, hipMemsetAsync(*a.p, a.fill, a.bytes, h->stream));        // 0xFF bytes = -1 for last_lost; gamma = 1
-        }
-        if (x0) {
-            HIP_TRY(h, hipMemcpyAsync(st.x, x0, b * nx * 8, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(st.x_hat, x0, b * nx * 8, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(st.x_nom, x0, b * nx * 8, hipMemcpyHostToDevice, h->stream));
-        }
+        // the state starts at x0 (or 0), with last_lost = -1 (0xFF bytes), gamma = 1 and every statistic 0
+        for (double **x : {&st.x, &st.x_hat, &st.x_nom}) a.piece(x, b * nx * 8, x0, 0);
+        a.piece(&st.Ubuf, b * (N + 1) * nu * 8, nullptr, 0);
+        a.piece(&st.u_latest0, b * nu * 8, nullptr, 0);
+        for (double **x : {&st.x_nom0_latest, &st.ref_k}) a.piece(x, b * nx * 8, nullptr, 0);
+        for (double **x : {&st.err2, &st.consistent}) a.piece(x, b * 8, nullptr, 0);
+        for (int32_t **c : {&st.q_est, &st.q_act, &st.s, &st.Theta, &st.last_lost, &st.tube_viol, &st.not_optimal, &st.iters_sum})
+            a.piece(c, b * 4, nullptr, c == &st.last_lost ? 0xFF : 0);
+        a.piece(&st.gamma, b, nullptr, 1);
+        a.piece(&st.dead, b, nullptr, 0);
         st.cap_index = -1;
-        st.cap = nullptr;
-        h->mc_cap_dev = nullptr;
         if (h->mc_capture >= 0 && h->mc_capture < B) {
-            if ((r2 = dalloc(t_ * (2 * nx + nu) * 8, reinterpret_cast<void **>(&st.cap)))) return r2;
-            HIP_TRY(h, hipMemsetAsync(st.cap, 0, t_ * (2 * nx + nu) * 8, h->stream));
+            a.piece(&st.cap, t_ * (2 * nx + nu) * 8, nullptr, 0);
             st.cap_index = h->mc_capture;
-            h->mc_cap_dev = st.cap;
-            h->mc_cap_T = T;
         }
-        h->mc_err2_phys = nullptr;
-        h->mc_phys_B = 0;
-        if (m.plant != TMPC_PLANT_LINEAR) {
-            if ((r2 = dalloc(b * 8, reinterpret_cast<void **>(&st.err2_phys)))) return r2;
-            HIP_TRY(h, hipMemsetAsync(st.err2_phys, 0, b * 8, h->stream));
-            h->mc_err2_phys = st.err2_phys; h->mc_phys_B = B;
-        }
-        h->mc_tick_sum = h->mc_tick_max = nullptr;
-        h->mc_tick_B = 0;
+        if (m.plant != TMPC_PLANT_LINEAR) a.piece(&st.err2_phys, b * 8, nullptr, 0);
         if (h->want_ticks) {
-            if ((r2 = dalloc(b * 8, reinterpret_cast<void **>(&st.tick_sum)))) return r2;
-            if ((r2 = dalloc(b * 8, reinterpret_cast<void **>(&st.tick_max)))) return r2;
-            HIP_TRY(h, hipMemsetAsync(st.tick_sum, 0, b * 8, h->stream));
-            HIP_TRY(h, hipMemsetAsync(st.tick_max, 0, b * 8, h->stream));
-            h->mc_tick_sum = st.tick_sum; h->mc_tick_max = st.tick_max; h->mc_tick_B = B;
+            a.piece(&st.tick_sum, b * 8, nullptr, 0);
+            a.piece(&st.tick_max, b * 8, nullptr, 0);
         }
         // warm start: one working-set record per trajectory and variant (row ids are per variant), updated in place by the
-        // solve kernel; m = 0 (the memset) means "nothing to start from"
+        // solve kernel; m = 0 (the zero fill) means "nothing to start from"
         int32_t *ws[2] = {nullptr, nullptr};
-        if (h->mc_warm) {
-            for (int k = 0; k < (extended ? 2 : 1); ++k) {
-                if ((r2 = dalloc(b * tmpc::WS_STRIDE * 4, reinterpret_cast<void **>(&ws[k])))) return r2;
-                HIP_TRY(h, hipMemsetAsync(ws[k], 0, b * tmpc::WS_STRIDE * 4, h->stream));
-            }
-        }
+        if (h->mc_warm)
+            for (int k = 0; k < (extended ? 2 : 1); ++k) a.piece(&ws[k], b * tmpc::WS_STRIDE * 4, nullptr, 0);
         if (rp) {
-            if ((r2 = up(rp->U, b * t_ * (N + 1) * nu * 8, reinterpret_cast<const void **>(&st.rp_U)))) return r2;
-            if (rp->xn0) { if ((r2 = up(rp->xn0, b * t_ * nx * 8, reinterpret_cast<const void **>(&st.rp_xn0)))) return r2; }
-            else {
-                // (plain controller: the packets carry no x_nom_0; the state machines then never read it -- zeros)
-                void *z = nullptr;
-                if ((r2 = dalloc(b * t_ * nx * 8, &z))) return r2;
-                HIP_TRY(h, hipMemsetAsync(z, 0, b * t_ * nx * 8, h->stream));
-                st.rp_xn0 = static_cast<const double *>(z);
-            }
-            if ((r2 = dalloc(b * t_ * (3 * nx + nu) * 8, reinterpret_cast<void **>(&st.trace_f)))) return r2;
-            if ((r2 = dalloc(b * t_ * 3 * 4, reinterpret_cast<void **>(&st.trace_i)))) return r2;
-            HIP_TRY(h, hipMemsetAsync(st.trace_f, 0, b * t_ * (3 * nx + nu) * 8, h->stream));
-            HIP_TRY(h, hipMemsetAsync(st.trace_i, 0, b * t_ * 3 * 4, h->stream));
+            // (plain controller: the packets carry no x_nom_0; the state machines then never read it -- zeros)
+            a.piece(&st.rp_U, b * t_ * (N + 1) * nu * 8, rp->U);
+            a.piece(&st.rp_xn0, b * t_ * nx * 8, rp->xn0, 0);
+            a.piece(&st.trace_f, b * t_ * (3 * nx + nu) * 8, nullptr, 0);
+            a.piece(&st.trace_i, b * t_ * 3 * 4, nullptr, 0);
         }
+        uint8_t *gam[2] = {nullptr, nullptr};           // selector read in a step / arrival flags written in it: swapped every step
+        tmpc::McFused *d_mf = nullptr;                  // the record itself lives in the arena: the kernel reads it field by field
+        if (fuse || step_fuse) {
+            a.piece(&mf.ref_seq, t_ * 8, ref);
+            if (step_fuse) a.piece(&gam[1], b, nullptr, 1);
+            a.piece(&d_mf, sizeof(mf));
+        }
+        HIP_TRY(h, a.carve(h->stream));
+        gam[0] = st.gamma;
+        if (st.cap) { h->rec.cap = st.cap; h->rec.cap_T = T; }
+        if (st.err2_phys) { h->rec.err2_phys = st.err2_phys; h->rec.phys_B = B; }
+        if (st.tick_sum) { h->rec.tick_sum = st.tick_sum; h->rec.tick_max = st.tick_max; h->rec.tick_B = B; }
         HIP_TRY(h, tmpc::launch_mc_pre(m, st, B, ref[0], h->stream));
-        // ONE launch for the whole sweep where the controller has one problem and it runs on the wave kernel: a wave keeps its
-        // trajectory for all T steps, solve and state machines alternating inside the kernel (tmpc_fused.hip).  The work item of
-        // that launch is a trajectory, T solves long: with B a little above a multiple of the resident waves the last round
-        // of trajectories would run on a nearly empty card, so TMPC_MC_FUSED_AUTO fuses when the rounds are at least 85 % full
-        // (or there is a single round) and otherwise keeps the launch per time step, whose work item is one solve.
-        h->mc_last_fused = 0;
-        bool fuse = !rp && !extended && h->mc_fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]);
-        if (fuse && h->mc_fused == TMPC_MC_FUSED_AUTO) {
-            const int64_t slots = tmpc::resident_waves(h->v[0].shape, h->n_cu);
-            const int64_t rounds = slots > 0 ? (B + slots - 1) / slots : 0;
-            fuse = rounds == 1 || (rounds > 0 && static_cast<double>(B) >= 0.85 * static_cast<double>(rounds * slots));
-        }
-        // the extended controller (two problems, two kernel shapes): per time step ONE launch per problem with the state machines of
-        // its trajectories inside (closed_loop_step_kernel) -- two launches per step where the plain per-step loop has three
-        // (TMPC_MC_FUSED_AUTO: from one round of resident waves on -- below that a step is the latency of its launches, and the state
-        // machines inside BOTH of them lengthen it: 200 trajectories at N = 20 0.0345 s with three launches per step, 0.0367 s with two)
-        bool step_fuse = !rp && extended && h->mc_fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]) && !use_block(h, h->v[1]);
-        if (step_fuse && h->mc_fused == TMPC_MC_FUSED_AUTO) step_fuse = B >= tmpc::resident_waves(h->v[1].shape, h->n_cu);
-        // per-solve tick buffer and the hand-over save slots of the wave kernel, as enqueue() provides them per call
-        auto prepare_wave = [&](int nvar) -> int {
-            long long *ticks = nullptr;
-            if (h->want_ticks) {
-                if (B > h->ticks_cap) {
-                    HIP_TRY(h, hipStreamSynchronize(h->stream));
-                    if (h->d_ticks) (void)hipFree(h->d_ticks);
-                    h->d_ticks = nullptr; h->ticks_cap = 0;
-                    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->d_ticks), static_cast<size_t>(B) * sizeof(long long)));
-                    h->ticks_cap = B;
-                }
-                ticks = h->d_ticks;
-                h->ticks_n = B;
-                HIP_TRY(h, hipMemsetAsync(ticks, 0, static_cast<size_t>(B) * sizeof(long long), h->stream));
-            }
-            st.ticks = ticks;
-            // (a slice of the save buffer per problem)
-            size_t need_save = 0, off_save[2] = {0, 0};
-            for (int k = 0; k < nvar; ++k) {
-                Variant &v = h->v[k];
-                v.d.ticks = ticks;
-                off_save[k] = need_save;
-                if (!tmpc::parks_in_lds(v.shape)) {
-                    const size_t rs = static_cast<size_t>(2 * v.shape.dp + v.shape.ds + 2 * v.shape.cp + v.shape.cs);
-                    need_save += static_cast<size_t>(h->n_cu) * 8 * 2 * rs * 64 * sizeof(float);
-                }
-            }
-            if (need_save > h->save_bytes) {
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                if (h->save_buf) (void)hipFree(h->save_buf);
-                h->save_buf = nullptr; h->save_bytes = 0;
-                HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->save_buf), need_save));
-                h->save_bytes = need_save;
-            }
-            for (int k = 0; k < nvar; ++k)
-                h->v[k].d.save = tmpc::parks_in_lds(h->v[k].shape) ? nullptr : h->save_buf + off_save[k] / sizeof(float);
-            return TMPC_OK;
-        };
-        if (step_fuse) {
-            tmpc::McFused mf{};
-            if ((r2 = up(ref, t_ * 8, reinterpret_cast<const void **>(&mf.ref_seq)))) return r2;
-            if ((r2 = prepare_wave(2))) return r2;
-            uint8_t *gam[2] = {st.gamma, nullptr};          // selector read in a step / arrival flags written in it: swapped every step
-            if ((r2 = dalloc(b, reinterpret_cast<void **>(&gam[1])))) return r2;
-            HIP_TRY(h, hipMemsetAsync(gam[1], 1, b, h->stream));
+        if (fuse || step_fuse) {
+            if (const int r2 = prepare_wave_scratch(h, B, step_fuse ? 2 : 1)) return r2;
+            st.ticks = h->want_ticks ? h->ticks.as<long long>() : nullptr;
             mf.m = m; mf.st = st; mf.T = T;
-            const tmpc::McFused *d_mf = nullptr;
-            if ((r2 = up(&mf, sizeof(mf), reinterpret_cast<const void **>(&d_mf)))) return r2;
+            HIP_TRY(h, hipMemcpyAsync(d_mf, &mf, sizeof(mf), hipMemcpyHostToDevice, h->stream));
+        }
+        if (step_fuse) {
             // (Measured and dropped: the two launches of a step on two streams, so that the second one's workgroups start on the CUs the
             // first one's tail leaves idle -- config 4 extended 0.27 -> 0.28 s: the fork / join events of every step cost more.)
             for (int t = 0; t < T; ++t) {
-                if ((r2 = begin_timed_launch(h))) return r2;
+                if (const int r2 = begin_timed_launch(h)) return r2;
                 for (int k = 0; k < 2; ++k)
                     HIP_TRY(h, tmpc::launch_solve_mc_step(h->v[k].d, h->v[k].shape, k, B, gam[t & 1], h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[k],
                                                           d_mf, t, gam[(t + 1) & 1], &h->wc, h->n_cu, h->stream));
                 HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
             }
             h->timed = true;
-            h->mc_last_fused = 2;
-            fuse = true;            // (the per-step loop below is skipped)
+            h->rec.fused = 2;
         } else if (fuse) {
-            tmpc::McFused mf{};
-            if ((r2 = up(ref, t_ * 8, reinterpret_cast<const void **>(&mf.ref_seq)))) return r2;
-            Variant &v = h->v[0];
-            if ((r2 = prepare_wave(1))) return r2;
-            mf.m = m; mf.st = st; mf.T = T;
-            const tmpc::McFused *d_mf = nullptr;            // the record itself lives in the arena: the kernel reads it field by field
-            if ((r2 = up(&mf, sizeof(mf), reinterpret_cast<const void **>(&d_mf)))) return r2;
-            if ((r2 = begin_timed_launch(h))) return r2;          // (the launch counts in tmpc_kernel_ms_total like any solve launch)
-            HIP_TRY(h, tmpc::launch_solve_mc(v.d, v.shape, B, h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[0], d_mf, &h->wc, h->n_cu, h->stream));
+            if (const int r2 = begin_timed_launch(h)) return r2;          // (the launch counts in tmpc_kernel_ms_total like any solve launch)
+            HIP_TRY(h, tmpc::launch_solve_mc(h->v[0].d, h->v[0].shape, B, h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[0], d_mf, &h->wc, h->n_cu,
+                                             h->stream));
             HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
             h->timed = true;
-            h->mc_last_fused = 1;
-        }
-        // Otherwise, per time step: the solve launch(es) -- one per problem variant in use -- and ONE launch of the state machines
-        // (round 3: mc_pre, the variant check, the solve, mc_post, mc_tube).  With injected packets nothing is solved.
-        for (int t = 0; t < T && !fuse; ++t) {
-            if (!rp) {
-                int r3 = enqueue(h, B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it, ws, true);
-                if (r3) return r3;
-                st.ticks = h->want_ticks ? h->d_ticks : nullptr;       // (allocated by the first enqueue)
+            h->rec.fused = 1;
+        } else {
+            // per time step: the solve launch(es) -- one per problem variant in use -- and ONE launch of the state machines
+            // (round 3: mc_pre, the variant check, the solve, mc_post, mc_tube).  With injected packets nothing is solved.
+            for (int t = 0; t < T; ++t) {
+                if (!rp) {
+                    const int r2 = enqueue(h, B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st,
+                                           h->d_it, ws, true);
+                    if (r2) return r2;
+                    st.ticks = h->want_ticks ? h->ticks.as<long long>() : nullptr;       // (allocated by the first enqueue)
+                }
+                HIP_TRY(h, tmpc::launch_mc_step(m, st, t, T, B, ref[t], ref[t + 1 < T ? t + 1 : t], h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it,
+                                                h->stream));
             }
-            HIP_TRY(h, tmpc::launch_mc_step(m, st, t, T, B, ref[t], ref[t + 1 < T ? t + 1 : t], h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, h->stream));
         }
         if (rp) {
             HIP_TRY(h, hipMemcpyAsync(rp->trace_f, st.trace_f, b * t_ * (3 * nx + nu) * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1356,90 +1240,52 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
     if (h->nu > 16) { h->err = "tmpc_reg_run: nu <= 16"; return TMPC_E_UNSUPPORTED; }
     if (B == 0 || T == 0) return TMPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_staging(h, B);
+    int rc = begin_loop(h, B);
     if (rc) return rc;
     if ((rc = ensure_reg_zero(h, B))) return rc;
     const size_t nx = h->nx, nu = h->nu, b = static_cast<size_t>(B), t_ = static_cast<size_t>(T);
     const bool host_w = w != nullptr, want_cap = capture >= 0 && capture < B && cap_x && cap_xn && cap_u;
-    // the state lives in the closed loop's grow-only arena (tmpc_mc_run's records there are gone from here on)
-    auto r256 = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t need = r256(8 * nx * nx) * 2 + r256(8 * nx * nu) + r256(8 * nu * nu) + r256(8 * nu * nx) + r256(8 * nx) +
-                        r256(8 * static_cast<size_t>(rX) * (nx + 1)) + r256(8 * static_cast<size_t>(rU) * (nu + 1)) +
-                        r256(8 * static_cast<size_t>(rZ) * (nx + 1)) + 6 * 256 + r256(8 * b * nx) + r256(8 * b) + 6 * r256(4 * b) +
-                        (host_w ? r256(8 * b * t_ * nx) : 0) + (want_cap ? r256(8 * (t_ + 1) * nx) + r256(8 * t_ * nx) + r256(8 * t_ * nu) : 0);
-    h->mc_cap_dev = nullptr; h->mc_cap_T = 0;
-    h->mc_err2_phys = nullptr; h->mc_phys_B = 0;
-    h->mc_tick_sum = h->mc_tick_max = nullptr; h->mc_tick_B = 0;
-    if (need > h->mc_arena_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->mc_arena) (void)hipFree(h->mc_arena);
-        h->mc_arena = nullptr;
-        h->mc_arena_bytes = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->mc_arena), need));
-        h->mc_arena_bytes = need;
-    }
-    size_t arena_off = 0;
-    auto dalloc = [&](size_t bytes, void **o) -> int {
-        const size_t sz = r256(bytes ? bytes : 8);
-        if (arena_off + sz > h->mc_arena_bytes) { h->err = "tmpc_reg_run: internal arena too small"; return TMPC_E_NOMEM; }
-        *o = h->mc_arena + arena_off;
-        arena_off += sz;
-        return TMPC_OK;
-    };
-    auto up = [&](const void *src, size_t bytes, const double **o) -> int {
-        void *q = nullptr;
-        int r2 = dalloc(bytes, &q);
-        if (r2) return r2;
-        if (bytes) HIP_TRY(h, hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream));
-        *o = static_cast<const double *>(q);
-        return TMPC_OK;
-    };
     auto run = [&]() -> int {
         tmpc::RegModel m{};
         tmpc::RegState st{};
         m.nx = h->nx; m.nu = h->nu; m.N = h->N; m.tube = h->reg_tube;
         m.rX = rX; m.rU = rU; m.rZ = rZ;
-        int r2;
-        if ((r2 = up(h->hA.data(), 8 * nx * nx, &m.A))) return r2;
-        if ((r2 = up(h->hB.data(), 8 * nx * nu, &m.B))) return r2;
-        if ((r2 = up(h->hQ.data(), 8 * nx * nx, &m.Q))) return r2;
-        if ((r2 = up(h->hR.data(), 8 * nu * nu, &m.R))) return r2;
-        if ((r2 = up(h->hK.data(), 8 * h->hK.size(), &m.K))) return r2;
-        if ((r2 = up(HX, 8 * static_cast<size_t>(rX) * nx, &m.HX))) return r2;
-        if ((r2 = up(hX, 8 * static_cast<size_t>(rX), &m.hX))) return r2;
-        if ((r2 = up(HU, 8 * static_cast<size_t>(rU) * nu, &m.HU))) return r2;
-        if ((r2 = up(hU, 8 * static_cast<size_t>(rU), &m.hU))) return r2;
-        if ((r2 = up(HZ, 8 * static_cast<size_t>(rZ) * nx, &m.HZ))) return r2;
-        if ((r2 = up(hZ, 8 * static_cast<size_t>(rZ), &m.hZ))) return r2;
-        if ((r2 = dalloc(8 * b * nx, reinterpret_cast<void **>(&st.x)))) return r2;
-        HIP_TRY(h, hipMemcpyAsync(st.x, x0, 8 * b * nx, hipMemcpyHostToDevice, h->stream));
-        if ((r2 = dalloc(8 * b, reinterpret_cast<void **>(&st.cost)))) return r2;
-        HIP_TRY(h, hipMemsetAsync(st.cost, 0, 8 * b, h->stream));
+        Arena &a = h->arena;
+        a.piece(&m.A, 8 * nx * nx, h->hA.data());
+        a.piece(&m.B, 8 * nx * nu, h->hB.data());
+        a.piece(&m.Q, 8 * nx * nx, h->hQ.data());
+        a.piece(&m.R, 8 * nu * nu, h->hR.data());
+        a.piece(&m.K, 8 * h->hK.size(), h->hK.data());
+        a.piece(&m.HX, 8 * static_cast<size_t>(rX) * nx, HX);
+        a.piece(&m.hX, 8 * static_cast<size_t>(rX), hX);
+        a.piece(&m.HU, 8 * static_cast<size_t>(rU) * nu, HU);
+        a.piece(&m.hU, 8 * static_cast<size_t>(rU), hU);
+        a.piece(&m.HZ, 8 * static_cast<size_t>(rZ) * nx, HZ);
+        a.piece(&m.hZ, 8 * static_cast<size_t>(rZ), hZ);
+        a.piece(&st.x, 8 * b * nx, x0);
+        a.piece(&st.cost, 8 * b, nullptr, 0);
         int32_t **counters[] = {&st.x_viol, &st.u_viol, &st.tube_viol, &st.not_optimal, &st.fail_step, &st.iters_sum};
-        for (int32_t **c : counters) {
-            if ((r2 = dalloc(4 * b, reinterpret_cast<void **>(c)))) return r2;
-            HIP_TRY(h, hipMemsetAsync(*c, c == &st.fail_step ? 0xFF : 0, 4 * b, h->stream));      // (0xFF bytes: fail_step = -1)
-        }
+        for (int32_t **c : counters) a.piece(c, 4 * b, nullptr, c == &st.fail_step ? 0xFF : 0);      // (0xFF bytes: fail_step = -1)
         if (host_w) {
-            if ((r2 = up(w, 8 * b * t_ * nx, &st.w))) return r2;
+            a.piece(&st.w, 8 * b * t_ * nx, w);
         } else if (h->mc_rng_on) {
             st.rng_on = 1;
             st.rng_seed = h->mc_rng_seed;
             st.rng_first = h->mc_rng_first;
-            if ((r2 = up(h->mc_w_bound.data(), 8 * nx, &st.w_bound))) return r2;
+            a.piece(&st.w_bound, 8 * nx, h->mc_w_bound.data());
         }
         st.cap_index = -1;
         if (want_cap) {
-            if ((r2 = dalloc(8 * (t_ + 1) * nx, reinterpret_cast<void **>(&st.cap_x)))) return r2;
-            if ((r2 = dalloc(8 * t_ * nx, reinterpret_cast<void **>(&st.cap_xn)))) return r2;
-            if ((r2 = dalloc(8 * t_ * nu, reinterpret_cast<void **>(&st.cap_u)))) return r2;
-            HIP_TRY(h, hipMemcpyAsync(st.cap_x, x0 + static_cast<size_t>(capture) * nx, 8 * nx, hipMemcpyHostToDevice, h->stream));
+            a.piece(&st.cap_x, 8 * (t_ + 1) * nx);
+            a.piece(&st.cap_xn, 8 * t_ * nx);
+            a.piece(&st.cap_u, 8 * t_ * nu);
             st.cap_index = capture;
         }
+        HIP_TRY(h, a.carve(h->stream));
+        if (want_cap) HIP_TRY(h, hipMemcpyAsync(st.cap_x, x0 + static_cast<size_t>(capture) * nx, 8 * nx, hipMemcpyHostToDevice, h->stream));
         // per step: the solve launch over all trajectories (x_k = the state, in place), then the step kernel
         for (int t = 0; t < T; ++t) {
-            if ((r2 = enqueue(h, B, st.x, h->reg_zero, nullptr, h->d_u, h->d_x0, nullptr, nullptr, h->d_st, h->d_it))) return r2;
+            if (const int r2 = enqueue(h, B, st.x, h->reg_zero.as<double>(), nullptr, h->d_u, h->d_x0, nullptr, nullptr, h->d_st, h->d_it)) return r2;
             HIP_TRY(h, tmpc::launch_reg_step(m, st, t, T, B, h->d_u, h->d_x0, h->d_st, h->d_it, h->stream));
         }
         if (cost) HIP_TRY(h, hipMemcpyAsync(cost, st.cost, 8 * b, hipMemcpyDeviceToHost, h->stream));
@@ -1596,6 +1442,12 @@ int lp_prepare(int32_t d, int32_t nr, const double *H, const double *hv, LpHost 
     return TMPC_OK;
 }
 
+// device memory of tmpc_lp_batch: one arena per host thread (the Gilbert-Tan recursion makes hundreds of small calls; ten
+// hipMalloc / hipFree pairs each cost more than the kernel), reallocated when the thread's device changes.  Lives until the
+// process ends.
+thread_local Arena g_lp_arena;
+thread_local int g_lp_device = -1;
+
 constexpr int LP_MAX_ITER = 80;
 constexpr double LP_TOL = 1e-8;
 }  // namespace
@@ -1642,21 +1494,23 @@ int tmpc_lp_batch(int device, int32_t d, int32_t nr, const double *H, const doub
     const int nblocks = static_cast<int>(std::min<int64_t>(want, 2 * static_cast<int64_t>(n_cu)));
     const size_t b = static_cast<size_t>(B), dd = static_cast<size_t>(d);
     const size_t nws = static_cast<size_t>(nblocks) * wpb * tmpc::lp_workspace_arrays() * nrp;
-    const size_t need = lp_round(Ht.size() * 8) + 2 * lp_round(static_cast<size_t>(nrp) * 8) + 2 * lp_round(b * dd * 8) + lp_round(nws * 8) +
-                        lp_round(b * 8) + 3 * lp_round(b * 4) + 512;
-    LpArena &ar = g_lp_arena;
-    LP_TRY(ar.reserve(device, need));
-    double *dHt = ar.take<double>(Ht.size()), *dh = ar.take<double>(nrp), *drs = ar.take<double>(nrp);
-    double *dC = ar.take<double>(b * dd), *dws = ar.take<double>(nws), *dval = ar.take<double>(b);
-    double *dx = x ? ar.take<double>(b * dd) : nullptr;
-    int32_t *dst = ar.take<int32_t>(b), *dit = ar.take<int32_t>(b), *drel = relax ? ar.take<int32_t>(b) : nullptr;
-    unsigned long long *dnext = ar.take<unsigned long long>(1);
-    LP_TRY(hipMemset(dnext, 0, sizeof(unsigned long long)));
-    if (relax) LP_TRY(hipMemcpy(drel, relax, b * sizeof(int32_t), hipMemcpyHostToDevice));
-    LP_TRY(hipMemcpy(dHt, Ht.data(), Ht.size() * sizeof(double), hipMemcpyHostToDevice));
-    LP_TRY(hipMemcpy(dh, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
-    LP_TRY(hipMemcpy(drs, rs.data(), rs.size() * sizeof(double), hipMemcpyHostToDevice));
-    LP_TRY(hipMemcpy(dC, C, b * dd * sizeof(double), hipMemcpyHostToDevice));
+    if (device != g_lp_device) { g_lp_arena.release(); g_lp_device = device; }
+    double *dHt, *dh, *drs, *dC, *dws, *dval, *dx = nullptr;
+    int32_t *dst, *dit, *drel = nullptr;
+    unsigned long long *dnext;
+    Arena &ar = g_lp_arena;
+    ar.piece(&dHt, Ht.size() * sizeof(double), Ht.data());
+    ar.piece(&dh, hs.size() * sizeof(double), hs.data());
+    ar.piece(&drs, rs.size() * sizeof(double), rs.data());
+    ar.piece(&dC, b * dd * sizeof(double), C);
+    ar.piece(&dws, nws * sizeof(double));
+    ar.piece(&dval, b * sizeof(double));
+    if (x) ar.piece(&dx, b * dd * sizeof(double));
+    ar.piece(&dst, b * sizeof(int32_t));
+    ar.piece(&dit, b * sizeof(int32_t));
+    if (relax) ar.piece(&drel, b * sizeof(int32_t), relax);
+    ar.piece(&dnext, sizeof(unsigned long long), nullptr, 0);
+    LP_TRY(ar.carve(nullptr));
     tmpc::LpDevice lp{};
     lp.d = d; lp.nr = nr; lp.nrp = nrp; lp.max_iter = LP_MAX_ITER;
     lp.tol = LP_TOL; lp.relax_by = relax_by; lp.hm = hm;
