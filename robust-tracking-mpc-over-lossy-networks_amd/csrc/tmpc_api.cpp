@@ -612,26 +612,21 @@ int prepare_wave_scratch(tmpc_handle *h, int64_t B, int nvar) {
     return TMPC_OK;
 }
 
-int enqueue(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, double *u_nom,
-            double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, int32_t *const *ws = nullptr,
-            bool variants_valid = false) {
+int enqueue(tmpc_handle *h, const tmpc::BatchIO &io, int32_t *const *ws = nullptr, bool variants_valid = false) {
     { const int rce = begin_timed_launch(h); if (rce) return rce; }
-    if (variant != nullptr && !variants_valid)      // (the closed loop's selector is its own gamma flags: always 0 or 1)
-        HIP_TRY(h, tmpc::launch_mark_invalid_variants(variant, h->nvariants, B, h->nx, h->nu, h->N, u_nom, x_nom0, xu_ss, x_nom, status,
-                                                      iters, h->stream));
-    const int nvar = variant != nullptr ? h->nvariants : 1;        // (no per-instance selector: everything is variant 0)
-    { const int rcs = prepare_wave_scratch(h, B, nvar); if (rcs) return rcs; }
+    if (io.variant != nullptr && !variants_valid)      // (the closed loop's selector is its own gamma flags: always 0 or 1)
+        HIP_TRY(h, tmpc::launch_mark_invalid_variants(io, h->nvariants, h->nx, h->nu, h->N, h->stream));
+    const int nvar = io.variant != nullptr ? h->nvariants : 1;        // (no per-instance selector: everything is variant 0)
+    { const int rcs = prepare_wave_scratch(h, io.B, nvar); if (rcs) return rcs; }
     for (int k = 0; k < nvar; ++k) {
         Variant &v = h->v[k];
         if (use_block(h, v)) {
             int rcw = ensure_block_ws(h);
             if (rcw) return rcw;
-            HIP_TRY(h, tmpc::launch_block(v.db, v.bq, v.bargs, v.tiles, h->blk_ws.as<double>(), h->blk_blocks, k, B, x_k, ref, variant, u_nom,
-                                          x_nom0, xu_ss, x_nom, status, iters, &h->wc, h->stream));
+            HIP_TRY(h, tmpc::launch_block(v.db, v.bargs, v.tiles, h->blk_ws.as<double>(), h->blk_blocks, k, io, &h->wc, h->stream));
             continue;
         }
-        HIP_TRY(h, tmpc::launch_solve(v.d, v.shape, k, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status,
-                                      iters, ws ? ws[k] : nullptr, ws ? ws[k] : nullptr, &h->wc, h->n_cu, h->stream));
+        HIP_TRY(h, tmpc::launch_solve(v.d, v.shape, k, io, ws ? ws[k] : nullptr, ws ? ws[k] : nullptr, &h->wc, h->n_cu, h->stream));
     }
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     h->timed = true;
@@ -830,7 +825,7 @@ int tmpc_solve_batch_device(tmpc_handle *h, int64_t B, const double *x_k, const 
         if (rz) return rz;
         ref = h->reg_zero.as<double>();
     }
-    return enqueue(h, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters);
+    return enqueue(h, {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters});
 }
 
 int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
@@ -848,8 +843,8 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double 
         {h->off_st, status, b * sizeof(int32_t)}, {h->off_it, iters, b * sizeof(int32_t)}, {h->off_xn, x_nom, b * (N + 1) * nx * sizeof(double)}};
     char *const dev_in = h->stage_dev.p, *const dev_out = dev_in + h->stage_in_bytes;
     auto launch = [&]() {
-        return enqueue(h, B, h->d_x, h->regulator ? h->reg_zero.as<double>() : h->d_r, variant ? h->d_var : nullptr, h->d_u, h->d_x0,
-                       h->d_ss, x_nom ? h->d_xn : nullptr, h->d_st, h->d_it);
+        return enqueue(h, {B, h->d_x, h->regulator ? h->reg_zero.as<double>() : h->d_r, variant ? h->d_var : nullptr, h->d_u, h->d_x0,
+                           h->d_ss, x_nom ? h->d_xn : nullptr, h->d_st, h->d_it});
     };
     if (h->stage_pin != nullptr) {
         // through the pinned mirror: one DMA in, one out, each up to the last array given
@@ -919,12 +914,7 @@ int tmpc_debug_dump_block_layout(const tmpc_handle *h, int variant, const char *
 const char *tmpc_kernel_name(const tmpc_handle *h, int variant) {
     if (!h || variant < 0 || variant >= h->nvariants) return "";
     const Variant &v = h->v[variant];
-    if (use_block(h, v)) {
-        static const char *names[] = {"", "tmpc::solve_block_kernel<1>", "tmpc::solve_block_kernel<2>", "", "tmpc::solve_block_kernel<4>",
-                                      "", "", "", "tmpc::solve_block_kernel<8>"};
-        return (v.tiles >= 0 && v.tiles <= 8) ? names[v.tiles] : "";
-    }
-    return tmpc::kernel_name(v.shape);
+    return use_block(h, v) ? tmpc::block_kernel_name(v.tiles) : tmpc::kernel_name(v.shape);
 }
 
 int tmpc_mc_set_actuator(tmpc_handle *h, int kind) {
@@ -1174,8 +1164,8 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
             // (round 3: mc_pre, the variant check, the solve, mc_post, mc_tube).  With injected packets nothing is solved.
             for (int t = 0; t < T; ++t) {
                 if (!rp) {
-                    const int r2 = enqueue(h, B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st,
-                                           h->d_it, ws, true);
+                    const int r2 = enqueue(h, {B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it},
+                                           ws, true);
                     if (r2) return r2;
                     st.ticks = h->want_ticks ? h->ticks.as<long long>() : nullptr;       // (allocated by the first enqueue)
                 }
@@ -1285,7 +1275,7 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
         if (want_cap) HIP_TRY(h, hipMemcpyAsync(st.cap_x, x0 + static_cast<size_t>(capture) * nx, 8 * nx, hipMemcpyHostToDevice, h->stream));
         // per step: the solve launch over all trajectories (x_k = the state, in place), then the step kernel
         for (int t = 0; t < T; ++t) {
-            if (const int r2 = enqueue(h, B, st.x, h->reg_zero.as<double>(), nullptr, h->d_u, h->d_x0, nullptr, nullptr, h->d_st, h->d_it)) return r2;
+            if (const int r2 = enqueue(h, {B, st.x, h->reg_zero.as<double>(), nullptr, h->d_u, h->d_x0, nullptr, nullptr, h->d_st, h->d_it})) return r2;
             HIP_TRY(h, tmpc::launch_reg_step(m, st, t, T, B, h->d_u, h->d_x0, h->d_st, h->d_it, h->stream));
         }
         if (cost) HIP_TRY(h, hipMemcpyAsync(cost, st.cost, 8 * b, hipMemcpyDeviceToHost, h->stream));

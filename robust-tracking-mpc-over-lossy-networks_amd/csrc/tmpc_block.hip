@@ -33,12 +33,14 @@
 #include <hip/hip_runtime.h>
 #endif
 
-#include <atomic>
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <string>
 #include <type_traits>
 
 #include "tmpc_device.hpp"
+#include "tmpc_launch.hpp"
 #include "tmpc_wave.hpp"
 
 namespace tmpc {
@@ -1426,71 +1428,36 @@ __global__ __launch_bounds__(BShape<T>::BT, BShape<T>::OCC) void solve_block_ker
 #undef rr_
 #undef inW_
 
-#ifdef TMPC_HOST_SIM
-unsigned long sim_rendezvous_total = 0;
-// tests/wavesim: one workgroup on the host execution model takes the whole batch (grid of one)
-template <int T>
-hipError_t launch_block_t(const DeviceQP &qp, const BlockQP &bq, const BlockArgs *dargs, double *ws, int ws_blocks, int variant_id, int64_t B,
-                          const double *x_k, const double *ref, const uint8_t *variant, double *u_nom, double *x_nom0,
-                          double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, WorkCounter *wc, hipStream_t stream) {
-    constexpr size_t lds = sizeof(double) * BShape<T>::TOTAL;
-    static_assert(lds <= 160 * 1024, "block shape does not fit the 160 KiB LDS of a CU");
-    (void)ws_blocks; (void)stream; (void)dargs; (void)wc;
-    unsigned long long counter = 0, *next_item = &counter;
-    const BlockArgs host_args{qp, bq};
-    sim::Dim3 bi, gd;
-    bi.x = bi.y = bi.z = 0;
-    sim_rendezvous_total += sim::run_block(BShape<T>::BT, lds, bi, gd, [&]() {
-        solve_block_kernel<T>(BlockLaunch{&host_args, qp.ticks, qp.dbg, ws, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, next_item});
-    });
-    return hipSuccess;
-}
-template <int T>
-int block_occupancy_t() { return 1; }
-#else
-template <int T>
-hipError_t launch_block_t(const DeviceQP &qp, const BlockQP &bq, const BlockArgs *dargs, double *ws, int ws_blocks, int variant_id, int64_t B,
-                          const double *x_k, const double *ref, const uint8_t *variant, double *u_nom, double *x_nom0,
-                          double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, WorkCounter *wc, hipStream_t stream) {
-    constexpr size_t lds = sizeof(double) * BShape<T>::TOTAL;
-    static_assert(lds <= 160 * 1024, "block shape does not fit the 160 KiB LDS of a CU");
-    static std::atomic<bool> attr_set[64] = {};       // (the size is a compile-time constant here: setting it twice is harmless)
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    if (dev_id < 0 || dev_id >= 64 || !attr_set[dev_id].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_block_kernel<T>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (dev_id >= 0 && dev_id < 64) attr_set[dev_id].store(true, std::memory_order_release);
+// f(integral_constant<int, tiles>) for the compiled tile counts; `miss` otherwise
+template <class Ret, class F>
+Ret with_tiles(int tiles, Ret miss, F &&f) {
+    switch (tiles) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
     }
-    if (dargs == nullptr || wc == nullptr || wc->ring == nullptr) return hipErrorInvalidValue;
-    (void)bq;
-    // a fresh (zero) word of the counter ring per launch; the ring is cleared in one piece when it has gone round (tmpc_device.hpp)
-    if (wc->pos >= wc->size) {
-        hipError_t e0 = hipMemsetAsync(wc->ring, 0, sizeof(unsigned long long) * wc->size, stream);
-        if (e0 != hipSuccess) return e0;
-        wc->pos = 0;
-    }
-    unsigned long long *const next_item = wc->ring + wc->pos;
-    ++wc->pos;
-    int64_t blocks = B < ws_blocks ? B : ws_blocks;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((solve_block_kernel<T>), dim3(static_cast<unsigned>(blocks)), dim3(BShape<T>::BT), lds, stream,
-                       BlockLaunch{dargs, qp.ticks, qp.dbg, ws, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, next_item});
-    return hipGetLastError();
+    return miss;
 }
 
 template <int T>
-int block_occupancy_t() {
-    constexpr size_t lds = sizeof(double) * BShape<T>::TOTAL;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_block_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(lds));
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_block_kernel<T>, BShape<T>::BT, lds) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+constexpr size_t block_lds() {
+    static_assert(sizeof(double) * BShape<T>::TOTAL <= 160 * 1024, "block shape does not fit the 160 KiB LDS of a CU");
+    return sizeof(double) * BShape<T>::TOTAL;
 }
 
-#endif
+// at most ws_blocks workgroups (each owns a slice of the workspace), every one drawing instances until the batch is done
+template <int T>
+hipError_t launch_block_t(const DeviceQP &qp, const BlockArgs *args, double *ws, int ws_blocks, int variant_id, const BatchIO &io,
+                          WorkCounter *wc, hipStream_t stream) {
+    if (args == nullptr) return hipErrorInvalidValue;
+    unsigned long long *next_item = nullptr;
+    if (const hipError_t e = next_word(wc, stream, &next_item); e != hipSuccess) return e;
+    const unsigned blocks = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(io.B, ws_blocks)));
+    return launch_grid(solve_block_kernel<T>, blocks, BShape<T>::BT, block_lds<T>(), stream,
+                       BlockLaunch{args, qp.ticks, qp.dbg, ws, variant_id, io.B, io.x_k, io.ref, io.variant, io.u_nom, io.x_nom0, io.xu_ss, io.x_nom,
+                                   io.status, io.iters, next_item});
+}
 
 }  // namespace
 
@@ -1503,40 +1470,36 @@ int block_tiles(int nv) {
 }
 
 int block_workspace_rows() { return WS_COUNT; }
-#ifdef TMPC_HOST_SIM
-unsigned long sim_rendezvous_count() { return sim_rendezvous_total; }
-#endif
 
 size_t block_lds_bytes(int tiles) {
-    switch (tiles) {
-        case 1: return sizeof(double) * BShape<1>::TOTAL;
-        case 2: return sizeof(double) * BShape<2>::TOTAL;
-        case 4: return sizeof(double) * BShape<4>::TOTAL;
-        case 8: return sizeof(double) * BShape<8>::TOTAL;
-    }
-    return 0;
+    return with_tiles(tiles, size_t{0}, [](auto t) { return block_lds<decltype(t)::value>(); });
 }
 
+const char *block_kernel_name(int tiles) {
+    return with_tiles(tiles, "", [](auto t) -> const char * {
+        static const std::string n = "tmpc::solve_block_kernel<" + std::to_string(decltype(t)::value) + ">";
+        return n.c_str();
+    });
+}
+
+#ifndef TMPC_HOST_SIM      // (asked by tmpc_api.cpp alone)
 int block_occupancy(int tiles) {
-    switch (tiles) {
-        case 1: return block_occupancy_t<1>();
-        case 2: return block_occupancy_t<2>();
-        case 4: return block_occupancy_t<4>();
-        case 8: return block_occupancy_t<8>();
-    }
-    return 1;
+    return with_tiles(tiles, 1, [](auto t) {
+        constexpr int T = decltype(t)::value;
+        int nb = 0;
+        if (raise_lds_limit(reinterpret_cast<const void *>(&solve_block_kernel<T>), block_lds<T>()) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_block_kernel<T>, BShape<T>::BT, block_lds<T>()) != hipSuccess || nb < 1)
+            nb = 1;
+        return nb;
+    });
 }
+#endif
 
-hipError_t launch_block(const DeviceQP &qp, const BlockQP &bq, const BlockArgs *dargs, int tiles, double *ws, int ws_blocks, int variant_id, int64_t B,
-                        const double *x_k, const double *ref, const uint8_t *variant, double *u_nom, double *x_nom0,
-                        double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, WorkCounter *wc, hipStream_t stream) {
-    switch (tiles) {
-        case 1: return launch_block_t<1>(qp, bq, dargs, ws, ws_blocks, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, wc, stream);
-        case 2: return launch_block_t<2>(qp, bq, dargs, ws, ws_blocks, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, wc, stream);
-        case 4: return launch_block_t<4>(qp, bq, dargs, ws, ws_blocks, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, wc, stream);
-        case 8: return launch_block_t<8>(qp, bq, dargs, ws, ws_blocks, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, wc, stream);
-    }
-    return hipErrorInvalidValue;
+hipError_t launch_block(const DeviceQP &qp, const BlockArgs *args, int tiles, double *ws, int ws_blocks, int variant_id, const BatchIO &io,
+                        WorkCounter *wc, hipStream_t stream) {
+    return with_tiles(tiles, hipErrorInvalidValue, [&](auto t) {
+        return launch_block_t<decltype(t)::value>(qp, args, ws, ws_blocks, variant_id, io, wc, stream);
+    });
 }
 
 }  // namespace tmpc

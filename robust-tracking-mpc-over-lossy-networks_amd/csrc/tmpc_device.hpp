@@ -116,10 +116,18 @@ struct WorkCounter {
     int size = 0, pos = 0;
 };
 
+// The batch of one solve call, device pointers ([instance]-major, include/tmpc.h: tmpc_solve_batch_device).  nullptr: the
+// optional ones not given (ref of the fused loops, variant: everything is variant 0) or not wanted (x_nom0, xu_ss, x_nom).
+struct BatchIO {
+    int64_t B;
+    const double *x_k, *ref;
+    const uint8_t *variant;
+    double *u_nom, *x_nom0, *xu_ss, *x_nom;
+    int32_t *status, *iters;
+};
+
 // ws_in / ws_out: optional working sets (WS_STRIDE ints per instance), see above
-hipError_t launch_solve(const DeviceQP &qp, const KernelShape &shape, int variant_id, int64_t B,
-                        const double *x_k, const double *ref, const uint8_t *variant, double *u_nom, double *x_nom0,
-                        double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, const int32_t *ws_in, int32_t *ws_out,
+hipError_t launch_solve(const DeviceQP &qp, const KernelShape &shape, int variant_id, const BatchIO &io, const int32_t *ws_in, int32_t *ws_out,
                         WorkCounter *wc, int n_cu, hipStream_t stream);
 
 // Block path: tiles = NVP / 16 in {1, 2, 4, 8} (0: nv > 128, unsupported); workspace = blocks * rows * ncp doubles
@@ -127,10 +135,10 @@ int block_tiles(int nv);
 int block_workspace_rows();
 size_t block_lds_bytes(int tiles);
 int block_occupancy(int tiles);
-// dargs: the device copy of {qp, bq} (unused on the host execution model of tests/wavesim, which reads qp / bq directly)
-hipError_t launch_block(const DeviceQP &qp, const BlockQP &bq, const BlockArgs *dargs, int tiles, double *ws, int ws_blocks, int variant_id, int64_t B,
-                        const double *x_k, const double *ref, const uint8_t *variant, double *u_nom, double *x_nom0,
-                        double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, WorkCounter *wc, hipStream_t stream);
+const char *block_kernel_name(int tiles);
+// qp: the host copy of the variant (its ticks / dbg of this launch); args: {qp, bq} where the kernel reads them, device memory
+hipError_t launch_block(const DeviceQP &qp, const BlockArgs *args, int tiles, double *ws, int ws_blocks, int variant_id, const BatchIO &io,
+                        WorkCounter *wc, hipStream_t stream);
 
 // Device-resident closed loop (tmpc_mc.hip)
 struct McModel {
@@ -169,9 +177,7 @@ struct McState {                         // all [trajectory]-major device arrays
     double *trace_f;                          // [B][T][3 nx + nu]: x_{t+1}, x_hat_{t+1}, nominal state of the plant's packet, u_t; or nullptr
     int32_t *trace_i;                         // [B][T][3]: s_t, Theta_t, q_t (the controller's packet)
 };
-hipError_t launch_mark_invalid_variants(const uint8_t *variant, int nvariants, int64_t B, int nx, int nu, int N, double *u_nom,
-                                        double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters,
-                                        hipStream_t stream);
+hipError_t launch_mark_invalid_variants(const BatchIO &io, int nvariants, int nx, int nu, int N, hipStream_t stream);
 // one launch before the first solve (reference of step 0), then one launch per time step after the solve launch(es)
 hipError_t launch_mc_pre(const McModel &m, const McState &st, int64_t B, double ref_0, hipStream_t stream);
 hipError_t launch_mc_step(const McModel &m, const McState &st, int t, int T, int64_t B, double ref_t, double ref_next, const double *u_nom,

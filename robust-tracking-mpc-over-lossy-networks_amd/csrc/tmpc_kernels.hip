@@ -37,14 +37,15 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include <algorithm>
 #include <cmath>
-#include <mutex>
 #include <cstdint>
 #include <string>
 #include <type_traits>
 #include <utility>
 
 #include "tmpc_device.hpp"
+#include "tmpc_launch.hpp"
 #include "tmpc_wave.hpp"
 #include "tmpc_mc_step.hpp"
 
@@ -65,9 +66,6 @@ using wv::OpMax;
 using wv::OpMin;
 using wv::OpSum;
 
-#ifdef TMPC_HOST_SIM
-unsigned long sim_rendezvous_total = 0;
-#endif
 constexpr int RED_STRIDE = 68;      // 64 lanes + a pad after every 16: conflict-free transposed reads
 constexpr int ZERO_ROWS = 4;        // zero rows behind the staged dense functionals: row `grows` stands for every functional beyond them,
                                     // and the look-ahead of the MFMA pass ends one k-step (four rows) past the last one it multiplies
@@ -1602,94 +1600,6 @@ constexpr int waves_per_block() {
     return kernel_lds_bytes<SH>(4, gr) <= 160 * 1024 ? 4 : (kernel_lds_bytes<SH>(3, gr) <= 160 * 1024 ? 3 : 2);
 }
 
-#ifdef TMPC_HOST_SIM
-// tests/wavesim: one workgroup of WPB waves on the host execution model; the persistent grid is that one workgroup
-template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB, int FUSED = 0>
-hipError_t launch_wpb(const DeviceQP &qp, int variant_id, int64_t B, const double *x_k, const double *ref,
-                      const uint8_t *variant, double *u_nom, double *x_nom0, double *xu_ss, double *x_nom,
-                      int32_t *status, int32_t *iters, const int32_t *ws_in, int32_t *ws_out, WorkCounter *wc, int n_cu,
-                      hipStream_t stream, McArg<FUSED> mc = McArg<FUSED>{}) {
-    using SH = Shape<NV, DP, DS, KC, CP, CS, tile_rows(NV, WPB)>;
-    const size_t lds = kernel_lds_bytes<SH>(WPB, 4 * qp.nks);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    (void)n_cu; (void)stream; (void)wc;
-    unsigned long long next_item = 0;
-    sim::Dim3 bi, gd;
-    bi.x = bi.y = bi.z = 0;                    // workgroup 0 of a grid of one
-    sim_rendezvous_total += sim::run_block(WAVE * WPB, lds, bi, gd, [&]() {
-        if constexpr (FUSED == 1)
-            closed_loop_kernel<NV, DP, DS, KC, CP, CS, WPB>(qp, B, u_nom, x_nom0, xu_ss, status, iters, ws_out, &next_item, mc);
-        else if constexpr (FUSED == 2)
-            closed_loop_step_kernel<NV, DP, DS, KC, CP, CS, WPB>(qp, variant_id, B, variant, u_nom, x_nom0, xu_ss, status, iters, ws_out, &next_item, mc);
-        else
-            solve_kernel<NV, DP, DS, KC, CP, CS, WPB>(qp, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters,
-                                                      ws_in, ws_out, &next_item);
-    });
-    return hipSuccess;
-}
-#else
-template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB, int FUSED = 0>
-hipError_t launch_wpb(const DeviceQP &qp, int variant_id, int64_t B, const double *x_k, const double *ref,
-                      const uint8_t *variant, double *u_nom, double *x_nom0, double *xu_ss, double *x_nom,
-                      int32_t *status, int32_t *iters, const int32_t *ws_in, int32_t *ws_out, WorkCounter *wc, int n_cu,
-                      hipStream_t stream, McArg<FUSED> mc = McArg<FUSED>{}) {
-    using SH = Shape<NV, DP, DS, KC, CP, CS, tile_rows(NV, WPB)>;
-    const size_t lds = kernel_lds_bytes<SH>(WPB, 4 * qp.nks);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;       // (tmpc_api.cpp checks lds_bytes() before it accepts the wave path)
-    static_assert(SH::RS <= 32, "validity mask is one 32-bit word per lane");
-    // > 64 KiB of dynamic LDS needs the opt-in per device and instantiation.  The size depends on the problem (rows of dense
-    // functionals staged), so the attribute is raised whenever a handle asks for more than any before it on this device
-    // (handles may be driven from different host threads: the check and the call are one critical section).
-    {
-        static std::mutex attr_mutex;
-        static size_t attr_lds[64] = {};
-        int dev_id = 0;
-        (void)hipGetDevice(&dev_id);
-        std::lock_guard<std::mutex> guard(attr_mutex);
-        if (dev_id < 0 || dev_id >= 64 || attr_lds[dev_id] < lds) {
-            const void *fn = nullptr;
-            if constexpr (FUSED == 1) fn = reinterpret_cast<const void *>(&closed_loop_kernel<NV, DP, DS, KC, CP, CS, WPB>);
-            else if constexpr (FUSED == 2) fn = reinterpret_cast<const void *>(&closed_loop_step_kernel<NV, DP, DS, KC, CP, CS, WPB>);
-            else fn = reinterpret_cast<const void *>(&solve_kernel<NV, DP, DS, KC, CP, CS, WPB>);
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-            if (e != hipSuccess) return e;
-            if (dev_id >= 0 && dev_id < 64) attr_lds[dev_id] = lds;
-        }
-    }
-    int64_t blocks = B;                                      // (capped at one workgroup per CU below; the first items are dealt wave-major)
-    // one persistent workgroup per CU (the LDS footprint admits no second one): the model is staged once and every wave
-    // fetches its next instance as soon as it is done with the current one (grid-stride over the batch)
-    const int64_t cap = static_cast<int64_t>(n_cu);
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    // every launch gets a fresh (zero) word of the counter ring; the ring is cleared in one piece when it has gone round
-    if (wc->pos >= wc->size) {
-        hipError_t e0 = hipMemsetAsync(wc->ring, 0, sizeof(unsigned long long) * wc->size, stream);
-        if (e0 != hipSuccess) return e0;
-        wc->pos = 0;
-    }
-    if constexpr (FUSED == 1)
-        hipLaunchKernelGGL((closed_loop_kernel<NV, DP, DS, KC, CP, CS, WPB>), dim3(static_cast<unsigned>(blocks)), dim3(WAVE * WPB), lds, stream,
-                           qp, B, u_nom, x_nom0, xu_ss, status, iters, ws_out, wc->ring + wc->pos, mc);
-    else if constexpr (FUSED == 2)
-        hipLaunchKernelGGL((closed_loop_step_kernel<NV, DP, DS, KC, CP, CS, WPB>), dim3(static_cast<unsigned>(blocks)), dim3(WAVE * WPB), lds, stream,
-                           qp, variant_id, B, variant, u_nom, x_nom0, xu_ss, status, iters, ws_out, wc->ring + wc->pos, mc);
-    else
-        hipLaunchKernelGGL((solve_kernel<NV, DP, DS, KC, CP, CS, WPB>), dim3(static_cast<unsigned>(blocks)), dim3(WAVE * WPB), lds, stream,
-                           qp, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, ws_in, ws_out,
-                           wc->ring + wc->pos);
-    ++wc->pos;
-    return hipGetLastError();
-}
-
-#endif
-
-}  // namespace
-
-#ifdef TMPC_HOST_SIM
-unsigned long sim_rendezvous_count() { return sim_rendezvous_total; }
-#endif
-
 // Compiled shapes (NVP, DP, DS, KC, CP, CS): padded variables; 64-functional slots of dense paired / dense single rows; width
 // of the factored block and its paired / single slots.  Dense-single-only shapes cover the small and the irregular problems
 // (config 1); the paired + factored shapes cover the cartpole: base problem at N <= 11 (bench) and N <= 23 (the reference's
@@ -1716,85 +1626,112 @@ unsigned long sim_rendezvous_count() { return sim_rendezvous_total; }
     X(11, 1, 0, 5, 4, 0) X(12, 1, 0, 5, 4, 0) X(22, 2, 0, 5, 4, 0) X(24, 2, 0, 5, 4, 0) X(15, 1, 0, 4, 7, 0) X(16, 1, 0, 4, 7, 0) X(26, 2, 0, 4, 7, 0)
 #endif
 
+// A compiled shape as a type: its waves per workgroup and the Shape the kernels derive from both
+template <int NV, int... R>
+struct ShapeTag {
+    static constexpr int WPB = waves_per_block<NV, R...>();
+    using SH = Shape<NV, R..., tile_rows(NV, WPB)>;
+};
+
+// f(ShapeTag) of the compiled shape `s` names; `miss` if it names none
+template <class Ret, class F>
+Ret with_shape(const KernelShape &s, Ret miss, F &&f) {
+#define TMPC_CASE(A, B_, C, D, E, F_) \
+    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F_) return f(ShapeTag<A, B_, C, D, E, F_>{});
+    TMPC_SHAPES(TMPC_CASE)
+#undef TMPC_CASE
+    return miss;
+}
+
+// The (shape, FUSED) pairs a binary instantiates.  The library: every shape, FUSED = 0 / 1 / 2 in the translation unit
+// tmpc_kernels.hip / tmpc_fused.hip / tmpc_fused_step.hip (which defines that launch function alone, below).  tests/wavesim,
+// one translation unit per binary: the binary of the extended controller holds closed_loop_step_kernel only, the others
+// everything else -- the fused loop on the bench shape alone under TMPC_SIM_SHAPES (one instantiation less per binary).
+template <class T, int FUSED>
+constexpr bool instantiated() {
+#if !defined(TMPC_HOST_SIM)
+    return true;
+#elif defined(TMPC_SIM_SHAPES_EXT)
+    return FUSED == 2;
+#elif defined(TMPC_SIM_SHAPES)
+    return FUSED == 0 || (FUSED == 1 && std::is_same_v<T, ShapeTag<11, 1, 0, 5, 4, 0>>);
+#else
+    return FUSED != 2;
+#endif
+}
+
+// One persistent workgroup per CU (the LDS footprint admits no second one): the model is staged once and every wave fetches
+// its next work item as soon as it is done with the current one (the first items are dealt wave-major).
+template <int FUSED, int... S>
+hipError_t launch_wpb(ShapeTag<S...>, const DeviceQP &qp, int variant_id, const BatchIO &io, const int32_t *ws_in, int32_t *ws_out,
+                      WorkCounter *wc, int n_cu, hipStream_t stream, McArg<FUSED> mc) {
+    using SH = typename ShapeTag<S...>::SH;
+    constexpr int WPB = ShapeTag<S...>::WPB;
+    static_assert(SH::RS <= 32, "validity mask is one 32-bit word per lane");
+    const size_t lds = kernel_lds_bytes<SH>(WPB, 4 * qp.nks);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;       // (tmpc_api.cpp asks lds_bytes() before a variant takes the wave path)
+    const unsigned blocks = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(io.B, n_cu)));
+    unsigned long long *next_item = nullptr;
+    if (const hipError_t e = next_word(wc, stream, &next_item); e != hipSuccess) return e;
+    if constexpr (FUSED == 1)
+        return launch_grid(closed_loop_kernel<S..., WPB>, blocks, WAVE * WPB, lds, stream, qp, io.B, io.u_nom, io.x_nom0, io.xu_ss, io.status,
+                           io.iters, ws_out, next_item, mc);
+    else if constexpr (FUSED == 2)
+        return launch_grid(closed_loop_step_kernel<S..., WPB>, blocks, WAVE * WPB, lds, stream, qp, variant_id, io.B, io.variant, io.u_nom,
+                           io.x_nom0, io.xu_ss, io.status, io.iters, ws_out, next_item, mc);
+    else
+        return launch_grid(solve_kernel<S..., WPB>, blocks, WAVE * WPB, lds, stream, qp, variant_id, io.B, io.x_k, io.ref, io.variant, io.u_nom,
+                           io.x_nom0, io.xu_ss, io.x_nom, io.status, io.iters, ws_in, ws_out, next_item);
+}
+
+template <int FUSED>
+hipError_t launch_shape(const DeviceQP &qp, const KernelShape &s, int variant_id, const BatchIO &io, const int32_t *ws_in, int32_t *ws_out,
+                        WorkCounter *wc, int n_cu, hipStream_t stream, McArg<FUSED> mc = McArg<FUSED>{}) {
+    return with_shape(s, hipErrorInvalidValue, [&](auto tag) -> hipError_t {
+        if constexpr (instantiated<decltype(tag), FUSED>()) return launch_wpb<FUSED>(tag, qp, variant_id, io, ws_in, ws_out, wc, n_cu, stream, mc);
+        else return hipErrorInvalidValue;
+    });
+}
+
+}  // namespace
+
 #if defined(TMPC_HOST_SIM) || (defined(TMPC_FUSED_TU) && TMPC_FUSED_TU == 2)
-// tmpc_fused_step.hip: the FUSED = 2 instantiations and nothing else
 hipError_t launch_solve_mc_step(const DeviceQP &qp, const KernelShape &s, int variant_id, int64_t B, const uint8_t *variant, double *u_nom,
                                 double *x_nom0, double *xu_ss, int32_t *status, int32_t *iters, int32_t *ws, const McFused *mc, int t,
                                 uint8_t *gamma_out, WorkCounter *wc, int n_cu, hipStream_t stream) {
-#if defined(TMPC_HOST_SIM) && !defined(TMPC_SIM_SHAPES_EXT)
-    (void)qp; (void)s; (void)variant_id; (void)B; (void)variant; (void)u_nom; (void)x_nom0; (void)xu_ss; (void)status; (void)iters; (void)ws; (void)mc; (void)t;
-    (void)gamma_out; (void)wc; (void)n_cu; (void)stream;
-    return hipErrorInvalidValue;       // (tests/wavesim: only the binary of the extended controller instantiates closed_loop_step_kernel)
-#else
-    const McStepArg arg{mc, t, gamma_out};
-#define TMPC_CASE(A, B_, C, D, E, F)                                                                                      \
-    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F)                                    \
-        return launch_wpb<A, B_, C, D, E, F, waves_per_block<A, B_, C, D, E, F>(), 2>(qp, variant_id, B, nullptr, nullptr, variant, u_nom, x_nom0, \
-                                                                                      xu_ss, nullptr, status, iters, ws, ws, wc, n_cu, stream, arg);
-    TMPC_SHAPES(TMPC_CASE)
-#undef TMPC_CASE
-    return hipErrorInvalidValue;
-#endif
+    return launch_shape<2>(qp, s, variant_id, BatchIO{B, nullptr, nullptr, variant, u_nom, x_nom0, xu_ss, nullptr, status, iters}, ws, ws, wc, n_cu,
+                           stream, McStepArg{mc, t, gamma_out});
 }
 #endif
 #if defined(TMPC_HOST_SIM) || (defined(TMPC_FUSED_TU) && TMPC_FUSED_TU == 1)
-// tmpc_fused.hip: this translation unit holds the FUSED = 1 instantiations and nothing else (compiled next to the main one)
 hipError_t launch_solve_mc(const DeviceQP &qp, const KernelShape &s, int64_t B, double *u_nom, double *x_nom0, double *xu_ss,
                            int32_t *status, int32_t *iters, int32_t *ws, const McFused *mc, WorkCounter *wc, int n_cu, hipStream_t stream) {
-#if defined(TMPC_HOST_SIM) && defined(TMPC_SIM_SHAPES_EXT)
-    return hipErrorInvalidValue;       // (tests/wavesim: the binary of the extended controller instantiates closed_loop_step_kernel only)
-#else
-#define TMPC_CASE(A, B_, C, D, E, F)                                                                                      \
-    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F)                                    \
-        return launch_wpb<A, B_, C, D, E, F, waves_per_block<A, B_, C, D, E, F>(), 1>(qp, 0, B, nullptr, nullptr, nullptr, u_nom, x_nom0, \
-                                                                                         xu_ss, nullptr, status, iters, ws, ws, wc, n_cu, stream, mc);
-#if defined(TMPC_HOST_SIM) && defined(TMPC_SIM_SHAPES)
-    TMPC_CASE(11, 1, 0, 5, 4, 0)       // (tests/wavesim: the fused loop is run on the bench shape; one instantiation less per binary)
-#else
-    TMPC_SHAPES(TMPC_CASE)
-#endif
-#undef TMPC_CASE
-    return hipErrorInvalidValue;
-#endif
+    return launch_shape<1>(qp, s, 0, BatchIO{B, nullptr, nullptr, nullptr, u_nom, x_nom0, xu_ss, nullptr, status, iters}, ws, ws, wc, n_cu, stream, mc);
 }
 #endif
 #if defined(TMPC_HOST_SIM) || !defined(TMPC_FUSED_TU)
+hipError_t launch_solve(const DeviceQP &qp, const KernelShape &s, int variant_id, const BatchIO &io, const int32_t *ws_in, int32_t *ws_out,
+                        WorkCounter *wc, int n_cu, hipStream_t stream) {
+    return launch_shape<0>(qp, s, variant_id, io, ws_in, ws_out, wc, n_cu, stream);
+}
+
 int resident_waves(const KernelShape &s, int n_cu) {
-#define TMPC_RW(A, B_, C, D, E, F) \
-    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F) return n_cu * waves_per_block<A, B_, C, D, E, F>();
-    TMPC_SHAPES(TMPC_RW)
-#undef TMPC_RW
-    return 0;
+    return with_shape(s, 0, [&](auto tag) { return n_cu * decltype(tag)::WPB; });
 }
 
 size_t lds_bytes(const KernelShape &s, int grows) {
-#define TMPC_LDS(A, B_, C, D, E, F) \
-    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F) { \
-        constexpr int wpb = waves_per_block<A, B_, C, D, E, F>(); \
-        return kernel_lds_bytes<Shape<A, B_, C, D, E, F, tile_rows(A, wpb)>>(wpb, grows); }
-    TMPC_SHAPES(TMPC_LDS)
-#undef TMPC_LDS
-    return 0;
+    return with_shape(s, size_t{0}, [&](auto tag) { return kernel_lds_bytes<typename decltype(tag)::SH>(decltype(tag)::WPB, grows); });
 }
 
 bool parks_in_lds(const KernelShape &s) {
-#define TMPC_PARK(A, B_, C, D, E, F) \
-    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F) \
-        return WaveLds<Shape<A, B_, C, D, E, F, tile_rows(A, waves_per_block<A, B_, C, D, E, F>())>>::PARK_LDS;
-    TMPC_SHAPES(TMPC_PARK)
-#undef TMPC_PARK
-    return false;
+    return with_shape(s, false, [](auto tag) { return WaveLds<typename decltype(tag)::SH>::PARK_LDS; });
 }
 
 const char *kernel_name(const KernelShape &s) {
-#define TMPC_NAME(A, B_, C, D, E, F) \
-    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F) { \
-        static const std::string n = std::string("tmpc::solve_kernel<") + #A "," #B_ "," #C "," #D "," #E "," #F "," + \
-                                     std::to_string(waves_per_block<A, B_, C, D, E, F>()) + ">"; \
-        return n.c_str(); }
-    TMPC_SHAPES(TMPC_NAME)
-#undef TMPC_NAME
-    return "";
+    return with_shape(s, "", []<int... S>(ShapeTag<S...>) -> const char * {
+        static const std::string n = "tmpc::solve_kernel<" + ((std::to_string(S) + ",") + ...) + std::to_string(ShapeTag<S...>::WPB) + ">";
+        return n.c_str();
+    });
 }
 
 bool pick_config(int nv, int nd2, int nd1, int kc, int nc2, int nc1, KernelShape *shape) {
@@ -1815,23 +1752,6 @@ bool pick_config(int nv, int nd2, int nd1, int kc, int nc2, int nc1, KernelShape
         }
     }
     return best >= 0;
-}
-
-hipError_t launch_solve(const DeviceQP &qp, const KernelShape &s, int variant_id, int64_t B,
-                        const double *x_k, const double *ref, const uint8_t *variant, double *u_nom, double *x_nom0,
-                        double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, const int32_t *ws_in, int32_t *ws_out,
-                        WorkCounter *wc, int n_cu, hipStream_t stream) {
-#if defined(TMPC_HOST_SIM) && defined(TMPC_SIM_SHAPES_EXT)
-    return hipErrorInvalidValue;
-#else
-#define TMPC_CASE(A, B_, C, D, E, F)                                                                                      \
-    if (s.nvp == A && s.dp == B_ && s.ds == C && s.kcp == D && s.cp == E && s.cs == F)                                    \
-        return launch_wpb<A, B_, C, D, E, F, waves_per_block<A, B_, C, D, E, F>()>(qp, variant_id, B, x_k, ref, variant, u_nom, x_nom0, \
-                                                                                   xu_ss, x_nom, status, iters, ws_in, ws_out, wc, n_cu, stream);
-    TMPC_SHAPES(TMPC_CASE)
-#undef TMPC_CASE
-    return hipErrorInvalidValue;
-#endif
 }
 
 #endif      // main translation unit

@@ -40,6 +40,7 @@
 #include <utility>
 
 #include "tmpc_device.hpp"
+#include "tmpc_launch.hpp"
 #include "tmpc_wave.hpp"
 
 namespace tmpc {
@@ -847,23 +848,7 @@ template <int D, bool STAGED>
 hipError_t launch_lp_ds(const LpDevice &p, int64_t B, int nblocks, const double *C, const int32_t *relax, double *ws, double *val,
                         double *xout, int32_t *status, int32_t *iters, hipStream_t stream) {
     const size_t lds = (static_cast<size_t>(LpLds<D>::TOTAL) * LP_WPB + (STAGED ? static_cast<size_t>(D) * p.nrp : 0)) * sizeof(double);
-#ifdef TMPC_HOST_SIM
-    // tests/wavesim: one workgroup (four waves, four LPs in flight) on the host execution model takes the whole batch
-    (void)nblocks; (void)stream;
-    sim::Dim3 bi, gd;
-    bi.x = bi.y = bi.z = 0;
-    unsigned long long counter = 0;
-    LpDevice ps = p;
-    ps.next_item = &counter;
-    sim::run_block(WAVE * LP_WPB, lds, bi, gd, [&]() { lp_kernel<D, STAGED>(ps, B, C, relax, ws, val, xout, status, iters); });
-    return hipSuccess;
-#else
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lp_kernel<D, STAGED>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((lp_kernel<D, STAGED>), dim3(nblocks), dim3(WAVE * LP_WPB), lds, stream, p, B, C, relax, ws, val, xout, status, iters);
-    return hipGetLastError();
-#endif
+    return launch_grid(lp_kernel<D, STAGED>, static_cast<unsigned>(nblocks), WAVE * LP_WPB, lds, stream, p, B, C, relax, ws, val, xout, status, iters);
 }
 
 template <int D>

@@ -68,13 +68,11 @@ __global__ void mark_invalid_variants_kernel(const uint8_t *__restrict__ variant
     status[b] = TMPC_STATUS_NUMERICAL;
     iters[b] = 0;
 }
-hipError_t launch_mark_invalid_variants(const uint8_t *variant, int nvariants, int64_t B, int nx, int nu, int N, double *u_nom,
-                                        double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters,
-                                        hipStream_t stream) {
+hipError_t launch_mark_invalid_variants(const BatchIO &io, int nvariants, int nx, int nu, int N, hipStream_t stream) {
     const int threads = 256;
-    const unsigned blocks = static_cast<unsigned>((B + threads - 1) / threads);
-    hipLaunchKernelGGL(mark_invalid_variants_kernel, dim3(blocks), dim3(threads), 0, stream, variant, nvariants, B, N * nu, nx, nx + nu,
-                       (N + 1) * nx, u_nom, x_nom0, xu_ss, x_nom, status, iters);
+    const unsigned blocks = static_cast<unsigned>((io.B + threads - 1) / threads);
+    hipLaunchKernelGGL(mark_invalid_variants_kernel, dim3(blocks), dim3(threads), 0, stream, io.variant, nvariants, io.B, N * nu, nx, nx + nu,
+                       (N + 1) * nx, io.u_nom, io.x_nom0, io.xu_ss, io.x_nom, io.status, io.iters);
     return hipGetLastError();
 }
 

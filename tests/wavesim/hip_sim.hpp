@@ -352,3 +352,4 @@ inline int max(int a, int b) { return a > b ? a : b; }
 typedef int hipError_t;
 typedef void *hipStream_t;
 constexpr hipError_t hipSuccess = 0, hipErrorInvalidValue = 1;
+inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) { std::memset(p, v, n); return hipSuccess; }

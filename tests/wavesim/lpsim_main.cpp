@@ -46,6 +46,8 @@ int main(int argc, char **argv) {
     lp.d = d; lp.nr = nr; lp.nrp = nrp; lp.max_iter = hd[4];
     lp.tol = sc[0]; lp.relax_by = sc[1]; lp.hm = sc[2];
     lp.Ht = Ht.data(); lp.h = h.data(); lp.rscale = rs.data();
+    unsigned long long counter = 0;               // the launch's work counter: a host word
+    lp.next_item = &counter;
     // the per-wave workspaces: uninitialised on purpose
     std::unique_ptr<double[]> ws(new double[static_cast<size_t>(tmpc::lp_waves_per_block()) * tmpc::lp_workspace_arrays() * nrp]);
     std::unique_ptr<double[]> val(new double[b]), x(new double[b * d]);

@@ -112,7 +112,8 @@ int run_loop(int argc, char **argv) {
     std::unique_ptr<double[]> u(new double[b * N * nu]), xo(new double[b * nx]), ss(new double[b * (nx + nu)]);
     std::unique_ptr<int32_t[]> sst(new int32_t[b]), it(new int32_t[b]);
     std::vector<int32_t> ws(hd[7] ? b * tmpc::WS_STRIDE : 0, 0), ws1(hd[7] && nvar == 2 ? b * tmpc::WS_STRIDE : 0, 0);
-    tmpc::WorkCounter wc;
+    unsigned long long word = 0;                  // the ring of work counters: one host word, cleared before every launch after the first
+    tmpc::WorkCounter wc{&word, 1, 0};
     if (nvar == 1) {
         // one problem: closed_loop_kernel, a wave per trajectory for all T steps
         const hipError_t e = tmpc::launch_solve_mc(lay.d, lay.ks, B, u.get(), xo.get(), ss.get(), sst.get(), it.get(), hd[7] ? ws.data() : nullptr, &mf, &wc, 1, nullptr);
@@ -166,10 +167,11 @@ int main(int argc, char **argv) {
     std::unique_ptr<double[]> u(new double[static_cast<size_t>(B) * N * nu]), x0(new double[static_cast<size_t>(B) * nx]),
         ss(new double[static_cast<size_t>(B) * (nx + nu)]);
     std::unique_ptr<int32_t[]> st(new int32_t[static_cast<size_t>(B)]), it(new int32_t[static_cast<size_t>(B)]);
+    const tmpc::BatchIO io{B, xk.data(), ref.data(), has_var ? var.data() : nullptr, u.get(), x0.get(), ss.get(), nullptr, st.get(), it.get()};
+    unsigned long long word = 0;                  // (see run_loop)
+    tmpc::WorkCounter wc{&word, 1, 0};
     for (int k = 0; k < nvar; ++k) {
-        tmpc::WorkCounter wc;
-        const hipError_t e = tmpc::launch_solve(lay[k].d, lay[k].ks, k, B, xk.data(), ref.data(), has_var ? var.data() : nullptr, u.get(), x0.get(),
-                                               ss.get(), nullptr, st.get(), it.get(), nullptr, nullptr, &wc, 1, nullptr);
+        const hipError_t e = tmpc::launch_solve(lay[k].d, lay[k].ks, k, io, nullptr, nullptr, &wc, 1, nullptr);
         need(e == hipSuccess, "launch failed (shape not compiled into this build?)");
         std::fprintf(stderr, "wavesim: %s, %lld instances\n", tmpc::kernel_name(lay[k].ks), static_cast<long long>(B));
     }
