@@ -30,7 +30,8 @@ extern "C" {
  * constraint violation (INFEASIBLE only with a Farkas-type certificate), host-only handles report their kernel path,
  * tmpc_debug_dump_layout (tmpc_debug_dump_lp_layout was added later without a bump: a new export, nothing else changed).
  * Added without a bump: the regulator QPs (tmpc_regulator_problem, tmpc_create_regulator, tmpc_reg_run) -- new exports; tmpc_problem
- * and every tracking handle behave as before (a regulator handle accepts ref == NULL in the solve calls, see below) */
+ * and every tracking handle behave as before (a regulator handle accepts ref == NULL in the solve calls, see below); the
+ * disturbance-set estimation (tmpc_estimate_w, tmpc_order_statistics) -- new exports */
 #define TMPC_ABI_VERSION 5
 
 /* error codes (function return values) */
@@ -502,6 +503,57 @@ int tmpc_get_condensed(const tmpc_handle *h, int variant,
 int tmpc_lp_batch(int device, int32_t d, int32_t nr, const double *H, const double *h,
                   int64_t B, const double *C, const int32_t *relax, double relax_by,
                   double *val, double *x, int32_t *status, int32_t *iters);
+
+/*
+ * Exact order statistics of columns of doubles, selected on the device (csrc/tmpc_west.hip: most-significant-digit radix
+ * select on an order-preserving 64-bit key, six passes of 11 + 11 + 11 + 11 + 11 + 9 bits; ties need no care).
+ *
+ *   n, ncol   data is ncol columns of n values, column-major (column c at data + c n), HOST memory
+ *   ranks     n_rank ranks in [0, n), the same for every column: rank r is element r of the sorted column (numpy.partition(col, r)[r])
+ *   out       ncol x n_rank, row-major.  -0 and +0 compare equal and may come back with either sign.
+ *   n_nonfinite  ncol counts (or NULL) of the values that are NaN or +-inf.  NaN have no order: they are left out, the ranks
+ *             count through the other values, and a rank beyond them comes back as NaN.  +-inf are ordered and keep their place.
+ * Errors: TMPC_E_INVALID (sizes, a rank out of range), TMPC_E_NOMEM (8 n ncol bytes of device memory), TMPC_E_DEVICE; text
+ * through tmpc_last_error(NULL).  Added without an ABI bump: a new export, nothing else changed.
+ */
+int tmpc_order_statistics(int device, int64_t n, int32_t ncol, const double *data, int32_t n_rank, const int64_t *ranks,
+                          double *out, int64_t *n_nonfinite);
+
+/*
+ * The disturbance set W of the linear model (A, B), estimated on the plant the model was derived from -- the procedure of the
+ * reference's Results/estimate_W_for_Cartpole.py on the plant of tmpc_mc_set_plant (the closed-form cart-pole, RK4, `substeps`
+ * steps per sampling period par7[6]; NOT the reference's PyBullet model): n_traj closed loops u = -K x of T sampling periods,
+ * the force held over a period, and at every period boundary k = 1 .. T - 1 the one-step prediction error
+ *
+ *        w_k = x_k - (A - B K) x_{k-1}                                        (estimate_W_for_Cartpole.py:94-107)
+ *
+ * i.e. T - 1 samples per trajectory and component (the state after the last period is not sampled; the reference's leading
+ * all-zero sample, :77, is not added).  One lane per trajectory; the samples stay on the device, where order statistics
+ * of each component are selected as by tmpc_order_statistics (the reference's quantiles, :117-120).
+ *
+ *   nx, nu, plant   only TMPC_PLANT_CARTPOLE with nx = 4, nu = 1; anything else: TMPC_E_UNSUPPORTED
+ *   A nx*nx, B nx*nu, K nu*nx (u = -K x), par7 = M, m, b, I, g, l, Th, substeps >= 1
+ *   n_traj >= 1, T >= 2
+ *   x0        n_traj x nx initial states, or NULL: trajectory b starts at x0_lo + (x0_hi - x0_lo) u (two roundings), u_i = (word_i >> 11) 2^-53
+ *             of the four words of Philox4x64-10 with key (seed, first_trajectory + b), counter 0 -- a trajectory does not
+ *             depend on how a sweep is split into calls
+ *   ranks     n_rank ranks in [0, n_traj (T - 1)), the same for every component
+ *   settle_tol  a trajectory with |x_T|_2 > settle_tol (or NaN) counts as not settled (the reference's check uses 1e-3, :110)
+ * Outputs (host memory; any may be NULL):
+ *   order_stats nx x n_rank      w_min, w_max  nx each: extremes of the finite samples (NaN without any)
+ *   n_samples   n_traj (T - 1)   n_nonfinite   nx counts of NaN / +-inf samples (see tmpc_order_statistics)
+ *   not_settled, x_final_norm_max (max |x_T|_2)      x0_used  n_traj x nx
+ *   samples     nx x (T - 1) x n_traj: sample k of trajectory b, component i, at [i][k - 1][b] (for tests and small runs)
+ *   kernel_ms   2 floats: device time of the rollout launch and of the selection launches (HIP events)
+ * Errors: TMPC_E_INVALID (sizes, ranks), TMPC_E_NOMEM when the sample buffer of 8 nx (T - 1) n_traj bytes cannot be allocated
+ * on the device, TMPC_E_DEVICE.  Nothing is launched after an argument error.  Added without an ABI bump: a new export.
+ */
+int tmpc_estimate_w(int device, int32_t nx, int32_t nu, const double *A, const double *B, const double *K,
+                    int plant, const double *par7, int32_t substeps, int64_t n_traj, int32_t T,
+                    const double *x0, const double *x0_lo, const double *x0_hi, uint64_t seed, int64_t first_trajectory,
+                    int32_t n_rank, const int64_t *ranks, double settle_tol,
+                    double *order_stats, double *w_min, double *w_max, int64_t *n_samples, int64_t *n_nonfinite,
+                    int64_t *not_settled, double *x_final_norm_max, double *x0_used, double *samples, float *kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,11 @@ def lib():
         L.tmpc_lp_batch.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmpc_lp_batch.restype = C.c_int
+        L.tmpc_order_statistics.argtypes = [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmpc_order_statistics.restype = C.c_int
+        L.tmpc_estimate_w.argtypes = ([C.c_int, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_int32]
+                                      + [C.c_void_p] * 3 + [C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_double] + [C.c_void_p] * 10)
+        L.tmpc_estimate_w.restype = C.c_int
         L.tmpc_synchronize.argtypes = [C.c_void_p]
         L.tmpc_synchronize.restype = C.c_int
         L.tmpc_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
@@ -590,4 +595,76 @@ def lp_batch(H, h, Cmat, relax=None, relax_by: float = 1.0, device: int = 0, wan
     out = {"val": val, "status": st, "iters": it}
     if want_x:
         out["x"] = x
+    return out
+
+
+def order_statistics(data, ranks, device: int = 0) -> dict:
+    """Exact order statistics of the columns of `data` (n x ncol, or n values), selected on the device (include/tmpc.h:
+    tmpc_order_statistics): out[c, r] = numpy.partition(data[:, c], ranks[r])[ranks[r]] over the values that are not NaN (NaN where
+    there are fewer); n_nonfinite[c] counts NaN and +-inf."""
+    L = lib()
+    d = np.asarray(data, dtype=np.float64)
+    d = d.reshape(-1, 1) if d.ndim == 1 else d
+    cols = np.ascontiguousarray(d.T)                      # column-major: one column after the other
+    ncol, n = cols.shape
+    rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+    out = np.empty((ncol, rk.size))
+    nf = np.empty(ncol, dtype=np.int64)
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = L.tmpc_order_statistics(int(device), n, ncol, ptr(cols), rk.size, ptr(rk), ptr(out), ptr(nf))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_order_statistics failed ({rc}): {L.tmpc_last_error(None).decode()}")
+    return {"order_stats": out, "n_nonfinite": nf}
+
+
+PLANT_KIND = {None: 0, "linear": 0, "cartpole": 1}         # include/tmpc.h: TMPC_PLANT_*
+
+
+def estimate_w(A, B, K, T: int, x0=None, x0_box=None, n_traj=None, seed: int = 0, first: int = 0, ranks=(), settle_tol: float = 1e-3,
+               plant="cartpole", Th: float = 0.02, substeps: int = 10, device: int = 0, want_samples: bool = False) -> dict:
+    """Closed loops u = -K x on the nonlinear plant, the samples w_k = x_k - (A - B K) x_{k-1} and their order statistics, all on the
+    device (include/tmpc.h: tmpc_estimate_w).  Initial states: the array x0 (n_traj x nx), or drawn on the device from
+    x0_box = (lo, hi) for trajectories first .. first + n_traj - 1 of the stream `seed`."""
+    from .workloads import CARTPOLE_PARAMS as P
+    L = lib()
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    nx, nu = B.shape
+    if A.shape != (nx, nx) or K.size != nu * nx:
+        raise ValueError("estimate_w: shapes of A (nx x nx), B (nx x nu), K (nu x nx) do not agree")
+    lo = hi = None
+    if x0 is not None:
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, nx)
+        n_traj = x0.shape[0]
+    elif x0_box is not None and n_traj is not None:
+        lo = np.ascontiguousarray(x0_box[0], dtype=np.float64).reshape(nx)
+        hi = np.ascontiguousarray(x0_box[1], dtype=np.float64).reshape(nx)
+    else:
+        raise ValueError("estimate_w: give x0, or x0_box and n_traj")
+    n_traj, T = int(n_traj), int(T)
+    if plant not in PLANT_KIND:
+        raise ValueError(f"unknown plant {plant!r}")
+    par = np.array([P["M"], P["m"], P["b"], P["I"], P["g"], P["l"], float(Th)])
+    rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+    nper = max(T - 1, 0)
+    stats = np.empty((nx, rk.size))
+    wmin, wmax = np.empty(nx), np.empty(nx)
+    nf = np.empty(nx, dtype=np.int64)
+    ns, bad = C.c_int64(0), C.c_int64(0)
+    worst = C.c_double(0.0)
+    x0u = np.empty((max(n_traj, 0), nx))
+    smp = np.empty((nx, nper, max(n_traj, 0))) if want_samples else None
+    ms = (C.c_float * 2)()
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = L.tmpc_estimate_w(int(device), nx, nu, ptr(A), ptr(B), ptr(K), PLANT_KIND[plant], ptr(par), int(substeps), n_traj, T,
+                           ptr(x0), ptr(lo), ptr(hi), int(seed), int(first), rk.size, ptr(rk), float(settle_tol),
+                           ptr(stats), ptr(wmin), ptr(wmax), C.cast(C.byref(ns), C.c_void_p), ptr(nf), C.cast(C.byref(bad), C.c_void_p),
+                           C.cast(C.byref(worst), C.c_void_p), ptr(x0u), ptr(smp), C.cast(ms, C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_estimate_w failed ({rc}): {L.tmpc_last_error(None).decode()}")
+    out = {"order_stats": stats, "w_min": wmin, "w_max": wmax, "n_samples": ns.value, "n_nonfinite": nf, "not_settled": bad.value,
+           "x_final_norm_max": worst.value, "x0_used": x0u, "rollout_ms": float(ms[0]), "selection_ms": float(ms[1])}
+    if want_samples:
+        out["samples"] = smp
     return out

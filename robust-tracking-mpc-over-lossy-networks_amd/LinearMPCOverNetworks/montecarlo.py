@@ -338,3 +338,133 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
         local = local.to(device)
     table = gather_statistics(local, n_total, rank, world, force_collective=force_collective)
     return table.cpu().numpy(), pi
+
+
+# --------------------------------------------------------------------------- the disturbance set W of the linear model
+W_REFERENCE_X0_BOX = (np.array([-1.0, -0.5, -0.3, -0.5]), np.array([1.0, 0.5, 0.3, 0.5]))      # estimate_W_for_Cartpole.py:66-73
+
+
+def draw_initial_states_philox(n: int, lo, hi, seed: int, first: int = 0):
+    """The initial states tmpc_estimate_w draws on the device (include/tmpc.h), reproduced on the host: trajectory g = first + i takes
+    the four words of Philox4x64-10 with key (seed, g), counter (0, 0, 0, 0); u = (word >> 11) 2^-53; x0 = lo + (hi - lo) u.
+    A trajectory's start does not depend on how a sweep is split."""
+    lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+    hi = np.asarray(hi, dtype=np.float64).reshape(-1)
+    if lo.size != 4 or hi.size != 4:
+        raise ValueError("draw_initial_states_philox: one Philox block per trajectory, four states")
+    g = np.uint64(first) + np.arange(n, dtype=np.uint64)
+    words = philox4x64(np.uint64(0), np.uint64(0), np.uint64(seed), g)                        # (4, n)
+    u = (words >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    return lo + (hi - lo) * u.T
+
+
+def reference_initial_states(n: int = 100, seed: int = 456, box=W_REFERENCE_X0_BOX):
+    """The initial states of the reference's run: four scalar uniform draws per trajectory from default_rng(456)
+    (estimate_W_for_Cartpole.py:12, 82-85); one (n, 4) draw consumes the generator in the same order."""
+    return np.random.default_rng(seed).uniform(box[0], box[1], (n, 4))
+
+
+def quantile_ranks(n: int, discard: float):
+    """The four ranks numpy's default (linear) quantile rule reads for q = discard / 2 and 1 - discard / 2 of n values, and the weight
+    of the upper neighbour of each pair: (ranks [lo_floor, lo_ceil, hi_floor, hi_ceil], gamma [lo, hi])."""
+    ranks, gam = [], []
+    for q in (discard / 2.0, 1.0 - discard / 2.0):
+        virt = (n - 1) * q                                 # numpy.lib: the virtual index of method 'linear'
+        prev = int(np.floor(virt))
+        gam.append(virt - prev)
+        ranks += [min(max(prev, 0), n - 1), min(max(prev + 1, 0), n - 1)]
+    return np.array(ranks, dtype=np.int64), np.array(gam)
+
+
+def _lerp(a, b, t):
+    """numpy.lib's _lerp for scalars"""
+    d = b - a
+    return a + d * t if t < 0.5 else b - d * (1.0 - t)
+
+
+def _box_result(samples, lo, hi, wmin, wmax, n_nonfinite, not_settled, x_final_norm_max, **extra):
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    return dict(samples=samples, lo=lo, hi=hi, w_bound=np.maximum(np.abs(lo), np.abs(hi)), min=np.asarray(wmin), max=np.asarray(wmax),
+                n_samples=None if samples is None else samples.shape[1] * samples.shape[2], n_nonfinite=np.asarray(n_nonfinite),
+                not_settled=int(not_settled), x_final_norm_max=float(x_final_norm_max), **extra)
+
+
+def estimate_disturbance_box_host(A, B, K, x0, T: int, discard: float = 0.025, plant="cartpole", Th: float = 0.02, substeps: int = 10,
+                                  settle_tol: float = 1e-3):
+    """The reference's estimate of the disturbance set (Results/estimate_W_for_Cartpole.py) on the numpy twin of the device plant
+    (workloads.cartpole_step: the closed-form cart-pole, RK4 at the physics rate -- NOT the reference's PyBullet model, so the numbers
+    are those of this plant and no replication of the reference's): closed loops u = -K x from the initial states x0 (n x 4) over T
+    sampling periods, the samples w_k = x_k - (A - B K) x_{k-1} for k = 1 .. T - 1 (:94-107), and per component the
+    discard / 2 and 1 - discard / 2 quantiles of all samples (:117-120, numpy's default linear rule).
+
+    The reference starts its sample list with one all-zero column (:77) that takes part in its quantiles; this function does not add
+    it (at the reference's size, 39 900 samples, that changes the fourth significant digit of the box).
+
+    Returns dict(samples (4, T - 1, n), lo, hi, w_bound = max(|lo|, |hi|), min, max, n_samples, n_nonfinite, not_settled: the number
+    of trajectories with |x_T|_2 > settle_tol (:110), x_final_norm_max).  Non-finite samples are counted per component; a component
+    that has any gets lo = hi = NaN (the loop diverged: there is no box)."""
+    if plant != "cartpole":
+        raise ValueError("estimate_disturbance_box_host: only the cart-pole plant")
+    from .workloads import cartpole_step
+    A = np.asarray(A, dtype=np.float64)
+    B = np.asarray(B, dtype=np.float64)
+    K = np.asarray(K, dtype=np.float64).reshape(1, 4)
+    Acl = A - B @ K
+    x = np.array(x0, dtype=np.float64).reshape(-1, 4)
+    n = x.shape[0]
+    samples = np.empty((4, T - 1, n))
+    for k in range(T):
+        xp = x
+        u = np.zeros(n)
+        for i in range(4):                                # the sums run in index order, as on the device
+            u = u - K[0, i] * xp[:, i]
+        x = cartpole_step(xp, u, Th, substeps)
+        if k + 1 < T:
+            for c in range(4):
+                s = Acl[c, 0] * xp[:, 0]
+                for i in range(1, 4):
+                    s = s + Acl[c, i] * xp[:, i]
+                samples[c, k] = x[:, c] - s
+    flat = samples.reshape(4, -1)
+    fin = np.isfinite(flat)
+    nf = (~fin).sum(axis=1)
+    q = [discard / 2.0, 1.0 - discard / 2.0]
+    lo, hi, wmin, wmax = (np.full(4, np.nan) for _ in range(4))
+    for c in range(4):
+        if nf[c] == 0:
+            lo[c], hi[c] = np.quantile(flat[c], q)
+        if fin[c].any():
+            wmin[c], wmax[c] = flat[c][fin[c]].min(), flat[c][fin[c]].max()
+    nrm = np.sqrt(x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1] + x[:, 2] * x[:, 2] + x[:, 3] * x[:, 3])
+    return _box_result(samples, lo, hi, wmin, wmax, nf, np.sum(~(nrm <= settle_tol)), np.nan if np.isnan(nrm).any() else np.max(nrm),
+                       x0_used=np.array(x0, dtype=np.float64).reshape(-1, 4))
+
+
+def estimate_disturbance_box(A, B, K, x0=None, T: int = 400, discard: float = 0.025, plant="cartpole", x0_box=None, n_traj=None,
+                             seed: int = 456, first: int = 0, Th: float = 0.02, substeps: int = 10, settle_tol: float = 1e-3,
+                             device: int = 0, want_samples: bool = False):
+    """estimate_disturbance_box_host on the device (include/tmpc.h: tmpc_estimate_w; csrc/tmpc_west.hip): one lane per trajectory,
+    the samples stay in device memory (8 * 4 * (T - 1) * n_traj bytes), and the four order statistics behind the two quantiles of each
+    component -- the neighbours floor and ceil of q (n - 1) -- are selected there exactly; the interpolation between them is numpy's.
+    Initial states: x0 (n x 4), or x0_box = (lo, hi) with n_traj and seed: drawn on the device, trajectory first + i from the stream
+    of draw_initial_states_philox.  Like the host twin -- and unlike the reference -- no all-zero sample is added in front.
+    Same return values (samples: None unless want_samples), and rollout_ms / selection_ms, the device times of the two stages."""
+    from . import _native
+    if x0 is not None:
+        n_traj = np.asarray(x0).reshape(-1, 4).shape[0]
+    if n_traj is None:
+        raise ValueError("estimate_disturbance_box: give x0, or x0_box and n_traj")
+    n = int(n_traj) * (int(T) - 1)
+    ranks, gam = quantile_ranks(max(n, 1), discard)
+    out = _native.estimate_w(A, B, K, T, x0=x0, x0_box=x0_box, n_traj=n_traj, seed=seed, first=first, ranks=ranks, settle_tol=settle_tol,
+                             plant=plant, Th=Th, substeps=substeps, device=device, want_samples=want_samples)
+    st = out["order_stats"]
+    lo, hi = np.full(4, np.nan), np.full(4, np.nan)
+    for c in range(4):
+        if out["n_nonfinite"][c] == 0:
+            lo[c], hi[c] = _lerp(st[c, 0], st[c, 1], gam[0]), _lerp(st[c, 2], st[c, 3], gam[1])
+    res = _box_result(out.get("samples"), lo, hi, out["w_min"], out["w_max"], out["n_nonfinite"], out["not_settled"],
+                      out["x_final_norm_max"], x0_used=out["x0_used"], rollout_ms=out["rollout_ms"], selection_ms=out["selection_ms"],
+                      order_stats=st, ranks=ranks)
+    res["n_samples"] = out["n_samples"]
+    return res

@@ -16,6 +16,7 @@
 
 #include "tmpc_condense.hpp"
 #include "tmpc_device.hpp"
+#include "tmpc_west.hpp"
 
 namespace {
 
@@ -86,6 +87,23 @@ class Arena {
     static size_t rounded(size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) / 256 * 256; }
     std::vector<Piece> pieces_;
     DeviceBuffer buf_;
+};
+
+// device memory of one call, freed when the call returns (the sample buffer is far too large to keep)
+struct WestMem {
+    std::vector<void *> blocks;
+    ~WestMem() { for (void *p : blocks) (void)hipFree(p); }
+    template <class T> hipError_t get(T **out, size_t bytes) {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
+        if (e == hipSuccess) blocks.push_back(p);
+        *out = static_cast<T *>(p);
+        return e;
+    }
+};
+struct WestEvents {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~WestEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 // What the last tmpc_mc_run / tmpc_reg_run left in the loop arena for the getters (nullptr / 0: nothing).  A run resets them
@@ -1532,6 +1550,161 @@ int tmpc_debug_dump_lp_layout(int32_t d, int32_t nr, const double *H, const doub
     ok = ok && std::fwrite(lh.rs.data(), 8, lh.rs.size(), f) == lh.rs.size();
     std::fclose(f);
     if (!ok) { g_create_error = "tmpc_debug_dump_lp_layout: short write"; return TMPC_E_INVALID; }
+    return TMPC_OK;
+}
+
+// ---- the disturbance set of the linear model, estimated on the plant it was derived from (tmpc_west.hip)
+
+#define WEST_TRY(expr)                                                                     \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            g_create_error = std::string(who) + ": " #expr ": " + hipGetErrorString(e_);   \
+            return TMPC_E_DEVICE;                                                          \
+        }                                                                                  \
+    } while (0)
+
+namespace {
+// selection on columns that are on the device already; the answers come back to host memory
+int west_select_to_host(const char *who, WestMem &mem, const double *d_data, int64_t n, int64_t col_stride, int ncol, int32_t n_rank,
+                        const int64_t *ranks, double *out, int64_t *n_nonfinite, hipEvent_t before = nullptr, hipEvent_t after = nullptr) {
+    unsigned long long *d_ranks = nullptr, *d_ws = nullptr, *d_nf = nullptr;
+    double *d_out = nullptr;
+    const size_t nr = static_cast<size_t>(n_rank), nc = static_cast<size_t>(ncol);
+    WEST_TRY(mem.get(&d_ranks, nr * 8));
+    WEST_TRY(mem.get(&d_ws, tmpc::west_select_ws_words(ncol) * 8));
+    WEST_TRY(mem.get(&d_nf, nc * 8));
+    WEST_TRY(mem.get(&d_out, nc * nr * 8));
+    if (n_rank > 0) WEST_TRY(hipMemcpy(d_ranks, ranks, nr * 8, hipMemcpyHostToDevice));
+    if (before) WEST_TRY(hipEventRecord(before, nullptr));
+    WEST_TRY(tmpc::launch_west_select(d_data, n, col_stride, ncol, n_rank > 0 && out ? n_rank : 0, d_ranks, d_ws, d_out, d_nf, nullptr));
+    if (after) WEST_TRY(hipEventRecord(after, nullptr));
+    WEST_TRY(hipDeviceSynchronize());
+    if (out && n_rank > 0) WEST_TRY(hipMemcpy(out, d_out, nc * nr * 8, hipMemcpyDeviceToHost));
+    if (n_nonfinite) WEST_TRY(hipMemcpy(n_nonfinite, d_nf, nc * 8, hipMemcpyDeviceToHost));
+    return TMPC_OK;
+}
+}  // namespace
+
+int tmpc_order_statistics(int device, int64_t n, int32_t ncol, const double *data, int32_t n_rank, const int64_t *ranks, double *out,
+                          int64_t *n_nonfinite) {
+    const char *who = "tmpc_order_statistics";
+    if (n < 1 || ncol < 1 || n_rank < 0 || !data || (n_rank > 0 && (!ranks || !out))) {
+        g_create_error = "tmpc_order_statistics: need n >= 1, ncol >= 1, data, and ranks / out for n_rank > 0";
+        return TMPC_E_INVALID;
+    }
+    for (int32_t r = 0; r < n_rank; ++r)
+        if (ranks[r] < 0 || ranks[r] >= n) { g_create_error = "tmpc_order_statistics: rank out of range [0, n)"; return TMPC_E_INVALID; }
+    WEST_TRY(hipSetDevice(device));
+    WestMem mem;
+    double *d_data = nullptr;
+    const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(ncol) * 8;
+    if (mem.get(&d_data, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        g_create_error = "tmpc_order_statistics: out of device memory";
+        return TMPC_E_NOMEM;
+    }
+    WEST_TRY(hipMemcpy(d_data, data, bytes, hipMemcpyHostToDevice));
+    return west_select_to_host(who, mem, d_data, n, n, ncol, n_rank, ranks, out, n_nonfinite);
+}
+
+int tmpc_estimate_w(int device, int32_t nx, int32_t nu, const double *A, const double *B, const double *K, int plant, const double *par7,
+                    int32_t substeps, int64_t n_traj, int32_t T, const double *x0, const double *x0_lo, const double *x0_hi, uint64_t seed,
+                    int64_t first_trajectory, int32_t n_rank, const int64_t *ranks, double settle_tol, double *order_stats, double *w_min,
+                    double *w_max, int64_t *n_samples, int64_t *n_nonfinite, int64_t *not_settled, double *x_final_norm_max,
+                    double *x0_used, double *samples, float *kernel_ms) {
+    const char *who = "tmpc_estimate_w";
+    if (plant != TMPC_PLANT_CARTPOLE || nx != tmpc::WEST_NX || nu != 1) {
+        g_create_error = "tmpc_estimate_w: only TMPC_PLANT_CARTPOLE (nx = 4, nu = 1) is supported";
+        return TMPC_E_UNSUPPORTED;
+    }
+    if (!A || !B || !K || !par7 || (!x0 && (!x0_lo || !x0_hi)) || (n_rank > 0 && !ranks)) { g_create_error = "tmpc_estimate_w: NULL argument"; return TMPC_E_INVALID; }
+    if (n_traj < 1 || T < 2 || substeps < 1 || n_rank < 0 || first_trajectory < 0) {
+        g_create_error = "tmpc_estimate_w: need n_traj >= 1, T >= 2, substeps >= 1, n_rank >= 0, first_trajectory >= 0";
+        return TMPC_E_INVALID;
+    }
+    const int64_t n = n_traj * static_cast<int64_t>(T - 1);
+    for (int32_t r = 0; r < n_rank; ++r)
+        if (ranks[r] < 0 || ranks[r] >= n) { g_create_error = "tmpc_estimate_w: rank out of range [0, n_traj (T - 1))"; return TMPC_E_INVALID; }
+    constexpr int NX = tmpc::WEST_NX;
+    tmpc::WestRollout a{};
+    {
+#pragma clang fp contract(off)
+        for (int i = 0; i < NX; ++i)
+            for (int j = 0; j < NX; ++j) {
+                const double bk = B[i] * K[j];           // A - B K in double, a product and a difference per entry (numpy's A - B @ K)
+                a.Acl[i * NX + j] = A[i * NX + j] - bk;
+            }
+    }
+    for (int i = 0; i < NX; ++i) { a.K[i] = K[i]; a.lo[i] = x0 ? 0.0 : x0_lo[i]; a.hi[i] = x0 ? 0.0 : x0_hi[i]; }
+    for (int i = 0; i < 7; ++i) a.par[i] = par7[i];
+    a.substeps = substeps; a.T = T; a.draw = x0 ? 0 : 1;
+    a.n_traj = n_traj; a.first = first_trajectory; a.seed = seed;
+
+    WEST_TRY(hipSetDevice(device));
+    WestMem mem;
+    const size_t nt = static_cast<size_t>(n_traj);
+    double *d_samples = nullptr, *d_x0 = nullptr, *d_x0u = nullptr, *d_norm = nullptr;
+    unsigned long long *d_mm = nullptr;
+    if (mem.get(&d_samples, static_cast<size_t>(n) * NX * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        g_create_error = "tmpc_estimate_w: out of device memory for the samples (8 nx (T - 1) n_traj bytes)";
+        return TMPC_E_NOMEM;
+    }
+    WEST_TRY(mem.get(&d_x0u, nt * NX * 8));
+    WEST_TRY(mem.get(&d_norm, nt * 8));
+    WEST_TRY(mem.get(&d_mm, 2 * NX * 8));
+    if (x0) {
+        WEST_TRY(mem.get(&d_x0, nt * NX * 8));
+        WEST_TRY(hipMemcpy(d_x0, x0, nt * NX * 8, hipMemcpyHostToDevice));
+    }
+    WEST_TRY(hipMemset(d_mm, 0xff, NX * 8));
+    WEST_TRY(hipMemset(d_mm + NX, 0, NX * 8));
+    a.x0 = d_x0; a.x0_used = d_x0u; a.samples = d_samples; a.xnorm = d_norm; a.minmax = d_mm;
+    WestEvents ev;
+    for (hipEvent_t &e : ev.ev) WEST_TRY(hipEventCreate(&e));
+    WEST_TRY(hipEventRecord(ev.ev[0], nullptr));
+    WEST_TRY(tmpc::launch_west_rollout(a, nullptr));
+    WEST_TRY(hipEventRecord(ev.ev[1], nullptr));
+    const bool want_sel = (order_stats && n_rank > 0) || n_nonfinite;
+    if (want_sel)
+        if (const int rc = west_select_to_host(who, mem, d_samples, n, n, NX, n_rank, ranks, order_stats, n_nonfinite, ev.ev[2], ev.ev[3]); rc != TMPC_OK) return rc;
+    WEST_TRY(hipDeviceSynchronize());
+    if (kernel_ms) {
+        WEST_TRY(hipEventElapsedTime(&kernel_ms[0], ev.ev[0], ev.ev[1]));
+        kernel_ms[1] = 0.0f;
+        if (want_sel) WEST_TRY(hipEventElapsedTime(&kernel_ms[1], ev.ev[2], ev.ev[3]));
+    }
+    if (w_min || w_max) {
+        unsigned long long mm[2 * NX];
+        WEST_TRY(hipMemcpy(mm, d_mm, sizeof mm, hipMemcpyDeviceToHost));
+        for (int c = 0; c < NX; ++c) {
+            double lo, hi;
+            const unsigned long long ul = tmpc::west_unkey(mm[c]), uh = tmpc::west_unkey(mm[NX + c]);
+            std::memcpy(&lo, &ul, 8);
+            std::memcpy(&hi, &uh, 8);
+            const bool none = !(lo <= hi);               // no finite sample: the start values, +inf / -inf
+            if (w_min) w_min[c] = none ? std::nan("") : lo;
+            if (w_max) w_max[c] = none ? std::nan("") : hi;
+        }
+    }
+    if (n_samples) *n_samples = n;
+    if (not_settled || x_final_norm_max) {
+        std::vector<double> nrm(nt);
+        WEST_TRY(hipMemcpy(nrm.data(), d_norm, nt * 8, hipMemcpyDeviceToHost));
+        int64_t bad = 0;
+        double worst = 0.0;
+        bool any_nan = false;
+        for (double v : nrm) {
+            if (!(v <= settle_tol)) ++bad;               // (a NaN has not settled either)
+            if (v != v) any_nan = true;
+            else if (v > worst) worst = v;
+        }
+        if (not_settled) *not_settled = bad;
+        if (x_final_norm_max) *x_final_norm_max = any_nan ? std::nan("") : worst;
+    }
+    if (x0_used) WEST_TRY(hipMemcpy(x0_used, d_x0u, nt * NX * 8, hipMemcpyDeviceToHost));
+    if (samples) WEST_TRY(hipMemcpy(samples, d_samples, static_cast<size_t>(n) * NX * 8, hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
 
