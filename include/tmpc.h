@@ -10,7 +10,7 @@
  * Conventions
  *   - plain C, no C++/torch types; every matrix is float64, row-major, dense;
  *   - the caller owns all buffers passed in; the library owns the opaque handle,
- *     its device copies of the problem, its scratch and its HIP stream;
+ *     its device copies of the problem, its scratch and its HIP streams;
  *   - every function returns 0 on success and a negative TMPC_E_* code otherwise;
  *     tmpc_last_error() gives the message; no C++ exception crosses the boundary;
  *   - a handle is not thread-safe; use one handle per host thread / per GPU.
@@ -31,7 +31,8 @@ extern "C" {
  * tmpc_debug_dump_layout (tmpc_debug_dump_lp_layout was added later without a bump: a new export, nothing else changed).
  * Added without a bump: the regulator QPs (tmpc_regulator_problem, tmpc_create_regulator, tmpc_reg_run) -- new exports; tmpc_problem
  * and every tracking handle behave as before (a regulator handle accepts ref == NULL in the solve calls, see below); the
- * disturbance-set estimation (tmpc_estimate_w, tmpc_order_statistics) -- new exports */
+ * disturbance-set estimation (tmpc_estimate_w, tmpc_order_statistics) -- new exports; tmpc_set_call_overlap, tmpc_debug_lane_counters,
+ * tmpc_debug_calls_conflict -- new exports (what tmpc_kernel_ms_total adds up for calls that overlap is defined there) */
 #define TMPC_ABI_VERSION 5
 
 /* error codes (function return values) */
@@ -224,16 +225,25 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B,
 
 /*
  * Same, with every pointer a DEVICE pointer on the handle's device (e.g. a torch
- * tensor's data_ptr()).  The kernels are enqueued on the handle's stream and the
+ * tensor's data_ptr()).  The kernels are enqueued on one of the handle's streams and the
  * call returns without synchronising; use tmpc_synchronize() or
  * tmpc_last_kernel_ms().
  *
- * Ordering contract: the handle's stream is its own non-blocking stream; it is NOT ordered against
- * the stream that produced the inputs or will consume the outputs (e.g. torch's current stream).
- * The caller synchronises on both sides: the producers of x_k / ref / variant must have completed
- * before this call (torch.cuda.synchronize() or an event wait), and the outputs may be read only
- * after tmpc_synchronize().  Instances whose variant id is >= the handle's number of problems get
- * status TMPC_STATUS_NUMERICAL and NaN outputs.
+ * Ordering contract: calls on a handle take effect as if executed in call order.  Independent calls may run concurrently: the
+ * handle keeps two launch lanes (a non-blocking stream each, with its own launch scratch), and a call goes to the other lane
+ * than the call before it when none of its arrays overlaps -- read after write, write after write or write after read, by byte
+ * range: x_k, ref, variant are read; u_nom, x_nom0, xu_ss, x_nom, status, iters written -- an array of the unfinished calls of
+ * that call's lane.  A call that does overlap stays behind the call it depends on, and waits for the other lane as well where it
+ * depends on both.  The tail of one launch (a launch ends with its slowest instances while most of the card idles) then runs
+ * under the head of the next: a server that streams independent batches through one handle needs no second handle.  The
+ * second lane is created by the first call that finds unfinished, independent work of the handle to run beside; every other entry
+ * point (tmpc_solve_batch, tmpc_mc_run / _replay, tmpc_reg_run, the getters) joins the lanes before it runs.  tmpc_set_call_overlap
+ * turns the second lane off.
+ * The handle's streams are its own: they are NOT ordered against the stream that produced the inputs or will consume the
+ * outputs (e.g. torch's current stream).  The caller synchronises on both sides: the producers of x_k / ref / variant must have
+ * completed before this call (torch.cuda.synchronize() or an event wait), and the outputs may be read only after
+ * tmpc_synchronize(), as before.  Instances whose variant id is >= the handle's number of problems get status TMPC_STATUS_NUMERICAL
+ * and NaN outputs.
  */
 int tmpc_solve_batch_device(tmpc_handle *h, int64_t B,
                             const double *x_k, const double *ref, const uint8_t *variant,
@@ -431,21 +441,45 @@ int tmpc_mc_get_physics_error(tmpc_handle *h, int64_t B, double *err2_phys);
 #define TMPC_ACTUATOR_SMART      1
 int tmpc_mc_set_actuator(tmpc_handle *h, int kind);
 
-/* Block until everything enqueued on the handle's stream has finished. */
+/* Block until everything enqueued on the handle, on either launch lane, has finished. */
 int tmpc_synchronize(tmpc_handle *h);
 
 /*
+ * Successive independent tmpc_solve_batch_device calls of the handle on two launch lanes (on != 0, the default; see the
+ * ordering contract there) or every call on the one stream the handle is created with (on = 0: calls run one after the
+ * other, and a second stream is never created).  Results do not depend on the setting.  Turning it off orders the first
+ * lane behind what the second one still holds; turning it on waits for the calls enqueued while it was off.
+ */
+int tmpc_set_call_overlap(tmpc_handle *h, int on);
+/*
+ * Diagnostics: calls_per_lane[2] = the tmpc_solve_batch_device calls enqueued on the first / second lane, *cross_lane_waits =
+ * those among them that depended on unfinished calls of both lanes and made their lane wait for the other one -- since the
+ * handle was created or the counters were last reset (reset != 0 clears them after reading).  Either pointer may be NULL.
+ */
+int tmpc_debug_lane_counters(tmpc_handle *h, int64_t *calls_per_lane, int64_t *cross_lane_waits, int reset);
+/*
+ * Diagnostics (tests/test_call_hazards.py): the overlap rule itself, no device and no handle involved.  a and b are the nine
+ * pointer arguments of two tmpc_solve_batch_device calls over B_a / B_b instances of a problem with nx, nu, N, in the order
+ * of that function (x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters; NULL: not given); nothing is
+ * dereferenced.  Returns 1 when the later call must stay behind the earlier one, 0 when they may overlap, TMPC_E_INVALID.
+ */
+int tmpc_debug_calls_conflict(int32_t nx, int32_t nu, int32_t N, int64_t B_a, const void *const *a, int64_t B_b, const void *const *b);
+
+/*
  * Device time of the solve kernel(s) of the most recent tmpc_solve_batch[_device]
- * call, from HIP events recorded on the handle's stream around the launch
- * (synchronises the stream).  This is what bench.py reports as the kernel's
- * launch duration.
+ * call: from its own start to its own end, HIP events recorded on the call's stream
+ * around its launches (waits for the call).  A call that overlapped with its neighbours
+ * shows a longer time here than it would alone.
  */
 int tmpc_last_kernel_ms(tmpc_handle *h, float *ms);
 
 /*
- * Sum of the per-call device times (same HIP events as above) of all solve calls since the
- * last reset, and their count (at most 4096 calls are tracked between resets).
- * Synchronises the stream.  bench.py divides the two for the average launch duration.
+ * Device time the handle was busy with the solve calls since the last reset, and their count (at most 4096 calls are
+ * tracked between resets).  Every call adds the time by which it extended the handle's busy period: from the later of
+ * {its own start event, the end event of the call that ended last among those before it} to its own end event.  For calls
+ * that do not overlap -- one lane, tmpc_set_call_overlap(0), the closed loops -- that is each call's own start-to-end time,
+ * the sum of what tmpc_last_kernel_ms reports; where calls overlap, the overlapped part counts once.
+ * Synchronises the handle.  bench.py divides the two for the average device time per call.
  */
 int tmpc_kernel_ms_total(tmpc_handle *h, float *total_ms, int32_t *launches, int reset);
 

@@ -136,6 +136,12 @@ def lib():
         L.tmpc_estimate_w.restype = C.c_int
         L.tmpc_synchronize.argtypes = [C.c_void_p]
         L.tmpc_synchronize.restype = C.c_int
+        L.tmpc_set_call_overlap.argtypes = [C.c_void_p, C.c_int]
+        L.tmpc_set_call_overlap.restype = C.c_int
+        L.tmpc_debug_lane_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+        L.tmpc_debug_lane_counters.restype = C.c_int
+        L.tmpc_debug_calls_conflict.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p)]
+        L.tmpc_debug_calls_conflict.restype = C.c_int
         L.tmpc_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.tmpc_last_kernel_ms.restype = C.c_int
         L.tmpc_kernel_ms_total.argtypes = [C.c_void_p, C.POINTER(C.c_float), _ip, C.c_int]
@@ -358,6 +364,35 @@ def solve_batch_device(h: Handle, B: int, x_ptr, r_ptr, var_ptr, u_ptr, x0_ptr, 
 def synchronize(h: Handle):
     if lib().tmpc_synchronize(h.ptr) != 0:
         raise RuntimeError(h.error())
+
+
+def set_call_overlap(h: Handle, on: bool = True):
+    """include/tmpc.h: tmpc_set_call_overlap -- independent tmpc_solve_batch_device calls of the handle may run side by side (default) or not."""
+    if lib().tmpc_set_call_overlap(h.ptr, int(bool(on))) != 0:
+        raise RuntimeError(h.error())
+
+
+def lane_counters(h: Handle, reset: bool = False):
+    """include/tmpc.h: tmpc_debug_lane_counters -> ((device-pointer calls enqueued on lane 0, on lane 1), calls that had to wait for
+    the other lane), since the handle was created or the counters were last reset."""
+    calls, waits = (C.c_int64 * 2)(), C.c_int64()
+    if lib().tmpc_debug_lane_counters(h.ptr, calls, C.byref(waits), int(reset)) != 0:
+        raise RuntimeError(h.error())
+    return (int(calls[0]), int(calls[1])), int(waits.value)
+
+
+SOLVE_POINTERS = ("x_k", "ref", "variant", "u_nom", "x_nom0", "xu_ss", "x_nom", "status", "iters")
+
+
+def calls_conflict(nx: int, nu: int, N: int, B_a: int, a: dict, B_b: int, b: dict) -> bool:
+    """include/tmpc.h: tmpc_debug_calls_conflict -- whether the later of two tmpc_solve_batch_device calls must stay behind the
+    earlier one.  a, b: {argument name (SOLVE_POINTERS): address}; a missing name or None is a NULL pointer.  No device is touched."""
+    pa = (C.c_void_p * 9)(*[a.get(k) for k in SOLVE_POINTERS])
+    pb = (C.c_void_p * 9)(*[b.get(k) for k in SOLVE_POINTERS])
+    rc = lib().tmpc_debug_calls_conflict(nx, nu, N, int(B_a), pa, int(B_b), pb)
+    if rc < 0:
+        raise RuntimeError("tmpc_debug_calls_conflict: invalid argument")
+    return bool(rc)
 
 
 def last_kernel_ms(h: Handle) -> float:

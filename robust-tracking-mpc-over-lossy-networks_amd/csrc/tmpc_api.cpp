@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <deque>
 #include <initializer_list>
 #include <new>
 #include <string>
@@ -16,6 +17,7 @@
 
 #include "tmpc_condense.hpp"
 #include "tmpc_device.hpp"
+#include "tmpc_hazard.hpp"
 #include "tmpc_west.hpp"
 
 namespace {
@@ -118,6 +120,29 @@ struct LoopRecords {
     int fused = 0;               // tmpc_mc_last_fused
 };
 
+// One launch lane of a device handle: a non-blocking stream and everything a solve launch on it mutates, so that launches on
+// different lanes may overlap while the launches of one lane stay ordered.  Lane 0 (the primary lane) exists from tmpc_create on
+// and takes every entry point; lane 1 is created by the first tmpc_solve_batch_device call that can run beside an unfinished one.
+struct Lane {
+    hipStream_t stream = nullptr;
+    tmpc::WorkCounter wc;        // work counters of the wave / block kernel's launches (tmpc_device.hpp)
+    DeviceBuffer blk_ws;         // block-kernel workspace
+    DeviceBuffer save;           // (s, lambda) of every resident wave at its hand-over to the refinement (DeviceQP::save)
+    DeviceBuffer ticks;          // tmpc_set_solve_timing: one tick count per instance of the lane's last call
+    // the unfinished tmpc_solve_batch_device calls of the lane, oldest first: what they touch and the event behind their last kernel
+    struct InFlight {
+        tmpc::CallRanges touched;
+        hipEvent_t end;
+    };
+    std::deque<InFlight> inflight;
+    // end events for the calls beyond the 4096 timing pairs of a handle (created when first needed); a call that would take the
+    // event of a record still in flight waits for that record
+    std::vector<hipEvent_t> spare;
+    size_t spare_next = 0;
+    int64_t calls = 0;           // tmpc_solve_batch_device calls enqueued here (tmpc_debug_lane_counters)
+};
+constexpr size_t LANE_SPARE_EVENTS = 64;
+
 struct Variant {
     tmpc::Condensed c;
     tmpc::DeviceQP d{};
@@ -145,18 +170,20 @@ struct tmpc_handle {
     int reg_tube = 0;
     std::vector<double> hA, hB, hK, hKanc, hQ, hR;   // host copies for the closed-loop entry points
     int kernel_path = TMPC_PATH_AUTO;
-    hipStream_t stream = nullptr;
-    tmpc::WorkCounter wc;        // work counters of the wave kernel's launches (tmpc_device.hpp)
+    Lane lane[2];
+    hipStream_t stream = nullptr;        // = lane[0].stream: everything but an overlapped tmpc_solve_batch_device call runs on it
+    int overlap = 1;             // tmpc_set_call_overlap
+    int cur = 0;                 // lane of the latest solve call
+    int64_t lane_waits = 0;      // calls that had to wait for the other lane (tmpc_debug_lane_counters)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-    // event pairs of the launches since the last tmpc_kernel_ms_total(reset): per-launch device time
+    // event pairs of the calls since the last tmpc_kernel_ms_total(reset), and the lane each ran on: per-call device time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+    std::vector<uint8_t> pool_lane;
     size_t pool_used = 0;
-    DeviceBuffer blk_ws;         // block-kernel workspace
-    int blk_blocks = 0;          // workgroups it is sized for
-    DeviceBuffer save;           // (s, lambda) of every resident wave at its hand-over to the refinement (DeviceQP::save)
+    int blk_blocks = 0;          // workgroups a lane's block-kernel workspace is sized for
     int want_ticks = 0;          // per-solve durations (tmpc_set_solve_timing): one tick count per instance of the last call
-    DeviceBuffer ticks;
+    int ticks_lane = 0;          // the lane that call ran on
     int64_t ticks_n = 0;
     DeviceBuffer reg_zero;       // regulator: the zero reference
     std::string err;
@@ -510,15 +537,34 @@ int upload_variant(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     return TMPC_OK;
 }
 
-// block-kernel workspace: one slice per resident workgroup, sized once for the largest variant (a slice is addressed with the
-// launching variant's ncp)
-int ensure_block_ws(tmpc_handle *h) {
-    if (h->blk_ws.p) return TMPC_OK;
+// Waits for everything enqueued on the handle, on either lane.
+hipError_t sync_lanes(tmpc_handle *h) {
+    hipError_t e = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
+    Lane &second = h->lane[1];
+    if (e == hipSuccess && second.stream) e = hipStreamSynchronize(second.stream);
+    if (e == hipSuccess)
+        for (Lane &l : h->lane) l.inflight.clear();
+    return e;
+}
+
+// Orders the primary lane behind what the secondary lane has been given, without blocking the host: the start of every entry
+// point that runs on the primary lane alone.  Each of them ends with a synchronisation of that lane, which then covers both.
+int join_lanes(tmpc_handle *h) {
+    Lane &second = h->lane[1];
+    if (second.stream && !second.inflight.empty()) HIP_TRY(h, hipStreamWaitEvent(h->stream, second.inflight.back().end, 0));
+    h->cur = 0;
+    return TMPC_OK;
+}
+
+// block-kernel workspace of a lane: one slice per resident workgroup, sized once for the largest variant (a slice is addressed
+// with the launching variant's ncp)
+int ensure_block_ws(tmpc_handle *h, Lane &lane) {
+    if (lane.blk_ws.p) return TMPC_OK;
     int ncp = 0, occ_max = 1;
     for (int k = 0; k < h->nvariants; ++k)
         if (h->v[k].tiles) { ncp = std::max(ncp, h->v[k].bq.ncp); occ_max = std::max(occ_max, tmpc::block_occupancy(h->v[k].tiles)); }
     h->blk_blocks = h->n_cu * occ_max;
-    HIP_TRY(h, h->blk_ws.reserve(static_cast<size_t>(h->blk_blocks) * tmpc::block_workspace_rows() * ncp * sizeof(double), h->stream));
+    HIP_TRY(h, lane.blk_ws.reserve(static_cast<size_t>(h->blk_blocks) * tmpc::block_workspace_rows() * ncp * sizeof(double), lane.stream));
     return TMPC_OK;
 }
 
@@ -578,14 +624,15 @@ int ensure_staging(tmpc_handle *h, int64_t B) {
 int ensure_reg_zero(tmpc_handle *h, int64_t B) {
     const size_t bytes = static_cast<size_t>(B) * h->nx * sizeof(double);
     if (bytes <= h->reg_zero.cap) return TMPC_OK;
+    HIP_TRY(h, sync_lanes(h));             // (launches on either lane read the old block)
     HIP_TRY(h, h->reg_zero.reserve(bytes, h->stream));
     HIP_TRY(h, hipMemset(h->reg_zero.p, 0, bytes));
     return TMPC_OK;
 }
 
-// The next pair of timing events of the handle's pool (tmpc_last_kernel_ms / tmpc_kernel_ms_total read them); records the first one.
-// Beyond 4096 pairs the last one is reused.
-int begin_timed_launch(tmpc_handle *h) {
+// The next pair of timing events of the handle's pool (tmpc_last_kernel_ms / tmpc_kernel_ms_total read them); records the first one
+// on the lane's stream.  Beyond 4096 pairs the last one is reused.
+int begin_timed_launch(tmpc_handle *h, Lane &lane) {
     hipEvent_t e0 = h->pool.back().first, e1 = h->pool.back().second;
     if (h->pool_used < 4096) {
         if (h->pool_used == h->pool.size()) {
@@ -596,24 +643,29 @@ int begin_timed_launch(tmpc_handle *h) {
         }
         e0 = h->pool[h->pool_used].first;
         e1 = h->pool[h->pool_used].second;
+        if (h->pool_lane.size() <= h->pool_used) h->pool_lane.resize(h->pool.size(), 0);
+        h->pool_lane[h->pool_used] = static_cast<uint8_t>(&lane - h->lane);
         ++h->pool_used;
     }
     h->ev0 = e0; h->ev1 = e1;
-    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev0, lane.stream));
     return TMPC_OK;
 }
 
 // Scratch of the solve launches of the first nvar variants over B instances: the per-solve tick buffer (zeroed; with
 // tmpc_set_solve_timing on) and the wave kernel's hand-over save slots, one per resident wave (at most 8 per CU).  The variants
-// share the slots: launches on one stream do not overlap, and a launch reads only what it wrote itself.
-int prepare_wave_scratch(tmpc_handle *h, int64_t B, int nvar) {
+// share the slots: launches on one stream do not overlap, and a launch reads only what it wrote itself.  Both buffers are the
+// lane's own, so the same holds for each lane while launches on different lanes overlap; a buffer that grows waits for its
+// lane alone, the only one whose launches use it.
+int prepare_wave_scratch(tmpc_handle *h, Lane &lane, int64_t B, int nvar) {
     long long *ticks = nullptr;
     if (h->want_ticks) {
         const size_t bytes = static_cast<size_t>(B) * sizeof(long long);
-        HIP_TRY(h, h->ticks.reserve(bytes, h->stream));
-        ticks = h->ticks.as<long long>();
+        HIP_TRY(h, lane.ticks.reserve(bytes, lane.stream));
+        ticks = lane.ticks.as<long long>();
         h->ticks_n = B;
-        HIP_TRY(h, hipMemsetAsync(ticks, 0, bytes, h->stream));
+        h->ticks_lane = static_cast<int>(&lane - h->lane);
+        HIP_TRY(h, hipMemsetAsync(ticks, 0, bytes, lane.stream));
     }
     size_t save = 0;
     for (int k = 0; k < nvar; ++k) {
@@ -621,33 +673,106 @@ int prepare_wave_scratch(tmpc_handle *h, int64_t B, int nvar) {
         if (!use_block(h, h->v[k]) && !tmpc::parks_in_lds(s))
             save = std::max(save, static_cast<size_t>(h->n_cu) * 8 * 2 * (2 * s.dp + s.ds + 2 * s.cp + s.cs) * 64 * sizeof(float));
     }
-    HIP_TRY(h, h->save.reserve(save, h->stream));
+    HIP_TRY(h, lane.save.reserve(save, lane.stream));
     for (int k = 0; k < nvar; ++k) {
         Variant &v = h->v[k];
-        v.d.ticks = v.db.ticks = ticks;
-        if (!use_block(h, v)) v.d.save = tmpc::parks_in_lds(v.shape) ? nullptr : h->save.as<float>();
+        v.d.ticks = v.db.ticks = ticks;          // (kernel arguments of the launches that follow: copied when they are enqueued)
+        if (!use_block(h, v)) v.d.save = tmpc::parks_in_lds(v.shape) ? nullptr : lane.save.as<float>();
     }
     return TMPC_OK;
 }
 
-int enqueue(tmpc_handle *h, const tmpc::BatchIO &io, int32_t *const *ws = nullptr, bool variants_valid = false) {
-    { const int rce = begin_timed_launch(h); if (rce) return rce; }
+// All kernels of one solve call, on one lane and in one order: the variant marking, then one launch per variant.
+int enqueue(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const *ws = nullptr, bool variants_valid = false) {
+    { const int rce = begin_timed_launch(h, lane); if (rce) return rce; }
     if (io.variant != nullptr && !variants_valid)      // (the closed loop's selector is its own gamma flags: always 0 or 1)
-        HIP_TRY(h, tmpc::launch_mark_invalid_variants(io, h->nvariants, h->nx, h->nu, h->N, h->stream));
+        HIP_TRY(h, tmpc::launch_mark_invalid_variants(io, h->nvariants, h->nx, h->nu, h->N, lane.stream));
     const int nvar = io.variant != nullptr ? h->nvariants : 1;        // (no per-instance selector: everything is variant 0)
-    { const int rcs = prepare_wave_scratch(h, io.B, nvar); if (rcs) return rcs; }
+    { const int rcs = prepare_wave_scratch(h, lane, io.B, nvar); if (rcs) return rcs; }
     for (int k = 0; k < nvar; ++k) {
         Variant &v = h->v[k];
         if (use_block(h, v)) {
-            int rcw = ensure_block_ws(h);
+            int rcw = ensure_block_ws(h, lane);
             if (rcw) return rcw;
-            HIP_TRY(h, tmpc::launch_block(v.db, v.bargs, v.tiles, h->blk_ws.as<double>(), h->blk_blocks, k, io, &h->wc, h->stream));
+            HIP_TRY(h, tmpc::launch_block(v.db, v.bargs, v.tiles, lane.blk_ws.as<double>(), h->blk_blocks, k, io, &lane.wc, lane.stream));
             continue;
         }
-        HIP_TRY(h, tmpc::launch_solve(v.d, v.shape, k, io, ws ? ws[k] : nullptr, ws ? ws[k] : nullptr, &h->wc, h->n_cu, h->stream));
+        HIP_TRY(h, tmpc::launch_solve(v.d, v.shape, k, io, ws ? ws[k] : nullptr, ws ? ws[k] : nullptr, &lane.wc, h->n_cu, lane.stream));
     }
-    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev1, lane.stream));
     h->timed = true;
+    return TMPC_OK;
+}
+
+// A stream and a zeroed work-counter ring for a lane of the handle's device.
+int create_lane(tmpc_handle *h, Lane &lane) {
+    HIP_TRY(h, hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
+    lane.wc.size = 4096;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&lane.wc.ring), lane.wc.size * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemset(lane.wc.ring, 0, lane.wc.size * sizeof(unsigned long long)));
+    return TMPC_OK;
+}
+
+// Drops the records of the lane's calls that have finished (they finish in order).
+void prune_finished(Lane &lane) {
+    while (!lane.inflight.empty()) {
+        if (hipEventQuery(lane.inflight.front().end) != hipSuccess) { (void)hipGetLastError(); break; }     // (not ready is no error)
+        lane.inflight.pop_front();
+    }
+}
+
+bool conflicts_with_lane(const Lane &lane, const tmpc::CallRanges &call) {
+    for (const Lane::InFlight &f : lane.inflight)
+        if (tmpc::calls_conflict(f.touched, call)) return true;
+    return false;
+}
+
+// The lane of a tmpc_solve_batch_device call.  It goes to the other lane than the call before it when it has no RAW, WAW or WAR
+// overlap with the unfinished calls of that call's lane: it may then run beside them, and on its own lane it is ordered behind
+// whatever that lane holds.  Otherwise it stays on the lane of the call it conflicts with, behind it; if unfinished calls
+// of the other lane conflict with it as well, its lane first waits for that lane's latest end event.  The second lane is created
+// by the first call that finds unfinished, independent work to run beside.
+int pick_lane(tmpc_handle *h, const tmpc::CallRanges &call, Lane **out) {
+    *out = &h->lane[0];
+    if (!h->overlap) return TMPC_OK;
+    for (Lane &l : h->lane) prune_finished(l);
+    Lane &prev = h->lane[h->cur], &other = h->lane[1 - h->cur];
+    if (conflicts_with_lane(prev, call)) {
+        if (other.stream && conflicts_with_lane(other, call)) {
+            HIP_TRY(h, hipStreamWaitEvent(prev.stream, other.inflight.back().end, 0));
+            ++h->lane_waits;
+        }
+        *out = &prev;
+        return TMPC_OK;
+    }
+    if (!other.stream) {
+        if (prev.inflight.empty()) { *out = &prev; return TMPC_OK; }
+        if (const int rc = create_lane(h, other)) return rc;
+    }
+    *out = &other;
+    return TMPC_OK;
+}
+
+// Notes a tmpc_solve_batch_device call just enqueued on `lane` as in flight.  Its end event is the call's timing event; when that
+// one is, or will be, shared with other calls (the last of the 4096 pairs), one of the lane's spare events, recorded behind it.
+int note_in_flight(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call) {
+    hipEvent_t end = h->ev1;
+    if (h->pool_used >= 4096) {
+        while (lane.inflight.size() >= LANE_SPARE_EVENTS) {
+            HIP_TRY(h, hipEventSynchronize(lane.inflight.front().end));
+            lane.inflight.pop_front();
+        }
+        if (lane.spare.size() < LANE_SPARE_EVENTS) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            lane.spare.push_back(e);
+        }
+        end = lane.spare[lane.spare_next++ % LANE_SPARE_EVENTS];
+        HIP_TRY(h, hipEventRecord(end, lane.stream));
+    }
+    lane.inflight.push_back({call, end});
+    ++lane.calls;
+    h->cur = static_cast<int>(&lane - h->lane);
     return TMPC_OK;
 }
 
@@ -674,10 +799,8 @@ int setup_handle(tmpc_handle *h, const tmpc_problem &p, int device) {
         return TMPC_E_DEVICE;
     }
     h->n_cu = prop.multiProcessorCount;
-    HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->wc.size = 4096;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->wc.ring), h->wc.size * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemset(h->wc.ring, 0, h->wc.size * sizeof(unsigned long long)));
+    if (const int rc = create_lane(h, h->lane[0])) return rc;
+    h->stream = h->lane[0].stream;
     for (int i = 0; i < 256; ++i) {       // timing events are created up front, not in the solve path
         hipEvent_t a = nullptr, b = nullptr;
         HIP_TRY(h, hipEventCreate(&a));
@@ -766,6 +889,7 @@ int write_dump(const char *path, const Variant &v, std::initializer_list<std::pa
 int begin_loop(tmpc_handle *h, int64_t B) {
     h->rec = LoopRecords{};
     HIP_TRY(h, hipSetDevice(h->device));
+    if (const int rc = join_lanes(h)) return rc;
     return ensure_staging(h, B);
 }
 
@@ -823,15 +947,21 @@ void tmpc_destroy(tmpc_handle *h) {
         return;
     }
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer *b : {&h->blk_ws, &h->save, &h->ticks, &h->reg_zero, &h->stage_dev}) b->release();
+    for (Lane &l : h->lane)
+        if (l.stream) (void)hipStreamSynchronize(l.stream);
+    for (Lane &l : h->lane) {
+        for (DeviceBuffer *b : {&l.blk_ws, &l.save, &l.ticks}) b->release();
+        if (l.wc.ring) (void)hipFree(l.wc.ring);
+        for (hipEvent_t e : l.spare) (void)hipEventDestroy(e);
+    }
+    for (DeviceBuffer *b : {&h->reg_zero, &h->stage_dev}) b->release();
     h->arena.release();
     if (h->stage_pin) (void)hipHostFree(h->stage_pin);
-    if (h->wc.ring) (void)hipFree(h->wc.ring);
     for (int k = 0; k < 2; ++k)
         for (void *p : h->v[k].dev) (void)hipFree(p);
     for (auto &pr : h->pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    for (Lane &l : h->lane)
+        if (l.stream) (void)hipStreamDestroy(l.stream);
     delete h;
 }
 
@@ -843,13 +973,20 @@ int tmpc_solve_batch_device(tmpc_handle *h, int64_t B, const double *x_k, const 
         if (rz) return rz;
         ref = h->reg_zero.as<double>();
     }
-    return enqueue(h, {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters});
+    // (a regulator's reference is the handle's zero block, which nothing writes: not a range of the call)
+    const tmpc::CallRanges call = tmpc::solve_call_ranges(B, h->nx, h->nu, h->N, x_k, h->regulator ? nullptr : ref, variant, u_nom, x_nom0, xu_ss,
+                                                          x_nom, status, iters);
+    Lane *lane = nullptr;
+    if (const int rc = pick_lane(h, call, &lane)) return rc;
+    if (const int rc = enqueue(h, *lane, {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters})) return rc;
+    return h->overlap ? note_in_flight(h, *lane, call) : (++lane->calls, TMPC_OK);
 }
 
 int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
                      double *u_nom, double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters) {
     int rc = check_solve(h, "tmpc_solve_batch", B, x_k, ref, variant, u_nom, xu_ss, status, iters, true);
     if (rc || B == 0) return rc;
+    if ((rc = join_lanes(h))) return rc;
     if ((rc = ensure_staging(h, B))) return rc;
     if (h->regulator && (rc = ensure_reg_zero(h, B))) return rc;
     const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(B);
@@ -861,7 +998,7 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double 
         {h->off_st, status, b * sizeof(int32_t)}, {h->off_it, iters, b * sizeof(int32_t)}, {h->off_xn, x_nom, b * (N + 1) * nx * sizeof(double)}};
     char *const dev_in = h->stage_dev.p, *const dev_out = dev_in + h->stage_in_bytes;
     auto launch = [&]() {
-        return enqueue(h, {B, h->d_x, h->regulator ? h->reg_zero.as<double>() : h->d_r, variant ? h->d_var : nullptr, h->d_u, h->d_x0,
+        return enqueue(h, h->lane[0], {B, h->d_x, h->regulator ? h->reg_zero.as<double>() : h->d_r, variant ? h->d_var : nullptr, h->d_u, h->d_x0,
                            h->d_ss, x_nom ? h->d_xn : nullptr, h->d_st, h->d_it});
     };
     if (h->stage_pin != nullptr) {
@@ -875,7 +1012,7 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double 
         HIP_TRY(h, hipMemcpyAsync(dev_in, pin_in, in_bytes, hipMemcpyHostToDevice, h->stream));
         if ((rc = launch())) return rc;
         HIP_TRY(h, hipMemcpyAsync(pin_out, dev_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, sync_lanes(h));
         for (const auto &a : out)
             if (a.host) std::memcpy(a.host, pin_out + a.off, a.bytes);
         return TMPC_OK;
@@ -885,7 +1022,7 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double 
     if ((rc = launch())) return rc;
     for (const auto &a : out)
         if (a.host) HIP_TRY(h, hipMemcpyAsync(a.host, dev_out + a.off, a.bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sync_lanes(h));
     return TMPC_OK;
 }
 
@@ -985,11 +1122,12 @@ int tmpc_set_solve_timing(tmpc_handle *h, int on) {
 
 int tmpc_get_solve_ticks(tmpc_handle *h, int64_t B, int64_t *ticks) {
     if (!h || !ticks) return TMPC_E_INVALID;
-    if (!h->want_ticks || B != h->ticks_n || !h->ticks.p) { h->err = "tmpc_get_solve_ticks: no solve of this batch size was timed (tmpc_set_solve_timing)"; return TMPC_E_INVALID; }
+    const DeviceBuffer &tk = h->lane[h->ticks_lane].ticks;
+    if (!h->want_ticks || B != h->ticks_n || !tk.p) { h->err = "tmpc_get_solve_ticks: no solve of this batch size was timed (tmpc_set_solve_timing)"; return TMPC_E_INVALID; }
     static_assert(sizeof(long long) == sizeof(int64_t), "tick counts are 64-bit");
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(ticks, h->ticks.p, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, sync_lanes(h));
+    HIP_TRY(h, hipMemcpy(ticks, tk.p, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
 
@@ -997,7 +1135,7 @@ int tmpc_mc_get_solve_ticks(tmpc_handle *h, int64_t B, int64_t *ticks_sum, int64
     if (!h) return TMPC_E_INVALID;
     if (!h->rec.tick_sum || B != h->rec.tick_B) { h->err = "tmpc_mc_get_solve_ticks: the last tmpc_mc_run was not timed (tmpc_set_solve_timing) or had another batch size"; return TMPC_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sync_lanes(h));
     if (ticks_sum) HIP_TRY(h, hipMemcpy(ticks_sum, h->rec.tick_sum, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (ticks_max) HIP_TRY(h, hipMemcpy(ticks_max, h->rec.tick_max, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyDeviceToHost));
     return TMPC_OK;
@@ -1018,7 +1156,7 @@ int tmpc_mc_get_physics_error(tmpc_handle *h, int64_t B, double *err2_phys) {
     if (!h || !err2_phys) return TMPC_E_INVALID;
     if (!h->rec.err2_phys || B != h->rec.phys_B) { h->err = "tmpc_mc_get_physics_error: the last tmpc_mc_run had the linear plant or another batch size"; return TMPC_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sync_lanes(h));
     HIP_TRY(h, hipMemcpy(err2_phys, h->rec.err2_phys, static_cast<size_t>(B) * sizeof(double), hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
@@ -1153,8 +1291,8 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
         if (st.tick_sum) { h->rec.tick_sum = st.tick_sum; h->rec.tick_max = st.tick_max; h->rec.tick_B = B; }
         HIP_TRY(h, tmpc::launch_mc_pre(m, st, B, ref[0], h->stream));
         if (fuse || step_fuse) {
-            if (const int r2 = prepare_wave_scratch(h, B, step_fuse ? 2 : 1)) return r2;
-            st.ticks = h->want_ticks ? h->ticks.as<long long>() : nullptr;
+            if (const int r2 = prepare_wave_scratch(h, h->lane[0], B, step_fuse ? 2 : 1)) return r2;
+            st.ticks = h->want_ticks ? h->lane[0].ticks.as<long long>() : nullptr;
             mf.m = m; mf.st = st; mf.T = T;
             HIP_TRY(h, hipMemcpyAsync(d_mf, &mf, sizeof(mf), hipMemcpyHostToDevice, h->stream));
         }
@@ -1162,17 +1300,17 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
             // (Measured and dropped: the two launches of a step on two streams, so that the second one's workgroups start on the CUs the
             // first one's tail leaves idle -- config 4 extended 0.27 -> 0.28 s: the fork / join events of every step cost more.)
             for (int t = 0; t < T; ++t) {
-                if (const int r2 = begin_timed_launch(h)) return r2;
+                if (const int r2 = begin_timed_launch(h, h->lane[0])) return r2;
                 for (int k = 0; k < 2; ++k)
                     HIP_TRY(h, tmpc::launch_solve_mc_step(h->v[k].d, h->v[k].shape, k, B, gam[t & 1], h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[k],
-                                                          d_mf, t, gam[(t + 1) & 1], &h->wc, h->n_cu, h->stream));
+                                                          d_mf, t, gam[(t + 1) & 1], &h->lane[0].wc, h->n_cu, h->stream));
                 HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
             }
             h->timed = true;
             h->rec.fused = 2;
         } else if (fuse) {
-            if (const int r2 = begin_timed_launch(h)) return r2;          // (the launch counts in tmpc_kernel_ms_total like any solve launch)
-            HIP_TRY(h, tmpc::launch_solve_mc(h->v[0].d, h->v[0].shape, B, h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[0], d_mf, &h->wc, h->n_cu,
+            if (const int r2 = begin_timed_launch(h, h->lane[0])) return r2;          // (the launch counts in tmpc_kernel_ms_total like any solve launch)
+            HIP_TRY(h, tmpc::launch_solve_mc(h->v[0].d, h->v[0].shape, B, h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[0], d_mf, &h->lane[0].wc, h->n_cu,
                                              h->stream));
             HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
             h->timed = true;
@@ -1182,10 +1320,10 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
             // (round 3: mc_pre, the variant check, the solve, mc_post, mc_tube).  With injected packets nothing is solved.
             for (int t = 0; t < T; ++t) {
                 if (!rp) {
-                    const int r2 = enqueue(h, {B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it},
+                    const int r2 = enqueue(h, h->lane[0], {B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it},
                                            ws, true);
                     if (r2) return r2;
-                    st.ticks = h->want_ticks ? h->ticks.as<long long>() : nullptr;       // (allocated by the first enqueue)
+                    st.ticks = h->want_ticks ? h->lane[0].ticks.as<long long>() : nullptr;       // (allocated by the first enqueue)
                 }
                 HIP_TRY(h, tmpc::launch_mc_step(m, st, t, T, B, ref[t], ref[t + 1 < T ? t + 1 : t], h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it,
                                                 h->stream));
@@ -1201,11 +1339,11 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
         if (x_final) HIP_TRY(h, hipMemcpyAsync(x_final, st.x, b * nx * 8, hipMemcpyDeviceToHost, h->stream));
         if (consistent) HIP_TRY(h, hipMemcpyAsync(consistent, st.consistent, b * 8, hipMemcpyDeviceToHost, h->stream));
         if (iters_sum) HIP_TRY(h, hipMemcpyAsync(iters_sum, st.iters_sum, b * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, sync_lanes(h));
         return TMPC_OK;
     };
     rc = run();
-    if (rc != TMPC_OK) (void)hipStreamSynchronize(h->stream);
+    if (rc != TMPC_OK) (void)sync_lanes(h);
     return rc;
 }
 }  // namespace
@@ -1293,7 +1431,7 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
         if (want_cap) HIP_TRY(h, hipMemcpyAsync(st.cap_x, x0 + static_cast<size_t>(capture) * nx, 8 * nx, hipMemcpyHostToDevice, h->stream));
         // per step: the solve launch over all trajectories (x_k = the state, in place), then the step kernel
         for (int t = 0; t < T; ++t) {
-            if (const int r2 = enqueue(h, {B, st.x, h->reg_zero.as<double>(), nullptr, h->d_u, h->d_x0, nullptr, nullptr, h->d_st, h->d_it})) return r2;
+            if (const int r2 = enqueue(h, h->lane[0], {B, st.x, h->reg_zero.as<double>(), nullptr, h->d_u, h->d_x0, nullptr, nullptr, h->d_st, h->d_it})) return r2;
             HIP_TRY(h, tmpc::launch_reg_step(m, st, t, T, B, h->d_u, h->d_x0, h->d_st, h->d_it, h->stream));
         }
         if (cost) HIP_TRY(h, hipMemcpyAsync(cost, st.cost, 8 * b, hipMemcpyDeviceToHost, h->stream));
@@ -1306,19 +1444,48 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
             HIP_TRY(h, hipMemcpyAsync(cap_xn, st.cap_xn, 8 * t_ * nx, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, hipMemcpyAsync(cap_u, st.cap_u, 8 * t_ * nu, hipMemcpyDeviceToHost, h->stream));
         }
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, sync_lanes(h));
         return TMPC_OK;
     };
     rc = run();
-    if (rc != TMPC_OK) (void)hipStreamSynchronize(h->stream);
+    if (rc != TMPC_OK) (void)sync_lanes(h);
     return rc;
 }
 
 int tmpc_synchronize(tmpc_handle *h) {
     if (!h) return TMPC_E_INVALID;
     if (h->device < 0) return TMPC_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sync_lanes(h));
     return TMPC_OK;
+}
+
+int tmpc_set_call_overlap(tmpc_handle *h, int on) {
+    if (!h) return TMPC_E_INVALID;
+    if (h->device >= 0 && (on != 0) != (h->overlap != 0)) {
+        // off: the primary lane, which takes every call from here on, goes behind what the secondary lane holds; on: no call enqueued
+        // while it was off has a record, so the lanes start empty
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (on) HIP_TRY(h, sync_lanes(h));
+        else if (const int rc = join_lanes(h)) return rc;
+    }
+    h->overlap = on ? 1 : 0;
+    return TMPC_OK;
+}
+
+int tmpc_debug_lane_counters(tmpc_handle *h, int64_t *calls_per_lane, int64_t *cross_lane_waits, int reset) {
+    if (!h) return TMPC_E_INVALID;
+    if (calls_per_lane)
+        for (int k = 0; k < 2; ++k) calls_per_lane[k] = h->lane[k].calls;
+    if (cross_lane_waits) *cross_lane_waits = h->lane_waits;
+    if (reset) { h->lane[0].calls = h->lane[1].calls = 0; h->lane_waits = 0; }
+    return TMPC_OK;
+}
+
+int tmpc_debug_calls_conflict(int32_t nx, int32_t nu, int32_t N, int64_t B_a, const void *const *a, int64_t B_b, const void *const *b) {
+    if (!a || !b || nx <= 0 || nu <= 0 || N <= 0) return TMPC_E_INVALID;
+    const tmpc::CallRanges ra = tmpc::solve_call_ranges(B_a, nx, nu, N, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]);
+    const tmpc::CallRanges rb = tmpc::solve_call_ranges(B_b, nx, nu, N, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8]);
+    return tmpc::calls_conflict(ra, rb) ? 1 : 0;
 }
 
 int tmpc_last_kernel_ms(tmpc_handle *h, float *ms) {
@@ -1332,11 +1499,22 @@ int tmpc_last_kernel_ms(tmpc_handle *h, float *ms) {
 int tmpc_kernel_ms_total(tmpc_handle *h, float *total_ms, int32_t *launches, int reset) {
     if (!h) return TMPC_E_INVALID;
     if (h->device < 0) { h->err = "host-only handle"; return TMPC_E_DEVICE; }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sync_lanes(h));
+    // A call adds the time by which it extended the handle's busy period: from the later of its own start and the end of the
+    // busy period so far (`busy`: the call that ended last) to its own end.  Calls of one lane follow each other, so only a
+    // call on the other lane than `busy` can have started before that end.
     float sum = 0.f;
+    size_t busy = 0;
     for (size_t i = 0; i < h->pool_used; ++i) {
         float ms = 0.f;
         HIP_TRY(h, hipEventElapsedTime(&ms, h->pool[i].first, h->pool[i].second));
+        if (i > 0 && h->pool_lane[i] != h->pool_lane[busy]) {
+            float past = 0.f;
+            HIP_TRY(h, hipEventElapsedTime(&past, h->pool[busy].second, h->pool[i].second));
+            if (past <= 0.f) continue;          // ended inside the busy period: extends nothing
+            ms = std::min(ms, past);
+        }
+        busy = i;
         sum += ms;
     }
     if (total_ms) *total_ms = sum;
@@ -1348,7 +1526,7 @@ int tmpc_kernel_ms_total(tmpc_handle *h, float *total_ms, int32_t *launches, int
 #ifdef TMPC_STAMPS
 int tmpc_debug_stamps(tmpc_handle *h, int variant, long long *out12 /* [16] */) {
     if (!h || !out12) return TMPC_E_INVALID;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sync_lanes(h));
     const long long *src = use_block(h, h->v[variant]) ? h->v[variant].db.dbg : h->v[variant].d.dbg;
     HIP_TRY(h, hipMemcpy(out12, src, 16 * sizeof(long long), hipMemcpyDeviceToHost));
     return TMPC_OK;

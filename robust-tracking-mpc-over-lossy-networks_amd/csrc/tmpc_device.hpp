@@ -110,7 +110,7 @@ bool parks_in_lds(const KernelShape &shape);               // the hand-over iter
 
 // Work counters of the persistent grids (wave kernel and block kernel): every launch draws its instances from a fresh, zeroed device word of
 // a ring that is cleared in one piece when it has gone round -- no reset and no extra stream operation per launch.
-// Launches that share a ring must be ordered on one stream.
+// Launches that share a ring must be ordered on one stream: a handle keeps one ring per launch lane (tmpc_api.cpp).
 struct WorkCounter {
     unsigned long long *ring = nullptr;
     int size = 0, pos = 0;
