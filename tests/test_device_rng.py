@@ -44,6 +44,26 @@ def test_philox_realisations_layout_and_sharding():
     assert np.all(np.abs(wL.mean(axis=(0, 1))) < 0.01 * wb[:4])
 
 
+@pytest.mark.parametrize("nx", [12, 16])
+def test_philox_realisations_in_the_later_blocks(nx):
+    """nx = 12 and nx = 16: the disturbance reaches blocks j = 2, 3 (config 5) and 4 of a step, w_i = word (i + 2) & 3 of block
+    (i + 2) >> 2 -- every component against numpy's own generator over the same key and counter."""
+    wb = 0.05 * (1.0 + np.arange(nx))
+    nblk = (nx + 2 + 3) // 4
+    assert nblk == (4 if nx == 12 else 5)
+    th, ga, w = montecarlo.draw_realisations_philox(5, 8, wb, seed=123, first=9)
+    assert w.shape == (5, 8, nx)
+    for g, t in ((0, 1), (3, 7), (4, 2)):
+        # numpy increments the counter before it generates: counter t - 1 yields the block of step t
+        u = np.concatenate([np.random.Generator(np.random.Philox(key=[123, 9 + g], counter=[t - 1, j, 0, 0])).random(4) for j in range(nblk)])
+        assert th[g, t] == u[0] and ga[g, t] == u[1]
+        assert np.array_equal(w[g, t], wb * (2.0 * u[2:2 + nx] - 1.0))
+    # the words themselves, block by block, for a key beyond 32 bits
+    for j in range(nblk):
+        want = np.random.Philox(key=np.array([2 ** 40 + 5, 77], dtype=np.uint64), counter=[6, j, 0, 0]).random_raw(4)
+        assert np.array_equal(montecarlo.philox4x64(7, j, 2 ** 40 + 5, 77).reshape(4), want)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("extended", [False, True])
 def test_device_generator_equals_host_twin(hip_lib, extended):
