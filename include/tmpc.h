@@ -421,7 +421,66 @@ int tmpc_mc_set_device_rng(tmpc_handle *h, int on, uint64_t seed, int64_t first_
  */
 #define TMPC_PLANT_LINEAR   0
 #define TMPC_PLANT_CARTPOLE 1
+#define TMPC_PLANT_EXTERNAL 2   /* the caller's plant: set by a stepped session (tmpc_mc_open) only, refused by tmpc_mc_set_plant */
 int tmpc_mc_set_plant(tmpc_handle *h, int kind, const double *par7, int substeps);
+
+/*
+ * Stepped closed loop around a plant the CALLER owns: the per-trajectory state machines and the solve kernels of tmpc_mc_run,
+ * opened once, advanced ONE time step per call with the plant state given by the caller, and closed for the statistics.  For a
+ * plant that is neither the handle's linear model nor the closed-form cart-pole -- another mechanism, saturation or friction, a
+ * batched simulator on the device, a physics engine or hardware on the host.
+ *
+ * The cut: in the loop body the plant appears once, x_{t+1} = f(x_t, u_t) + w_t.  The estimator predicts from x_t / x_nom_t and
+ * u_t, the solve of step t reads x_hat_t, which step t-1 produced; so a step needs the caller's x_t only AFTER its solve (actuator,
+ * statistics, checks, estimator) and gives back u_t only.
+ *
+ * tmpc_mc_open(h, B, T, extended, p_loss, ref, th_u, ga_u, x0, HZ, hZ, rZ, HX, hX, rX, HU, hU, rU): HOST pointers, copied.
+ *        B, T          trajectories; the number of steps the session MAY take (ref, th_u, ga_u are sized by it)
+ *        p_loss, ref, th_u, ga_u, x0, HZ / hZ / rZ     as tmpc_mc_run; x, x_hat and x_nom start at x0 (NULL: zeros), the first
+ *                      packet always arrives.  With tmpc_mc_set_device_rng on, th_u / ga_u may be NULL: the loss uniforms are
+ *                      those of Philox block 0, exactly tmpc_mc_run's.
+ *        HX,hX  rX x nx, rX     optional check set for the caller's x_t   (rX = 0: none)
+ *        HU,hU  rU x nu, rU     optional check set for the applied u_t    (rU = 0: none); a step counts when a row is exceeded
+ *                      by more than 1e-7 (tmpc_reg_run's convention).
+ *   NO disturbance is ever drawn or added: w belongs to the caller's plant (draw_realisations_philox of the Python package
+ *   reproduces the library's w for a caller who wants it).  The session honours tmpc_mc_set_actuator, _set_warm_start,
+ *   _set_capture, tmpc_set_solve_timing and tmpc_set_kernel_path as set at open (no setter succeeds before close); it
+ *   ignores tmpc_mc_set_plant (and leaves that setting alone) and tmpc_mc_set_fused: every step is the solve launch(es) of tmpc_solve_batch -- one per problem -- and ONE launch of the state
+ *   machines, on the wave and on the block kernel path alike (the results do not depend on the launch form, see above).
+ *
+ * tmpc_mc_step_device(h, x_t, u_t, caller_stream): step t = the number of steps taken so far.  x_t (B*nx, read) and u_t (B*nu,
+ *   written: the applied input, 0 for an R-MPC trajectory that has stopped) are DEVICE pointers and may differ from call to call.
+ *   Returns without synchronising: no host synchronisation, no host<->device transfer, (number of problems + 1) kernel launches,
+ *   no copy.  caller_stream != NULL (a hipStream_t, e.g. torch.cuda.current_stream().cuda_stream): the step's state machines are
+ *   ordered behind the work already enqueued on that stream and the work enqueued on it afterwards is ordered behind the step,
+ *   by an event each way (hipEventRecord / hipStreamWaitEvent); the launches stay on the handle's stream.  The step's SOLVE does
+ *   not read x_t and is not ordered behind the caller's stream.  caller_stream == NULL: the caller synchronises on both sides
+ *   (x_t complete before the call, tmpc_synchronize before u_t is read) -- the contract of tmpc_solve_batch_device.
+ * tmpc_mc_step(h, x_t, u_t): the same with HOST pointers, one DMA each way through a pinned block; returns when u_t is in place
+ *   (a plant that lives on the host).
+ * tmpc_mc_close(h, err2, tube_viol, x_viol, u_viol, not_optimal, consistent, iters_sum, steps_done): synchronises and copies
+ *   out the per-trajectory statistics over the steps taken (semantics of tmpc_mc_run; x_viol / u_viol: steps with x_t outside X /
+ *   u_t outside U; steps_done: one int32); any pointer may be NULL.  There is no x_final: the caller has it.  After close
+ *   tmpc_mc_get_capture (with the T of open; rows of steps not taken are zero) and tmpc_mc_get_solve_ticks work as after a run.
+ *
+ * One session per handle.  tmpc_mc_open: TMPC_E_INVALID on a regulator handle or while a session is open, TMPC_E_DEVICE on a
+ * host-only handle.  While a session is open tmpc_solve_batch, tmpc_solve_batch_device, tmpc_mc_run, tmpc_mc_replay and
+ * tmpc_reg_run return TMPC_E_INVALID and leave the session intact (they would re-carve the memory it lives in); so does EVERY
+ * setter of the handle (tmpc_set_solve_timing, tmpc_set_kernel_path, tmpc_set_call_overlap, tmpc_mc_set_actuator, _set_plant,
+ * _set_capture, _set_device_rng, _set_warm_start, _set_fused): the session's arrays are carved for the settings of its open, and
+ * none changes under it -- choose them before tmpc_mc_open.  A step beyond T,
+ * and a step or a close without a session, return TMPC_E_INVALID.  A step that fails on the device ends the session: further
+ * steps return TMPC_E_INVALID, close is still allowed.  tmpc_destroy closes an open session; after close the handle behaves as
+ * before open.  R-MPC (TMPC_ACTUATOR_SMART): a trajectory whose solve is infeasible stops as in tmpc_mc_run (err2 NaN, counted
+ * once in not_optimal) and its u_t is 0 from that step on.  Added without an ABI bump: new exports, nothing else changed.
+ */
+int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const double *p_loss, const double *ref, const double *th_u,
+                 const double *ga_u, const double *x0, const double *HZ, const double *hZ, int32_t rZ, const double *HX,
+                 const double *hX, int32_t rX, const double *HU, const double *hU, int32_t rU);
+int tmpc_mc_step_device(tmpc_handle *h, const double *x_t, double *u_t, void *caller_stream);
+int tmpc_mc_step(tmpc_handle *h, const double *x_t, double *u_t);
+int tmpc_mc_close(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_viol, int32_t *u_viol, int32_t *not_optimal,
+                  double *consistent, int32_t *iters_sum, int32_t *steps_done);
 /*
  * With a nonlinear plant tmpc_mc_run also sums |x - ref|^2 over the T * substeps physics steps (the state at the start of
  * every physics step, i.e. x_traj[:, 0:-1] of results_nonlinear_system.py:361, whose tracking error is taken at 500 Hz);

@@ -213,6 +213,42 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         U = np.concatenate([out["u_nom"], u_ss[:, None, :]], axis=1)     # (B, N+1, nu)
         return np.ascontiguousarray(U.transpose(0, 2, 1)), out["x_nom0"], out["status"]
 
+    def open_closed_loop(self, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, extended: bool = False, X=None, U=None,
+                         warm_start: bool = False, capture=None, timing: bool = False, device_rng=None) -> "ClosedLoopSession":
+        """The closed loop of run_closed_loop around a plant of the CALLER's, one time step per call (include/tmpc.h:
+        tmpc_mc_open): `with mpc.open_closed_loop(...) as s: u = s.step(x) ...; stats = s.stats`.  The session runs the same
+        state machines and solves on the device; the caller gives x_t and gets the applied u_t back.  th_u / ga_u (B, T): the
+        loss uniforms (None with device_rng = (seed, first_trajectory[, ..])); no disturbance is drawn -- w is the plant's.
+        X, U: optional check sets for x_t / u_t (polytopes) -> x_violations, u_violations.  T: steps the session may take
+        (default len(ref)).  One session per controller at a time; nothing else may be solved with it until close()."""
+        from . import _native
+        if self._handle is None:
+            raise RuntimeError("setup_optimization() has not been called")
+        _native.mc_set_actuator(self._handle, self._smart_actuator)
+        info = _native.mc_open(self._handle, p_loss, ref, th_u, ga_u, x0=x0, T=T, Z=None if self._smart_actuator else self._Z,
+                               X=X, U=U, extended=extended, warm_start=warm_start, capture=capture, timing=timing,
+                               device_rng=device_rng)
+        return ClosedLoopSession(self, info)
+
+    def _run_closed_loop_around(self, plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng):
+        """run_closed_loop(plant=callable): a session driven by plant(x, u) -> x_plus on device tensors, + w[:, t] as the host loop adds it."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        ref = np.asarray(ref, dtype=np.float64).reshape(-1)
+        B, T, nx = int(np.asarray(p_loss).reshape(-1).shape[0]), ref.shape[0], self._nx
+        x = torch.zeros((B, nx), dtype=torch.float64, device=dev) if x0 is None else \
+            torch.as_tensor(np.asarray(x0, dtype=np.float64).reshape(B, nx), device=dev)
+        wd = None if w is None else torch.as_tensor(np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(B, T, nx).transpose(1, 0, 2)), device=dev)
+        with torch.cuda.device(dev):
+            with self.open_closed_loop(p_loss, ref, th_u, ga_u, x0=x0, T=T, extended=extended, warm_start=warm_start, capture=capture,
+                                       timing=timing, device_rng=device_rng) as s:
+                for t in range(T):
+                    xp = plant(x, s.step(x))
+                    x = (xp if wd is None else xp + wd[t]).contiguous()
+            out = s.stats
+            out["x_final"] = x.cpu().numpy()
+        return out
+
     def run_closed_loop(self, p_loss, ref, th_u=None, ga_u=None, w=None, x0=None, extended: bool = False, plant=None,
                         warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, fused=None) -> dict:
         """The lossy-network closed loop of the reference's Monte-Carlo scripts (results_linear_system.py:209-291)
@@ -225,10 +261,18 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         timing: per trajectory the mean / maximum device time of a solve (solve_time_mean, solve_time_max, seconds); the
         means are also appended to get_computational_times(), the list the scripts take their quantiles of (:305-315).
         device_rng = (seed, first_trajectory, w_bound): draw the realisations on the device instead of taking th_u, ga_u, w
-        (tmpc_mc_set_device_rng; montecarlo.draw_realisations_philox is the host twin)."""
+        (tmpc_mc_set_device_rng; montecarlo.draw_realisations_philox is the host twin).
+        plant: None / "linear" / "cartpole" -- the plants the library simulates itself; or a callable (x, u) -> x_plus on
+        float64 CUDA tensors (B, nx), (B, nu): any other plant, stepped through open_closed_loop (one call per time step; w[:, t],
+        if given, is added to x_plus; `fused` does not apply)."""
         from . import _native
         if self._handle is None:
             raise RuntimeError("setup_optimization() has not been called")
+        if callable(plant):
+            out = self._run_closed_loop_around(plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng)
+            if timing:
+                self._computational_times.extend(out["solve_time_mean"].tolist())
+            return out
         _native.mc_set_plant(self._handle, plant)        # None: the linear model; 'cartpole': the nonlinear cart-pole (RK4, 500 Hz)
         _native.mc_set_actuator(self._handle, self._smart_actuator)
         out = _native.mc_run(self._handle, p_loss, ref, th_u, ga_u, w, x0=x0, Z=None if self._smart_actuator else self._Z,
@@ -278,6 +322,64 @@ class TubeTrackingMPC(TubeRegulatorMPC):
             self._close()
         except Exception:
             pass
+
+
+class ClosedLoopSession:
+    """A stepped closed loop (TubeTrackingMPC.open_closed_loop; include/tmpc.h: tmpc_mc_open / _step / _close).  step(x) takes
+    the plant states x_t (B, nx) and returns the applied inputs u_t (B, nu):
+      a contiguous float64 CUDA tensor -> a CUDA tensor the session owns and REUSES every step (clone it to keep it), ordered on
+                                          torch's current stream: no synchronisation, the plant's kernels may follow at once;
+      a numpy array                    -> a numpy array, when the inputs are in place.
+    close() (or leaving the `with` block) ends the session and returns the statistics of run_closed_loop over the steps taken,
+    plus x_violations, u_violations and steps; they stay in .stats."""
+
+    def __init__(self, mpc, info: dict):
+        self._mpc, self._info = mpc, info
+        self._u = None               # the tensor u_t goes to
+        self._side = None            # a stream of the session's for callers on torch's default stream, which has no handle to wait on
+        self.stats = None
+        self.steps = 0
+
+    def step(self, x):
+        from . import _native
+        if self._info is None:
+            raise RuntimeError("the session is closed")
+        h = self._mpc._handle
+        B = self._info["B"]
+        if isinstance(x, np.ndarray):
+            u = _native.mc_step(h, self._info, x).reshape(B, h.nu)
+            self.steps += 1
+            return u
+        import torch
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.numel() == B * h.nx):
+            raise ValueError("step: x must be a numpy array or a contiguous float64 CUDA tensor of B * nx entries")
+        if self._u is None:
+            self._u = torch.empty((B, h.nu), dtype=torch.float64, device=x.device)
+        cur = torch.cuda.current_stream(x.device)
+        if cur.cuda_stream != 0:
+            _native.mc_step(h, self._info, x.data_ptr(), self._u.data_ptr(), cur.cuda_stream)
+        else:
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=x.device)
+            self._side.wait_stream(cur)
+            _native.mc_step(h, self._info, x.data_ptr(), self._u.data_ptr(), self._side.cuda_stream)
+            cur.wait_stream(self._side)
+        self.steps += 1
+        return self._u
+
+    def close(self) -> dict:
+        from . import _native
+        if self._info is not None:
+            info, self._info = self._info, None
+            self.stats = _native.mc_close(self._mpc._handle, info)
+        return self.stats
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 class ExtendedTubeTrackingMPC(TubeTrackingMPC):

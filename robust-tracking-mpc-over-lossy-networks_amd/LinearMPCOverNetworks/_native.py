@@ -120,6 +120,15 @@ def lib():
         L.tmpc_mc_last_fused.argtypes = [C.c_void_p]
         L.tmpc_mc_last_fused.restype = C.c_int
         L.tmpc_mc_run.restype = C.c_int
+        L.tmpc_mc_open.argtypes = ([C.c_void_p, C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 7 + [C.c_int32]
+                                   + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32])
+        L.tmpc_mc_open.restype = C.c_int
+        L.tmpc_mc_step_device.argtypes = [C.c_void_p] * 4
+        L.tmpc_mc_step_device.restype = C.c_int
+        L.tmpc_mc_step.argtypes = [C.c_void_p] * 3
+        L.tmpc_mc_step.restype = C.c_int
+        L.tmpc_mc_close.argtypes = [C.c_void_p] * 9
+        L.tmpc_mc_close.restype = C.c_int
         L.tmpc_mc_replay.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 8
         L.tmpc_mc_replay.restype = C.c_int
         L.tmpc_mc_set_actuator.argtypes = [C.c_void_p, C.c_int]
@@ -525,6 +534,107 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     out["tracking_error"] = np.sqrt(out["err2"]) / T
     out["consistent_estimate_error"] = float(out["consistent"].max()) if B else 0.0
     out["iters_mean"] = float(out["iters_sum"].sum()) / max(B * T, 1)            # interior-point iterations per solve
+    return out
+
+
+def _check_set(P, dim: int, who: str):
+    """(H, h, rows) of a check polytope, or (None, None, 0)."""
+    if P is None:
+        return None, None, 0
+    HA = np.ascontiguousarray(np.asarray(P.A, dtype=np.float64))
+    hb = np.ascontiguousarray(np.asarray(P.b, dtype=np.float64)).reshape(-1)
+    if HA.ndim != 2 or HA.shape[1] != dim or hb.size != HA.shape[0]:
+        raise ValueError(f"{who}: a check set has the wrong dimension")
+    return HA, hb, HA.shape[0]
+
+
+def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=None, X=None, U=None, extended: bool = False,
+            warm_start: bool = False, capture=None, timing: bool = False, device_rng=None) -> dict:
+    """include/tmpc.h: tmpc_mc_open -- opens the stepped closed loop around a plant of the caller's.  p_loss (B,), ref (T,),
+    th_u / ga_u (B, T) loss uniforms (None with device_rng = (seed, first_trajectory[, ignored]): Philox block 0, the draws of
+    mc_run), x0 (B, nx) or None; T: steps the session may take (default: len(ref)); Z / X / U: tube cross-section and the check
+    sets for x_t / u_t (polytopes or None).  No disturbance is drawn: w is the plant's.  Returns what mc_close needs."""
+    c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))      # noqa: E731
+    p_loss, ref = c(p_loss).reshape(-1), c(ref).reshape(-1)
+    B = p_loss.shape[0]
+    T = ref.shape[0] if T is None else int(T)
+    if ref.shape[0] < T:
+        raise ValueError("mc_open: ref must cover the T steps of the session")
+    for call, arg in ((lib().tmpc_set_solve_timing, int(bool(timing))), (lib().tmpc_mc_set_warm_start, int(bool(warm_start))),
+                      (lib().tmpc_mc_set_capture, -1 if capture is None else int(capture))):
+        if call(h.ptr, arg) != 0:
+            raise RuntimeError(h.error())
+    if device_rng is not None:
+        if lib().tmpc_mc_set_device_rng(h.ptr, 1, int(device_rng[0]), int(device_rng[1]), None) != 0:
+            raise RuntimeError(h.error())
+        th_u = ga_u = None
+    else:
+        if lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None) != 0:
+            raise RuntimeError(h.error())
+        th_u, ga_u = c(th_u), c(ga_u)
+        if th_u.shape != (B, T) or ga_u.shape != (B, T):
+            raise ValueError(f"mc_open: th_u and ga_u must be (B, T) = {(B, T)}")
+    x0c = None if x0 is None else c(x0).reshape(B, h.nx)
+    HZ, hZ, rZ = _check_set(Z, h.nx, "mc_open")
+    HX, hX, rX = _check_set(X, h.nx, "mc_open")
+    HU, hU, rU = _check_set(U, h.nu, "mc_open")
+    ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+    rc = lib().tmpc_mc_open(h.ptr, B, T, int(bool(extended)), ptr(p_loss), ptr(ref), ptr(th_u), ptr(ga_u), ptr(x0c),
+                            ptr(HZ), ptr(hZ), rZ, ptr(HX), ptr(hX), rX, ptr(HU), ptr(hU), rU)
+    if rc != 0:
+        raise RuntimeError(f"tmpc_mc_open failed ({rc}): {h.error()}")
+    return dict(B=B, T=T, capture=capture, timing=bool(timing))
+
+
+def mc_step(h: Handle, info: dict, x, u=None, stream=None):
+    """One step of the open session `info` = mc_open(...) describes.  x, u numpy (B, nx) / (B, nu): tmpc_mc_step, returns u when
+    u_t is in place.  x, u integers: DEVICE addresses of B * nx / B * nu doubles for tmpc_mc_step_device, with `stream` the
+    caller's hipStream_t as an integer (None / 0: the caller synchronises on both sides); returns without synchronising."""
+    if isinstance(x, np.ndarray):
+        B = info["B"]
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != B * h.nx:           # (the library copies B * nx entries out of x)
+            raise ValueError(f"mc_step: x must hold B * nx = {B * h.nx} entries, got {x.size}")
+        if u is None:
+            u = np.empty((B, h.nu))
+        if not (isinstance(u, np.ndarray) and u.dtype == np.float64 and u.flags.c_contiguous and u.size == B * h.nu):
+            raise ValueError("mc_step: u must be a contiguous float64 array of B * nu entries")
+        rc = lib().tmpc_mc_step(h.ptr, x.ctypes.data, u.ctypes.data)
+    else:
+        rc = lib().tmpc_mc_step_device(h.ptr, int(x), int(u), int(stream) if stream else None)
+    if rc != 0:
+        raise RuntimeError(f"tmpc_mc_step failed ({rc}): {h.error()}")
+    return u
+
+
+def mc_close(h: Handle, info: dict) -> dict:
+    """include/tmpc.h: tmpc_mc_close -- ends the session `info` = mc_open(...) describes and returns its statistics over the
+    steps taken: the keys of mc_run (without x_final: the caller has it) plus x_violations, u_violations, steps."""
+    B, T = info["B"], info["T"]
+    out = dict(err2=np.empty(B), tube_violations=np.empty(B, np.int32), x_violations=np.empty(B, np.int32),
+               u_violations=np.empty(B, np.int32), not_optimal=np.empty(B, np.int32), consistent=np.empty(B),
+               iters_sum=np.empty(B, np.int32))
+    steps = C.c_int32(0)
+    rc = lib().tmpc_mc_close(h.ptr, *[out[k].ctypes.data for k in ("err2", "tube_violations", "x_violations", "u_violations",
+                                                                   "not_optimal", "consistent", "iters_sum")], C.addressof(steps))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_mc_close failed ({rc}): {h.error()}")
+    n = out["steps"] = int(steps.value)
+    if info.get("capture") is not None:
+        xt, xn, ut = np.empty((T, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))
+        if lib().tmpc_mc_get_capture(h.ptr, T, xt.ctypes.data, xn.ctypes.data, ut.ctypes.data) != 0:
+            raise RuntimeError(h.error())
+        out["x_traj"], out["x_nom_traj"], out["u_traj"] = xt[:n], xn[:n], ut[:n]
+    if info.get("timing"):
+        tsum, tmax = np.empty(B, np.int64), np.empty(B, np.int64)
+        if lib().tmpc_mc_get_solve_ticks(h.ptr, B, tsum.ctypes.data, tmax.ctypes.data) != 0:
+            raise RuntimeError(h.error())
+        out["solve_time_mean"], out["solve_time_max"] = tsum * (TICK_SECONDS / max(n, 1)), tmax * TICK_SECONDS
+    out["loop_mode"] = 0          # solve launches + a state-machine launch per step
+    out["fused"] = False
+    out["tracking_error"] = np.sqrt(out["err2"]) / max(n, 1)
+    out["consistent_estimate_error"] = float(out["consistent"].max()) if B else 0.0
+    out["iters_mean"] = float(out["iters_sum"].sum()) / max(B * n, 1)
     return out
 
 

@@ -143,6 +143,22 @@ struct Lane {
 };
 constexpr size_t LANE_SPARE_EVENTS = 64;
 
+// The stepped closed loop of a handle (tmpc_mc_open .. tmpc_mc_close): the records of tmpc_mc_run, whose arrays live in the loop
+// arena until the next loop carves it -- which is why the other entry points refuse to run while `open`.
+struct McSession {
+    bool open = false, failed = false;   // failed: a step did not go through on the device; only close is left
+    int64_t B = 0;
+    int T = 0, t = 0, extended = 0;      // steps allowed / taken
+    tmpc::McModel m{};
+    tmpc::McState st{};
+    tmpc::McExternal ext{};              // (x_t / u_t: the device staging of tmpc_mc_step; a device-pointer step brings its own)
+    int32_t *ws[2] = {nullptr, nullptr}; // warm start: working sets per problem
+    bool warm = false;
+    std::vector<double> ref;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;     // caller's stream -> handle's stream, and back
+    char *pin = nullptr;                 // pinned host block [x_t | u_t] of tmpc_mc_step (nullptr: copies from / to the caller's memory)
+};
+
 struct Variant {
     tmpc::Condensed c;
     tmpc::DeviceQP d{};
@@ -212,6 +228,7 @@ struct tmpc_handle {
     // left in it
     Arena arena;
     LoopRecords rec;
+    McSession ses;
 };
 
 namespace {
@@ -849,6 +866,7 @@ int create_handle(const char *who, int nx, int nu, int N, int device, tmpc_handl
 int check_solve(tmpc_handle *h, const char *who, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
                 const double *u_nom, const double *xu_ss, const int32_t *status, const int32_t *iters, bool variant_range) {
     if (!h) return TMPC_E_INVALID;
+    if (h->ses.open) { h->err = std::string(who) + ": a stepped closed loop is open on this handle (tmpc_mc_close first)"; return TMPC_E_INVALID; }
     if (B < 0 || !x_k || (!ref && !h->regulator) || !u_nom || !status || !iters) { h->err = std::string(who) + ": NULL argument"; return TMPC_E_INVALID; }
     if (h->regulator && (xu_ss || variant)) {
         h->err = std::string(who) + ": a regulator handle has no steady state and one problem (xu_ss, variant must be NULL)";
@@ -884,6 +902,15 @@ int write_dump(const char *path, const Variant &v, std::initializer_list<std::pa
     return TMPC_OK;
 }
 
+// What a stepped loop holds beyond the arena: its events and its pinned block.  The caller has synchronised.
+void release_session(tmpc_handle *h) {
+    McSession &s = h->ses;
+    if (s.ev_in) (void)hipEventDestroy(s.ev_in);
+    if (s.ev_out) (void)hipEventDestroy(s.ev_out);
+    if (s.pin) (void)hipHostFree(s.pin);
+    s = McSession{};
+}
+
 // Common start of the closed loops: what the last run left in the arena is unreadable from here on (tmpc_mc_get_capture /
 // _solve_ticks / _physics_error must not read a freed or half-written arena); the staging block's outputs take the solves'.
 int begin_loop(tmpc_handle *h, int64_t B) {
@@ -891,6 +918,14 @@ int begin_loop(tmpc_handle *h, int64_t B) {
     HIP_TRY(h, hipSetDevice(h->device));
     if (const int rc = join_lanes(h)) return rc;
     return ensure_staging(h, B);
+}
+
+// A stepped loop runs under the handle's settings as they were at tmpc_mc_open (its arrays are carved for them): no setter changes
+// one under it.  True, with the message, while a session is open.
+bool session_bars(tmpc_handle *h, const char *who) {
+    if (!h->ses.open) return false;
+    h->err = std::string(who) + ": a stepped closed loop is open on this handle (tmpc_mc_close first)";
+    return true;
 }
 
 }  // namespace
@@ -949,6 +984,7 @@ void tmpc_destroy(tmpc_handle *h) {
     (void)hipSetDevice(h->device);
     for (Lane &l : h->lane)
         if (l.stream) (void)hipStreamSynchronize(l.stream);
+    release_session(h);                  // (an open stepped loop ends here: its arrays go with the arena below)
     for (Lane &l : h->lane) {
         for (DeviceBuffer *b : {&l.blk_ws, &l.save, &l.ticks}) b->release();
         if (l.wc.ring) (void)hipFree(l.wc.ring);
@@ -1028,6 +1064,7 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double 
 
 int tmpc_set_kernel_path(tmpc_handle *h, int path) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_set_kernel_path")) return TMPC_E_INVALID;
     if (path != TMPC_PATH_AUTO && path != TMPC_PATH_WAVE && path != TMPC_PATH_BLOCK) { h->err = "tmpc_set_kernel_path: unknown path"; return TMPC_E_INVALID; }
     for (int k = 0; k < h->nvariants; ++k) {
         if (path == TMPC_PATH_WAVE && !h->v[k].wave_ok && h->device >= 0) { h->err = "tmpc_set_kernel_path: no wave-per-QP shape covers this problem"; return TMPC_E_UNSUPPORTED; }
@@ -1074,6 +1111,7 @@ const char *tmpc_kernel_name(const tmpc_handle *h, int variant) {
 
 int tmpc_mc_set_actuator(tmpc_handle *h, int kind) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_actuator")) return TMPC_E_INVALID;
     if (kind != TMPC_ACTUATOR_CONSISTENT && kind != TMPC_ACTUATOR_SMART) { h->err = "tmpc_mc_set_actuator: unknown actuator"; return TMPC_E_INVALID; }
     h->actuator = kind;
     return TMPC_OK;
@@ -1081,6 +1119,7 @@ int tmpc_mc_set_actuator(tmpc_handle *h, int kind) {
 
 int tmpc_mc_set_plant(tmpc_handle *h, int kind, const double *par7, int substeps) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_plant")) return TMPC_E_INVALID;
     if (kind == TMPC_PLANT_LINEAR) { h->plant = kind; return TMPC_OK; }
     if (kind != TMPC_PLANT_CARTPOLE || !par7 || substeps < 1) { h->err = "tmpc_mc_set_plant: unknown plant or missing parameters"; return TMPC_E_INVALID; }
     if (h->nx != 4 || h->nu != 1) { h->err = "tmpc_mc_set_plant: the cart-pole plant needs nx = 4, nu = 1"; return TMPC_E_INVALID; }
@@ -1092,6 +1131,7 @@ int tmpc_mc_set_plant(tmpc_handle *h, int kind, const double *par7, int substeps
 
 int tmpc_mc_set_capture(tmpc_handle *h, int64_t index) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_capture")) return TMPC_E_INVALID;
     h->mc_capture = index < 0 ? -1 : index;
     return TMPC_OK;
 }
@@ -1115,6 +1155,7 @@ int tmpc_mc_get_capture(tmpc_handle *h, int32_t T, double *x_traj, double *x_nom
 
 int tmpc_set_solve_timing(tmpc_handle *h, int on) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_set_solve_timing")) return TMPC_E_INVALID;
     h->want_ticks = on ? 1 : 0;
     if (!on) h->ticks_n = 0;
     return TMPC_OK;
@@ -1143,6 +1184,7 @@ int tmpc_mc_get_solve_ticks(tmpc_handle *h, int64_t B, int64_t *ticks_sum, int64
 
 int tmpc_mc_set_device_rng(tmpc_handle *h, int on, uint64_t seed, int64_t first_trajectory, const double *w_bound) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_device_rng")) return TMPC_E_INVALID;
     h->mc_rng_on = on ? 1 : 0;
     h->mc_rng_seed = seed;
     h->mc_rng_first = first_trajectory;
@@ -1163,12 +1205,14 @@ int tmpc_mc_get_physics_error(tmpc_handle *h, int64_t B, double *err2_phys) {
 
 int tmpc_mc_set_warm_start(tmpc_handle *h, int on) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_warm_start")) return TMPC_E_INVALID;
     h->mc_warm = on ? 1 : 0;
     return TMPC_OK;
 }
 
 int tmpc_mc_set_fused(tmpc_handle *h, int mode) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_fused")) return TMPC_E_INVALID;
     if (mode != TMPC_MC_FUSED_OFF && mode != TMPC_MC_FUSED_ON && mode != TMPC_MC_FUSED_AUTO) { h->err = "tmpc_mc_set_fused: mode is TMPC_MC_FUSED_OFF / _ON / _AUTO"; return TMPC_E_INVALID; }
     h->mc_fused = mode;
     return TMPC_OK;
@@ -1191,6 +1235,7 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
                 int32_t rZ, double *err2, int32_t *tube_viol, int32_t *not_optimal, double *x_final, double *consistent,
                 int32_t *iters_sum, const McReplay *rp) {
     if (!h) return TMPC_E_INVALID;
+    if (h->ses.open) { h->err = "tmpc_mc_run: a stepped closed loop is open on this handle (tmpc_mc_close first)"; return TMPC_E_INVALID; }
     const bool host_draws = rp != nullptr || !h->mc_rng_on;
     if (B < 0 || T < 0 || !p_loss || !ref || (host_draws && (!th_u || !ga_u || !w)) || (rZ > 0 && (!HZ || !hZ))) { h->err = "tmpc_mc_run: NULL argument"; return TMPC_E_INVALID; }
     if (h->regulator) { h->err = "tmpc_mc_run: a regulator handle runs its loop with tmpc_reg_run"; return TMPC_E_INVALID; }
@@ -1377,6 +1422,7 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
                  double *cost, int32_t *x_viol, int32_t *u_viol, int32_t *tube_viol, int32_t *not_optimal, int32_t *fail_step,
                  double *x_final, int32_t *iters_sum, int64_t capture, double *cap_x, double *cap_xn, double *cap_u) {
     if (!h) return TMPC_E_INVALID;
+    if (h->ses.open) { h->err = "tmpc_reg_run: a stepped closed loop is open on this handle (tmpc_mc_close first)"; return TMPC_E_INVALID; }
     if (!h->regulator) { h->err = "tmpc_reg_run: needs a regulator handle (tmpc_create_regulator); tracking handles run tmpc_mc_run"; return TMPC_E_INVALID; }
     if (B < 0 || T < 0 || !x0 || rX < 0 || rU < 0 || rZ < 0 || (rX > 0 && (!HX || !hX)) || (rU > 0 && (!HU || !hU)) || (rZ > 0 && (!HZ || !hZ))) {
         h->err = "tmpc_reg_run: NULL argument or negative count";
@@ -1452,6 +1498,203 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
     return rc;
 }
 
+int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const double *p_loss, const double *ref, const double *th_u,
+                 const double *ga_u, const double *x0, const double *HZ, const double *hZ, int32_t rZ, const double *HX,
+                 const double *hX, int32_t rX, const double *HU, const double *hU, int32_t rU) {
+    if (!h) return TMPC_E_INVALID;
+    if (h->ses.open) { h->err = "tmpc_mc_open: a stepped closed loop is already open on this handle (one session per handle)"; return TMPC_E_INVALID; }
+    if (h->regulator) { h->err = "tmpc_mc_open: a regulator handle has no stepped loop"; return TMPC_E_INVALID; }
+    const bool host_draws = !h->mc_rng_on;
+    if (B <= 0 || T <= 0 || rZ < 0 || rX < 0 || rU < 0) { h->err = "tmpc_mc_open: need B > 0, T > 0 and row counts >= 0"; return TMPC_E_INVALID; }
+    if (!p_loss || !ref || (host_draws && (!th_u || !ga_u)) || (rZ > 0 && (!HZ || !hZ)) || (rX > 0 && (!HX || !hX)) || (rU > 0 && (!HU || !hU))) {
+        h->err = "tmpc_mc_open: NULL argument";
+        return TMPC_E_INVALID;
+    }
+    if (extended && h->nvariants < 2) { h->err = "tmpc_mc_open: extended loop needs a problem created with extended = 1"; return TMPC_E_INVALID; }
+    if (h->hK.empty() || h->hKanc.empty()) { h->err = "tmpc_mc_open: the problem description carries no gains K / K_anc"; return TMPC_E_INVALID; }
+    if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
+    if (h->nu > 16) { h->err = "tmpc_mc_open: nu <= 16"; return TMPC_E_UNSUPPORTED; }
+    int rc = begin_loop(h, B);
+    if (rc) return rc;
+    const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(B), t_ = static_cast<size_t>(T);
+    McSession &s = h->ses;
+    auto open = [&]() -> int {
+        tmpc::McModel &m = s.m;
+        tmpc::McState &st = s.st;
+        tmpc::McExternal &ext = s.ext;
+        m.nx = h->nx; m.nu = h->nu; m.N = h->N; m.extended = extended ? 1 : 0; m.rZ = rZ;
+        m.plant = TMPC_PLANT_EXTERNAL; m.substeps = 1; m.smart = h->actuator == TMPC_ACTUATOR_SMART ? 1 : 0;
+        ext.rX = rX; ext.rU = rU;
+        // the pieces of mc_run_impl without a plant state's disturbance, plus the caller's sets, counters and the staging of tmpc_mc_step
+        Arena &a = h->arena;
+        a.piece(&m.A, nx * nx * 8, h->hA.data());
+        a.piece(&m.B, nx * nu * 8, h->hB.data());
+        a.piece(&m.K, nu * nx * 8, h->hK.data());
+        a.piece(&m.K_anc, nu * nx * 8, h->hKanc.data());
+        a.piece(&m.HZ, static_cast<size_t>(rZ) * nx * 8, HZ);
+        a.piece(&m.hZ, static_cast<size_t>(rZ) * 8, hZ);
+        a.piece(&ext.HX, static_cast<size_t>(rX) * nx * 8, HX);
+        a.piece(&ext.hX, static_cast<size_t>(rX) * 8, hX);
+        a.piece(&ext.HU, static_cast<size_t>(rU) * nu * 8, HU);
+        a.piece(&ext.hU, static_cast<size_t>(rU) * 8, hU);
+        a.piece(&st.p_loss, b * 8, p_loss);
+        if (host_draws) {
+            a.piece(&st.th_u, b * t_ * 8, th_u);
+            a.piece(&st.ga_u, b * t_ * 8, ga_u);
+        } else {
+            st.rng_on = 1;
+            st.rng_seed = h->mc_rng_seed;
+            st.rng_first = h->mc_rng_first;
+        }
+        // (st.x is carried for the record's sake: the state machines of a session never read or write it)
+        for (double **x : {&st.x, &st.x_hat, &st.x_nom}) a.piece(x, b * nx * 8, x0, 0);
+        a.piece(&st.Ubuf, b * (N + 1) * nu * 8, nullptr, 0);
+        a.piece(&st.u_latest0, b * nu * 8, nullptr, 0);
+        for (double **x : {&st.x_nom0_latest, &st.ref_k}) a.piece(x, b * nx * 8, nullptr, 0);
+        for (double **x : {&st.err2, &st.consistent}) a.piece(x, b * 8, nullptr, 0);
+        for (int32_t **c : {&st.q_est, &st.q_act, &st.s, &st.Theta, &st.last_lost, &st.tube_viol, &st.not_optimal, &st.iters_sum, &ext.x_viol, &ext.u_viol})
+            a.piece(c, b * 4, nullptr, c == &st.last_lost ? 0xFF : 0);
+        a.piece(&st.gamma, b, nullptr, 1);
+        a.piece(&st.dead, b, nullptr, 0);
+        st.cap_index = -1;
+        if (h->mc_capture >= 0 && h->mc_capture < B) {
+            a.piece(&st.cap, t_ * (2 * nx + nu) * 8, nullptr, 0);
+            st.cap_index = h->mc_capture;
+        }
+        if (h->want_ticks) {
+            a.piece(&st.tick_sum, b * 8, nullptr, 0);
+            a.piece(&st.tick_max, b * 8, nullptr, 0);
+        }
+        s.warm = h->mc_warm != 0;
+        if (s.warm)
+            for (int k = 0; k < (extended ? 2 : 1); ++k) a.piece(&s.ws[k], b * tmpc::WS_STRIDE * 4, nullptr, 0);
+        double *x_stage = nullptr, *u_stage = nullptr;
+        a.piece(&x_stage, b * nx * 8, nullptr, 0);
+        a.piece(&u_stage, b * nu * 8, nullptr, 0);
+        HIP_TRY(h, a.carve(h->stream));
+        ext.x_t = x_stage;
+        ext.u_t = u_stage;
+        HIP_TRY(h, tmpc::launch_mc_pre(m, st, B, ref[0], h->stream));
+        HIP_TRY(h, hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
+        // (the pinned block is a convenience: without it tmpc_mc_step copies from / to the caller's memory)
+        if (hipHostMalloc(reinterpret_cast<void **>(&s.pin), b * (nx + nu) * 8, hipHostMallocDefault) != hipSuccess) {
+            s.pin = nullptr;
+            (void)hipGetLastError();
+        }
+        HIP_TRY(h, sync_lanes(h));       // the uploads read the caller's arrays, which are theirs again from here on
+        return TMPC_OK;
+    };
+    rc = open();
+    if (rc != TMPC_OK) {
+        (void)sync_lanes(h);
+        release_session(h);
+        return rc;
+    }
+    s.ref.assign(ref, ref + T);
+    s.B = B; s.T = T; s.t = 0; s.extended = extended ? 1 : 0;
+    s.open = true;
+    return TMPC_OK;
+}
+
+namespace {
+// One step of the open session on the handle's stream: the solve launch(es) on x_hat_t, then -- behind `caller` (a stream, or
+// nullptr) -- the state machines around the given x_t / u_t.
+int session_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t, hipStream_t caller) {
+    McSession &s = h->ses;
+    if (!s.open) { h->err = std::string(who) + ": no stepped closed loop is open on this handle (tmpc_mc_open)"; return TMPC_E_INVALID; }
+    if (s.failed) { h->err = std::string(who) + ": an earlier step of the session failed on the device; only tmpc_mc_close is left"; return TMPC_E_INVALID; }
+    if (!x_t || !u_t) { h->err = std::string(who) + ": NULL argument"; return TMPC_E_INVALID; }
+    if (s.t >= s.T) { h->err = std::string(who) + ": the session was opened for T steps and has taken them"; return TMPC_E_INVALID; }
+    auto step = [&]() -> int {
+        HIP_TRY(h, hipSetDevice(h->device));
+        tmpc::McState &st = s.st;
+        if (const int rc = enqueue(h, h->lane[0], {s.B, st.x_hat, st.ref_k, s.extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it},
+                                   s.warm ? s.ws : nullptr, true))
+            return rc;
+        st.ticks = st.tick_sum ? h->lane[0].ticks.as<long long>() : nullptr;       // (timed at open; allocated by the first enqueue)
+        // the solve did not need x_t; the state machines do
+        if (caller) {
+            HIP_TRY(h, hipEventRecord(s.ev_in, caller));
+            HIP_TRY(h, hipStreamWaitEvent(h->stream, s.ev_in, 0));
+        }
+        tmpc::McExternal ext = s.ext;
+        ext.x_t = x_t;
+        ext.u_t = u_t;
+        const int t = s.t;
+        HIP_TRY(h, tmpc::launch_mc_step_external(s.m, st, ext, t, s.T, s.B, s.ref[t], s.ref[t + 1 < s.T ? t + 1 : t], h->d_u, h->d_x0, h->d_ss,
+                                                 h->d_st, h->d_it, h->stream));
+        if (caller) {
+            HIP_TRY(h, hipEventRecord(s.ev_out, h->stream));
+            HIP_TRY(h, hipStreamWaitEvent(caller, s.ev_out, 0));
+        }
+        return TMPC_OK;
+    };
+    const int rc = step();
+    if (rc != TMPC_OK) s.failed = true;
+    else ++s.t;
+    return rc;
+}
+}  // namespace
+
+int tmpc_mc_step_device(tmpc_handle *h, const double *x_t, double *u_t, void *caller_stream) {
+    if (!h) return TMPC_E_INVALID;
+    return session_step(h, "tmpc_mc_step_device", x_t, u_t, static_cast<hipStream_t>(caller_stream));
+}
+
+int tmpc_mc_step(tmpc_handle *h, const double *x_t, double *u_t) {
+    if (!h) return TMPC_E_INVALID;
+    McSession &s = h->ses;
+    if (!s.open || s.failed || !x_t || !u_t || s.t >= s.T) return session_step(h, "tmpc_mc_step", x_t, u_t, nullptr);     // (its message and code)
+    const size_t xb = static_cast<size_t>(s.B) * h->nx * 8, ub = static_cast<size_t>(s.B) * h->nu * 8;
+    double *const d_x = const_cast<double *>(s.ext.x_t), *const d_u = s.ext.u_t;
+    auto copies = [&](bool in) -> int {
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (in) {
+            if (s.pin) std::memcpy(s.pin, x_t, xb);
+            HIP_TRY(h, hipMemcpyAsync(d_x, s.pin ? static_cast<const void *>(s.pin) : x_t, xb, hipMemcpyHostToDevice, h->stream));
+        } else {
+            HIP_TRY(h, hipMemcpyAsync(s.pin ? static_cast<void *>(s.pin + xb) : u_t, d_u, ub, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, sync_lanes(h));
+            if (s.pin) std::memcpy(u_t, s.pin + xb, ub);
+        }
+        return TMPC_OK;
+    };
+    int rc = copies(true);
+    if (rc == TMPC_OK) rc = session_step(h, "tmpc_mc_step", d_x, d_u, nullptr);
+    if (rc == TMPC_OK) rc = copies(false);
+    if (rc != TMPC_OK) { s.failed = true; (void)sync_lanes(h); }
+    return rc;
+}
+
+int tmpc_mc_close(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_viol, int32_t *u_viol, int32_t *not_optimal,
+                  double *consistent, int32_t *iters_sum, int32_t *steps_done) {
+    if (!h) return TMPC_E_INVALID;
+    McSession &s = h->ses;
+    if (!s.open) { h->err = "tmpc_mc_close: no stepped closed loop is open on this handle (tmpc_mc_open)"; return TMPC_E_INVALID; }
+    const size_t b = static_cast<size_t>(s.B);
+    auto close = [&]() -> int {
+        HIP_TRY(h, hipSetDevice(h->device));
+        const tmpc::McState &st = s.st;
+        if (err2) HIP_TRY(h, hipMemcpyAsync(err2, st.err2, b * 8, hipMemcpyDeviceToHost, h->stream));
+        if (consistent) HIP_TRY(h, hipMemcpyAsync(consistent, st.consistent, b * 8, hipMemcpyDeviceToHost, h->stream));
+        const struct { int32_t *host; const int32_t *dev; } counters[] = {
+            {tube_viol, st.tube_viol}, {x_viol, s.ext.x_viol}, {u_viol, s.ext.u_viol}, {not_optimal, st.not_optimal}, {iters_sum, st.iters_sum}};
+        for (const auto &c : counters)
+            if (c.host) HIP_TRY(h, hipMemcpyAsync(c.host, c.dev, b * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, sync_lanes(h));
+        return TMPC_OK;
+    };
+    const int rc = close();
+    if (rc != TMPC_OK) (void)sync_lanes(h);
+    if (steps_done) *steps_done = s.t;
+    // what the getters read, as after a run (the arena stays as it is until the next loop)
+    if (rc == TMPC_OK && s.st.cap) { h->rec.cap = s.st.cap; h->rec.cap_T = s.T; }
+    if (rc == TMPC_OK && s.st.tick_sum) { h->rec.tick_sum = s.st.tick_sum; h->rec.tick_max = s.st.tick_max; h->rec.tick_B = s.B; }
+    release_session(h);
+    return rc;
+}
+
 int tmpc_synchronize(tmpc_handle *h) {
     if (!h) return TMPC_E_INVALID;
     if (h->device < 0) return TMPC_OK;
@@ -1461,6 +1704,7 @@ int tmpc_synchronize(tmpc_handle *h) {
 
 int tmpc_set_call_overlap(tmpc_handle *h, int on) {
     if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_set_call_overlap")) return TMPC_E_INVALID;
     if (h->device >= 0 && (on != 0) != (h->overlap != 0)) {
         // off: the primary lane, which takes every call from here on, goes behind what the secondary lane holds; on: no call enqueued
         // while it was off has a record, so the lanes start empty

@@ -177,11 +177,24 @@ struct McState {                         // all [trajectory]-major device arrays
     double *trace_f;                          // [B][T][3 nx + nu]: x_{t+1}, x_hat_{t+1}, nominal state of the plant's packet, u_t; or nullptr
     int32_t *trace_i;                         // [B][T][3]: s_t, Theta_t, q_t (the controller's packet)
 };
+// The caller's side of the stepped closed loop (tmpc_mc_open / tmpc_mc_step_device, m.plant = TMPC_PLANT_EXTERNAL): the plant
+// state of this step comes from the caller and the applied input goes back; X and U are the caller's check sets for the two.
+struct McExternal {
+    const double *x_t;                   // plant state of the step, given by the caller                       [B][nx]
+    double *u_t;                         // applied input of the step (0 for a stopped trajectory), for the caller [B][nu]
+    int rX, rU;                          // rows of the check sets (0: no check)
+    const double *HX, *hX, *HU, *hU;
+    int32_t *x_viol, *u_viol;            // steps with x_t outside X / u_t outside U                           [B]
+};
 hipError_t launch_mark_invalid_variants(const BatchIO &io, int nvariants, int nx, int nu, int N, hipStream_t stream);
 // one launch before the first solve (reference of step 0), then one launch per time step after the solve launch(es)
 hipError_t launch_mc_pre(const McModel &m, const McState &st, int64_t B, double ref_0, hipStream_t stream);
 hipError_t launch_mc_step(const McModel &m, const McState &st, int t, int T, int64_t B, double ref_t, double ref_next, const double *u_nom,
                           const double *x_nom0, const double *xu_ss, const int32_t *status, const int32_t *iters, hipStream_t stream);
+// one time step of the stepped loop: the state machines around the caller's x_t / u_t, behind the solve launch(es) of the step
+hipError_t launch_mc_step_external(const McModel &m, const McState &st, const McExternal &ext, int t, int T, int64_t B, double ref_t,
+                                   double ref_next, const double *u_nom, const double *x_nom0, const double *xu_ss, const int32_t *status,
+                                   const int32_t *iters, hipStream_t stream);
 
 // Fused closed loop (tmpc_fused.hip: the wave kernel with the state machines inside, a trajectory per work item): available for
 // every wave shape; one problem variant (the plain controllers: the extended one changes its problem from step to step)

@@ -50,6 +50,20 @@ __global__ __launch_bounds__(WAVE_MC * MC_WPB) void mc_step_kernel(const McModel
     (void)mc_step_wave(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, sh[wave], lane);
 }
 
+// The same launch for the stepped loop (tmpc_mc_step_device): the plant state is the caller's array, the applied input goes to
+// the caller's array (mc_step_impl<true>).
+__global__ __launch_bounds__(WAVE_MC * MC_WPB) void mc_session_kernel(const McModel m, const McState st, const McExternal ext, const int t,
+                                                                      const int T, const int64_t B, const double ref_t, const double ref_next,
+                                                                      const double *__restrict__ u_nom, const double *__restrict__ x_nom0,
+                                                                      const double *__restrict__ xu_ss, const int32_t *__restrict__ status,
+                                                                      const int32_t *__restrict__ iters) {
+    __shared__ double sh[MC_WPB][V_COUNT][MAXN];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * MC_WPB + wave;
+    if (b >= B) return;
+    (void)mc_step_impl<true>(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, sh[wave], lane, nullptr, ext);
+}
+
 }  // namespace
 
 // Instances whose variant id names no problem of the handle are solved by no kernel: they get status NUMERICAL and NaN
@@ -89,6 +103,16 @@ hipError_t launch_mc_step(const McModel &m, const McState &st, int t, int T, int
     const unsigned blocks = static_cast<unsigned>((B + MC_WPB - 1) / MC_WPB);
     hipLaunchKernelGGL(mc_step_kernel, dim3(blocks), dim3(WAVE_MC * MC_WPB), 0, stream, m, st, t, T, B, ref_t, ref_next, u_nom, x_nom0, xu_ss,
                        status, iters);
+    return hipGetLastError();
+}
+
+hipError_t launch_mc_step_external(const McModel &m, const McState &st, const McExternal &ext, int t, int T, int64_t B, double ref_t,
+                                   double ref_next, const double *u_nom, const double *x_nom0, const double *xu_ss, const int32_t *status,
+                                   const int32_t *iters, hipStream_t stream) {
+    if (m.nx > MAXN || m.nu > MAXN || m.plant != TMPC_PLANT_EXTERNAL || !ext.x_t || !ext.u_t) return hipErrorInvalidValue;
+    const unsigned blocks = static_cast<unsigned>((B + MC_WPB - 1) / MC_WPB);
+    hipLaunchKernelGGL(mc_session_kernel, dim3(blocks), dim3(WAVE_MC * MC_WPB), 0, stream, m, st, ext, t, T, B, ref_t, ref_next, u_nom, x_nom0,
+                       xu_ss, status, iters);
     return hipGetLastError();
 }
 

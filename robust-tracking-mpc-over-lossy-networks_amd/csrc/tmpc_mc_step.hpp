@@ -54,12 +54,14 @@ __device__ __forceinline__ double u01(unsigned long long x) { return static_cast
 // The step's draws of trajectory b as seen by one lane of its wave: theta and gamma uniforms (every lane), component
 // `comp` of the disturbance w (lanes comp < nx; nx <= 16).  Device generator: block j = 0 of the step holds
 // [theta, gamma, w_0, w_1], block j >= 1 holds w_{4j-2} .. w_{4j+1} (include/tmpc.h: tmpc_mc_set_device_rng).
-template <class StateRec>
+// (W = false: the stepped loop around a plant of the caller's -- the disturbance is the caller's, none is drawn or read)
+template <bool W = true, class StateRec>
 __device__ __forceinline__ void mc_draws(const StateRec &st, int64_t b, int t, int T, int nx, int comp, double &th, double &ga, double &w) {
     if (!st.rng_on) {
         th = st.th_u[b * T + t];
         ga = st.ga_u[b * T + t];
-        w = comp < nx ? st.w[(b * T + t) * nx + comp] : 0.0;
+        w = 0.0;
+        if constexpr (W) w = comp < nx ? st.w[(b * T + t) * nx + comp] : 0.0;
         return;
     }
     const unsigned long long key1 = static_cast<unsigned long long>(st.rng_first + b);
@@ -67,6 +69,8 @@ __device__ __forceinline__ void mc_draws(const StateRec &st, int64_t b, int t, i
     philox4x64(static_cast<unsigned long long>(t), 0ull, st.rng_seed, key1, r);
     th = u01(r[0]);
     ga = u01(r[1]);
+    w = 0.0;
+    if constexpr (!W) return;
     const int idx = comp + 2;
     if (idx >= 4) philox4x64(static_cast<unsigned long long>(t), static_cast<unsigned long long>(idx >> 2), st.rng_seed, key1, r);
     const unsigned long long rc = (idx & 3) == 0 ? r[0] : ((idx & 3) == 1 ? r[1] : ((idx & 3) == 2 ? r[2] : r[3]));
@@ -90,19 +94,29 @@ enum { V_X = 0, V_XN, V_E, V_ET, V_U, V_UN, V_BASE, V_TMP, V_COUNT };
 // The sums run in the order of the round-3 kernels (and of the numpy twins in montecarlo.py).
 // (ModelRec, StateRec: McModel / McState, or the same records read through the constant address space -- the fused kernel, where every field is then a
 // scalar load at its use instead of a kernel argument that lives in registers for the whole solve)
-template <class ModelRec, class StateRec>
-__device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &st, const int t, const int T, const int64_t b,
+//
+// EXT = true (TMPC_PLANT_EXTERNAL, the stepped loop of tmpc_mc_open / tmpc_mc_step_device): the plant is the caller's.  Lane i takes
+// x_t from ext.x_t instead of st.x, lanes < nu write the applied input to ext.u_t (0 for a trajectory that has stopped), x_t and u_t
+// are checked against the caller's sets X and U, the nominal model and the estimator advance as ever, and no plant state and no
+// disturbance is read, drawn or written.  A template parameter, not a branch on m.plant: the solve kernels that inline this function
+// keep their code and their registers, and the caller's record is an argument of the one kernel that has a caller.
+template <bool EXT, class ModelRec, class StateRec>
+__device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &st, const int t, const int T, const int64_t b,
                                              const double ref_t, const double ref_next,
                                              const double *u_nom, const double *x_nom0, const double *xu_ss, const int32_t *status,
                                              const int32_t *iters, double (&S)[V_COUNT][MAXN], const int lane,
-                                             uint8_t *gamma_out = nullptr /* where this step's arrival flag goes instead of st.gamma */) {
+                                             uint8_t *gamma_out /* where this step's arrival flag goes instead of st.gamma */,
+                                             const McExternal &ext) {
     const int nx = m.nx, nu = m.nu, N = m.N;
-    if (st.dead[b]) return false;                                                        // results_linear_system.py:262
+    if (st.dead[b]) {                                                                    // results_linear_system.py:262
+        if constexpr (EXT) { if (lane < nu) ext.u_t[b * nu + lane] = 0.0; }
+        return false;
+    }
     const bool replay = st.rp_U != nullptr;      // packets injected by the caller instead of solved (tmpc_mc_replay)
     const bool lx = lane < nx, lu = lane < nu;
     const double p = st.p_loss[b];
     double th_draw, ga_draw, w_l;
-    mc_draws(st, b, t, T, nx, lane, th_draw, ga_draw, w_l);
+    mc_draws<!EXT>(st, b, t, T, nx, lane, th_draw, ga_draw, w_l);
     int theta = (t > 0 && th_draw < p) ? 0 : 1;                                          // strict <, first packet always arrives
     const int stat = replay ? 0 : status[b];
     const bool bad = stat >= 2;
@@ -122,13 +136,16 @@ __device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &
             st.err2[b] = __longlong_as_double(0x7ff8000000000000ll);
             if (st.err2_phys) st.err2_phys[b] = __longlong_as_double(0x7ff8000000000000ll);
         }
+        if constexpr (EXT) { if (lu) ext.u_t[b * nu + lane] = 0.0; }
         return false;
     }
     // the controller's packet of this step: u_0 .. u_{N-1}, the terminal column u_bar + K x_bar (TubeTrackingMPC.py:217), x_nom_0
     const double *pk_u = replay ? st.rp_U + (b * T + t) * static_cast<int64_t>((N + 1) * nu) : u_nom + b * N * nu;
     const double *pk_x0 = replay ? st.rp_xn0 + (b * T + t) * static_cast<int64_t>(nx) : x_nom0 + b * nx;
 
-    const double x_l = lx ? st.x[b * nx + lane] : 0.0;
+    double x_l = 0.0;
+    if constexpr (EXT) { if (lx) x_l = ext.x_t[b * nx + lane]; }
+    else { if (lx) x_l = st.x[b * nx + lane]; }
     double xnom_l = lx ? st.x_nom[b * nx + lane] : 0.0;
     // The tube statistic of the scripts is x_traj[:, t] - x_nom_traj[:, t] (results_linear_system.py:258,
     // results_linear_system_with_extendedMPC.py:331): the nominal state appended after the PREVIOUS step's process_packet,
@@ -208,6 +225,28 @@ __device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &
         }
         if (__any(out) && lane == 0) st.tube_viol[b] += 1;
     }
+    if constexpr (EXT) {
+        // the caller's plant in X, the applied input in U (rows over the lanes, abs_tol as above; tmpc_reg.hip: set_violated)
+        if (lu) ext.u_t[b * nu + lane] = u_l;
+        if (ext.rX > 0) {
+            int out = 0;
+            for (int r = lane; r < ext.rX; r += WAVE_MC) {
+                double v = -ext.hX[r];
+                for (int i = 0; i < nx; ++i) v += ext.HX[r * nx + i] * S[V_X][i];
+                out |= (v > 1e-7);
+            }
+            if (__any(out) && lane == 0) ext.x_viol[b] += 1;
+        }
+        if (ext.rU > 0) {
+            int out = 0;
+            for (int r = lane; r < ext.rU; r += WAVE_MC) {
+                double v = -ext.hU[r];
+                for (int j = 0; j < nu; ++j) v += ext.HU[r * nu + j] * S[V_U][j];
+                out |= (v > 1e-7);
+            }
+            if (__any(out) && lane == 0) ext.u_viol[b] += 1;
+        }
+    }
     // ---- plant and nominal model
     double xp_l = 0.0, xnp_l = 0.0;
     if (lx) {
@@ -217,7 +256,7 @@ __device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &
         xp_l = v;
         xnp_l = vn;
     }
-    if (m.plant == TMPC_PLANT_CARTPOLE) {
+    if (!EXT && m.plant == TMPC_PLANT_CARTPOLE) {
         // zero-order hold of u over the sampling period, RK4 at the physics rate (every lane integrates the same four states);
         // the nominal model stays linear
         double y[4] = {S[V_X][0], S[V_X][1], S[V_X][2], S[V_X][3]};
@@ -242,7 +281,10 @@ __device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &
         if (lx) xp_l = yl + w_l;
         if (st.err2_phys && lane == 0) st.err2_phys[b] += aphys;
     }
-    if (lx) { st.x[b * nx + lane] = xp_l; st.x_nom[b * nx + lane] = xnp_l; }
+    if (lx) {
+        if constexpr (!EXT) st.x[b * nx + lane] = xp_l;
+        st.x_nom[b * nx + lane] = xnp_l;
+    }
     // ---- estimator (Estimator.py:43-98; robust: :113-156)
     const int gamma = (t > 0 && ga_draw < p) ? 0 : 1;
     double xh_l = 0.0;
@@ -281,7 +323,7 @@ __device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &
     }
     if (lane == 0) (gamma_out ? gamma_out : st.gamma)[b] = static_cast<uint8_t>(gamma);
     if (lx) st.ref_k[b * nx + lane] = (lane == 0) ? ref_next : 0.0;      // ref = [ref_{t+1}, 0, ..] of the next solve (:240)
-    if (st.trace_f) {
+    if (!EXT && st.trace_f) {
         // every step of every trajectory (tmpc_mc_replay): x_{t+1}, x_hat_{t+1}, the nominal state of the plant's packet, u_t;
         // s_t, Theta_t and the q_t the controller put into its packet
         double *tf = st.trace_f + (b * T + t) * static_cast<int64_t>(3 * nx + nu);
@@ -292,6 +334,15 @@ __device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &
     return true;
 }
 
+// the loops that own their plant (tmpc_mc_run, tmpc_mc_replay: mc_step_kernel and the fused solve kernels)
+template <class ModelRec, class StateRec>
+__device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &st, const int t, const int T, const int64_t b,
+                                             const double ref_t, const double ref_next,
+                                             const double *u_nom, const double *x_nom0, const double *xu_ss, const int32_t *status,
+                                             const int32_t *iters, double (&S)[V_COUNT][MAXN], const int lane,
+                                             uint8_t *gamma_out = nullptr) {
+    return mc_step_impl<false>(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, S, lane, gamma_out, McExternal{});
+}
 
 }  // namespace mcstep
 }  // namespace tmpc
