@@ -322,6 +322,11 @@ int tmpc_debug_dump_lp_layout(int32_t d, int32_t nr, const double *H, const doub
  *        iters_sum   B   interior-point iterations spent on the trajectory (the solve effort the reference's scripts report
  *                        as times, results_linear_system.py:305-315)
  * All pointers are HOST pointers; the call returns when the results are in place.
+ *
+ * With a reference table set (tmpc_mc_set_reference_table below, "full-reference mode") `ref` is not read and may be NULL: the
+ * solve of step t of trajectory b gets the full state table[ref_id[b]][t][0..nx), and err2 is sum_t sum_i (x_t[i] - r_t[i])^2
+ * (the physics-rate error of a nonlinear plant likewise, r_t held over the sampling period).  B must be the table's B and
+ * T <= T_tab, else TMPC_E_INVALID.  Everything else is unchanged.
  */
 int tmpc_mc_run(tmpc_handle *h, int64_t B, int32_t T, int extended, const double *p_loss, const double *ref,
                 const double *th_u, const double *ga_u, const double *w, const double *x0, const double *HZ, const double *hZ,
@@ -481,6 +486,28 @@ int tmpc_mc_step_device(tmpc_handle *h, const double *x_t, double *u_t, void *ca
 int tmpc_mc_step(tmpc_handle *h, const double *x_t, double *u_t);
 int tmpc_mc_close(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_viol, int32_t *u_viol, int32_t *not_optimal,
                   double *consistent, int32_t *iters_sum, int32_t *steps_done);
+/*
+ * Full-state reference schedules of the closed loops, per trajectory ("full-reference mode" of tmpc_mc_run and tmpc_mc_open).
+ *   table   K x T_tab x nx, row-major, HOST memory, copied: K >= 1 schedules of full-state references
+ *   ref_id  B, in [0, K): the schedule of trajectory b of the next loops.  NULL: schedule 0 for everybody when K == 1,
+ *           schedule b when K == B, TMPC_E_INVALID otherwise.
+ *   K == 0  clears the setting (table, T_tab, B and ref_id are then ignored).
+ * The copy lives on the host (the setter works on a host-only handle) and is uploaded with each loop.  While a table is set,
+ * tmpc_mc_run and tmpc_mc_open need their B equal to the table's B and their T <= T_tab (TMPC_E_INVALID otherwise) and do not
+ * read their `ref` (NULL allowed): the solve of step t of trajectory b gets table[ref_id[b]][t], and the tracking error of step t
+ * is sum_i (x_t[i] - r_t[i])^2 against the reference the solve of step t used.  tmpc_mc_replay and tmpc_reg_run ignore the
+ * setting.  TMPC_E_INVALID: K < 0, T_tab < 1, B < 1, table == NULL with K > 0, an id out of range, a regulator handle, an open
+ * session.  Without a table every loop runs as before.
+ *
+ * tmpc_mc_step_device_ref / tmpc_mc_step_ref: tmpc_mc_step_device / tmpc_mc_step with ref_next (B*nx; a DEVICE pointer for the
+ * former, read by the state-machine launch behind caller_stream like x_t; a HOST pointer for the latter), the reference of the
+ * solve of step t + 1.  NULL: row t + 1 of the schedule, i.e. the plain call.  Only in a session opened in full-reference mode
+ * (TMPC_E_INVALID otherwise; the session stays usable): the table gives the reference of step 0 and the default of every later
+ * step -- a caller with online references only passes a constant table.  Added without an ABI bump.
+ */
+int tmpc_mc_set_reference_table(tmpc_handle *h, int32_t K, int32_t T_tab, const double *table, int64_t B, const int32_t *ref_id);
+int tmpc_mc_step_device_ref(tmpc_handle *h, const double *x_t, double *u_t, const double *ref_next, void *caller_stream);
+int tmpc_mc_step_ref(tmpc_handle *h, const double *x_t, double *u_t, const double *ref_next);
 /*
  * With a nonlinear plant tmpc_mc_run also sums |x - ref|^2 over the T * substeps physics steps (the state at the start of
  * every physics step, i.e. x_traj[:, 0:-1] of results_nonlinear_system.py:361, whose tracking error is taken at 500 Hz);

@@ -214,34 +214,41 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         return np.ascontiguousarray(U.transpose(0, 2, 1)), out["x_nom0"], out["status"]
 
     def open_closed_loop(self, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, extended: bool = False, X=None, U=None,
-                         warm_start: bool = False, capture=None, timing: bool = False, device_rng=None) -> "ClosedLoopSession":
+                         warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None) -> "ClosedLoopSession":
         """The closed loop of run_closed_loop around a plant of the CALLER's, one time step per call (include/tmpc.h:
         tmpc_mc_open): `with mpc.open_closed_loop(...) as s: u = s.step(x) ...; stats = s.stats`.  The session runs the same
         state machines and solves on the device; the caller gives x_t and gets the applied u_t back.  th_u / ga_u (B, T): the
         loss uniforms (None with device_rng = (seed, first_trajectory[, ..])); no disturbance is drawn -- w is the plant's.
         X, U: optional check sets for x_t / u_t (polytopes) -> x_violations, u_violations.  T: steps the session may take
-        (default len(ref)).  One session per controller at a time; nothing else may be solved with it until close()."""
+        (default len(ref)).  One session per controller at a time; nothing else may be solved with it until close().
+        ref: (T,) position reference, or a full-state form -- (T, nx), (B, T, nx), (K, T, nx) with ref_id (B,), or (nx,) together
+        with T (see run_closed_loop); such a session also takes step(x, ref_next): the reference of the next solve, online."""
         from . import _native
         if self._handle is None:
             raise RuntimeError("setup_optimization() has not been called")
         _native.mc_set_actuator(self._handle, self._smart_actuator)
         info = _native.mc_open(self._handle, p_loss, ref, th_u, ga_u, x0=x0, T=T, Z=None if self._smart_actuator else self._Z,
                                X=X, U=U, extended=extended, warm_start=warm_start, capture=capture, timing=timing,
-                               device_rng=device_rng)
+                               device_rng=device_rng, ref_id=ref_id)
         return ClosedLoopSession(self, info)
 
-    def _run_closed_loop_around(self, plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng):
+    def _run_closed_loop_around(self, plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng,
+                                ref_id=None, T=None):
         """run_closed_loop(plant=callable): a session driven by plant(x, u) -> x_plus on device tensors, + w[:, t] as the host loop adds it."""
         import torch
         dev = torch.device("cuda", self._device)
-        ref = np.asarray(ref, dtype=np.float64).reshape(-1)
-        B, T, nx = int(np.asarray(p_loss).reshape(-1).shape[0]), ref.shape[0], self._nx
+        from . import _native
+        nx, B = self._nx, int(np.asarray(p_loss).reshape(-1).shape[0])
+        if T is None and th_u is not None and device_rng is None:
+            T = np.shape(th_u)[1]
+        T = _native.reference_form(nx, "run_closed_loop", ref, B, T, ref_id, flatten_legacy=True)[2] if T is None else T
+        T = int(T)
         x = torch.zeros((B, nx), dtype=torch.float64, device=dev) if x0 is None else \
             torch.as_tensor(np.asarray(x0, dtype=np.float64).reshape(B, nx), device=dev)
         wd = None if w is None else torch.as_tensor(np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(B, T, nx).transpose(1, 0, 2)), device=dev)
         with torch.cuda.device(dev):
             with self.open_closed_loop(p_loss, ref, th_u, ga_u, x0=x0, T=T, extended=extended, warm_start=warm_start, capture=capture,
-                                       timing=timing, device_rng=device_rng) as s:
+                                       timing=timing, device_rng=device_rng, ref_id=ref_id) as s:
                 for t in range(T):
                     xp = plant(x, s.step(x))
                     x = (xp if wd is None else xp + wd[t]).contiguous()
@@ -250,7 +257,8 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         return out
 
     def run_closed_loop(self, p_loss, ref, th_u=None, ga_u=None, w=None, x0=None, extended: bool = False, plant=None,
-                        warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, fused=None) -> dict:
+                        warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, fused=None, ref_id=None,
+                        T=None) -> dict:
         """The lossy-network closed loop of the reference's Monte-Carlo scripts (results_linear_system.py:209-291)
         for a batch of trajectories, resident on the device (include/tmpc.h: tmpc_mc_run): ONE launch for the whole sweep
         where the controller has one QP (a wavefront keeps its trajectory for all T steps: solve, state machines, solve, ...;
@@ -264,12 +272,17 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         (tmpc_mc_set_device_rng; montecarlo.draw_realisations_philox is the host twin).
         plant: None / "linear" / "cartpole" -- the plants the library simulates itself; or a callable (x, u) -> x_plus on
         float64 CUDA tensors (B, nx), (B, nu): any other plant, stepped through open_closed_loop (one call per time step; w[:, t],
-        if given, is added to x_plus; `fused` does not apply)."""
+        if given, is added to x_plus; `fused` does not apply).
+        ref: (T,) -- the scripts' position reference, shared by the batch: the solve gets [ref_t, 0, ..] and the tracking error is
+        taken against it; or FULL-STATE references per trajectory (tmpc_mc_set_reference_table): (T, nx) one schedule, (B, T, nx)
+        one per trajectory, (K, T, nx) with ref_id (B,) K schedules shared by the batch, (nx,) together with T (> nx) a constant
+        full state -- the solve of step t gets the row, the tracking error is |x_t - r_t| over all states."""
         from . import _native
         if self._handle is None:
             raise RuntimeError("setup_optimization() has not been called")
         if callable(plant):
-            out = self._run_closed_loop_around(plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng)
+            out = self._run_closed_loop_around(plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng,
+                                               ref_id=ref_id, T=T)
             if timing:
                 self._computational_times.extend(out["solve_time_mean"].tolist())
             return out
@@ -277,7 +290,8 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         _native.mc_set_actuator(self._handle, self._smart_actuator)
         out = _native.mc_run(self._handle, p_loss, ref, th_u, ga_u, w, x0=x0, Z=None if self._smart_actuator else self._Z,
                              extended=extended, warm_start=warm_start, capture=capture, timing=timing,
-                             physics_substeps=0 if plant in (None, "linear") else 10, device_rng=device_rng, fused=fused)
+                             physics_substeps=0 if plant in (None, "linear") else 10, device_rng=device_rng, fused=fused,
+                             ref_id=ref_id, T=T)
         if timing:
             self._computational_times.extend(out["solve_time_mean"].tolist())
         return out
@@ -326,7 +340,8 @@ class TubeTrackingMPC(TubeRegulatorMPC):
 
 class ClosedLoopSession:
     """A stepped closed loop (TubeTrackingMPC.open_closed_loop; include/tmpc.h: tmpc_mc_open / _step / _close).  step(x) takes
-    the plant states x_t (B, nx) and returns the applied inputs u_t (B, nu):
+    the plant states x_t (B, nx) and returns the applied inputs u_t (B, nu); step(x, ref_next), in a session opened with a
+    full-state reference, also hands over the reference (B, nx) of the NEXT solve, same kind of array as x (None: the schedule's row):
       a contiguous float64 CUDA tensor -> a CUDA tensor the session owns and REUSES every step (clone it to keep it), ordered on
                                           torch's current stream: no synchronisation, the plant's kernels may follow at once;
       a numpy array                    -> a numpy array, when the inputs are in place.
@@ -340,29 +355,35 @@ class ClosedLoopSession:
         self.stats = None
         self.steps = 0
 
-    def step(self, x):
+    def step(self, x, ref_next=None):
         from . import _native
         if self._info is None:
             raise RuntimeError("the session is closed")
         h = self._mpc._handle
         B = self._info["B"]
         if isinstance(x, np.ndarray):
-            u = _native.mc_step(h, self._info, x).reshape(B, h.nu)
+            u = _native.mc_step(h, self._info, x, ref_next=ref_next).reshape(B, h.nu)
             self.steps += 1
             return u
         import torch
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.numel() == B * h.nx):
             raise ValueError("step: x must be a numpy array or a contiguous float64 CUDA tensor of B * nx entries")
+        rn = None
+        if ref_next is not None:
+            if not (isinstance(ref_next, torch.Tensor) and ref_next.is_cuda and ref_next.dtype == torch.float64 and ref_next.is_contiguous()
+                    and ref_next.numel() == B * h.nx):
+                raise ValueError("step: with a tensor x, ref_next must be a contiguous float64 CUDA tensor of B * nx entries")
+            rn = ref_next.data_ptr()
         if self._u is None:
             self._u = torch.empty((B, h.nu), dtype=torch.float64, device=x.device)
         cur = torch.cuda.current_stream(x.device)
         if cur.cuda_stream != 0:
-            _native.mc_step(h, self._info, x.data_ptr(), self._u.data_ptr(), cur.cuda_stream)
+            _native.mc_step(h, self._info, x.data_ptr(), self._u.data_ptr(), cur.cuda_stream, ref_next=rn)
         else:
             if self._side is None:
                 self._side = torch.cuda.Stream(device=x.device)
             self._side.wait_stream(cur)
-            _native.mc_step(h, self._info, x.data_ptr(), self._u.data_ptr(), self._side.cuda_stream)
+            _native.mc_step(h, self._info, x.data_ptr(), self._u.data_ptr(), self._side.cuda_stream, ref_next=rn)
             cur.wait_stream(self._side)
         self.steps += 1
         return self._u

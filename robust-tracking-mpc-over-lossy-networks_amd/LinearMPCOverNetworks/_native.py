@@ -127,6 +127,12 @@ def lib():
         L.tmpc_mc_step_device.restype = C.c_int
         L.tmpc_mc_step.argtypes = [C.c_void_p] * 3
         L.tmpc_mc_step.restype = C.c_int
+        L.tmpc_mc_set_reference_table.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        L.tmpc_mc_set_reference_table.restype = C.c_int
+        L.tmpc_mc_step_device_ref.argtypes = [C.c_void_p] * 5
+        L.tmpc_mc_step_device_ref.restype = C.c_int
+        L.tmpc_mc_step_ref.argtypes = [C.c_void_p] * 4
+        L.tmpc_mc_step_ref.restype = C.c_int
         L.tmpc_mc_close.argtypes = [C.c_void_p] * 9
         L.tmpc_mc_close.restype = C.c_int
         L.tmpc_mc_replay.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 8
@@ -461,11 +467,74 @@ def mc_set_plant(h: Handle, plant=None, Th: float = 0.02, substeps: int = 10):
         raise RuntimeError(h.error())
 
 
+def mc_set_reference(h: Handle, table=None, ref_id=None, B=None):
+    """include/tmpc.h: tmpc_mc_set_reference_table -- full-state reference schedules of the next closed loops.  table
+    (K, T_tab, nx) (or (T_tab, nx): K = 1); ref_id (B,) ints in [0, K) or None (K == 1: schedule 0 for everybody, K == B: schedule
+    b); B: the batch of the loops (default: len(ref_id), else K).  table None clears the setting."""
+    if table is None:
+        if lib().tmpc_mc_set_reference_table(h.ptr, 0, 0, None, 0, None) != 0:
+            raise RuntimeError(h.error())
+        return
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.float64))
+    if table.ndim == 2:
+        table = table[None]
+    if table.ndim != 3 or table.shape[2] != h.nx:
+        raise ValueError(f"mc_set_reference: table must be (K, T_tab, nx = {h.nx}), got {table.shape}")
+    K, T_tab = table.shape[:2]
+    ids = None
+    if ref_id is not None:
+        ids = np.ascontiguousarray(np.asarray(ref_id).reshape(-1), dtype=np.int32)
+        if not np.array_equal(ids, np.asarray(ref_id).reshape(-1)):
+            raise ValueError("mc_set_reference: ref_id must hold integers")
+        if B is not None and int(B) != ids.shape[0]:
+            raise ValueError("mc_set_reference: ref_id must have B entries")
+    Bv = int(B) if B is not None else (ids.shape[0] if ids is not None else K)
+    rc = lib().tmpc_mc_set_reference_table(h.ptr, K, T_tab, table.ctypes.data, Bv, None if ids is None else ids.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"tmpc_mc_set_reference_table failed ({rc}): {h.error()}")
+
+
+def reference_form(nx: int, who: str, ref, B: int, T, ref_id, flatten_legacy: bool = False):
+    """The `ref` forms of the closed loops -> (legacy (T,) array or None, table (K, T, nx) or None, T): (T,) legacy; (nx,) with
+    T > nx, or (1, nx) with any T: constant full state; (T, nx): one schedule; (B, T, nx): one per trajectory; (K, T, nx) with
+    ref_id (B,): K shared schedules.  flatten_legacy (the stepped loop, which has always flattened its `ref`): a scalar, and a 2-D
+    array that is no full-state form -- one row or one column, the other extent not nx -- are the legacy reference flattened.
+    The one place that tells the forms apart."""
+    ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64))
+    if flatten_legacy and ref_id is None and (ref.ndim == 0 or (ref.ndim == 2 and 1 in ref.shape and ref.shape[1] != nx)):
+        ref = ref.reshape(-1)
+    if ref.ndim == 2 and ref.shape == (1, nx) and T is not None and ref_id is None:
+        ref = np.broadcast_to(ref[None], (1, int(T), nx))          # the constant form for every T (T <= nx included)
+    if ref.ndim == 1:
+        # (nx,) is the constant form where it cannot be the legacy one: T is given and the array does not cover T steps
+        if not (T is not None and ref.shape[0] == nx and ref.shape[0] < int(T)):
+            if ref_id is not None:
+                raise ValueError(f"{who}: ref_id selects among (K, T, nx) schedules")
+            return ref, None, ref.shape[0]
+        ref = np.broadcast_to(ref, (1, int(T), nx))
+    elif ref.ndim == 2:
+        ref = ref[None]
+    if ref.ndim != 3 or ref.shape[2] != nx:
+        raise ValueError(f"{who}: ref must be (T,), (nx,) with T > nx or (1, nx) with T, (T, nx), (B, T, nx) or (K, T, nx) with ref_id; "
+                         f"got {ref.shape} (nx = {nx})")
+    if ref_id is None and ref.shape[0] not in (1, B):
+        raise ValueError(f"{who}: ref holds {ref.shape[0]} schedules for B = {B} trajectories and no ref_id")
+    return None, ref, (ref.shape[1] if T is None else int(T))
+
+
+def _loop_reference(h: Handle, who: str, ref, B: int, T, ref_id, flatten_legacy: bool = False):
+    """reference_form applied to the handle: the table set for the full-state forms, cleared for the legacy one (so that a
+    handle's earlier setting never leaks into a legacy call) -> (the legacy (T,) array or None, T)."""
+    legacy, table, T = reference_form(h.nx, who, ref, B, T, ref_id, flatten_legacy)
+    mc_set_reference(h, table, ref_id if table is not None else None, B=B if table is not None else None)
+    return legacy, T
+
+
 MC_FUSED = {"off": 0, "on": 1, "auto": 2, False: 0, True: 1, None: 2}      # include/tmpc.h: TMPC_MC_FUSED_*
 
 
 def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: bool = False, warm_start: bool = False,
-           capture=None, timing: bool = False, physics_substeps: int = 0, device_rng=None, fused=None) -> dict:
+           capture=None, timing: bool = False, physics_substeps: int = 0, device_rng=None, fused=None, ref_id=None, T=None) -> dict:
     """include/tmpc.h: tmpc_mc_run -- the closed loop over the lossy network, resident on the device.
     warm_start: tmpc_mc_set_warm_start for this call; capture: index of a trajectory to record (tmpc_mc_set_capture) ->
     x_traj (T, nx), x_nom_traj (T, nx), u_traj (T, nu) in the result; timing: per trajectory the mean and the maximum
@@ -476,7 +545,11 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     montecarlo.draw_realisations_philox gives the same numbers on the host); th_u, ga_u, w are then ignored and may be None,
     the batch is len(p_loss) x len(ref).
     fused: "on" / "off" / "auto" (None) -- tmpc_mc_set_fused: one launch for all T steps, a launch pair per step, or the library's
-    choice; the result's "fused" says what ran."""
+    choice; the result's "fused" says what ran.
+    ref: (T,) position reference of the whole batch (the solve gets [ref_t, 0, ..]); or full-state references through
+    tmpc_mc_set_reference_table -- (T, nx) one schedule, (B, T, nx) one per trajectory, (K, T, nx) with ref_id (B,) K shared
+    schedules, (nx,) together with T (more than nx steps) a constant full state; the tracking error is then |x_t - r_t| over
+    all states.  A (T,) call clears an earlier table.  T: the steps (default: the draws' or the reference's)."""
     if lib().tmpc_set_solve_timing(h.ptr, int(bool(timing))) != 0:
         raise RuntimeError(h.error())
     if lib().tmpc_mc_set_fused(h.ptr, MC_FUSED[fused]) != 0:
@@ -486,21 +559,25 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     if lib().tmpc_mc_set_capture(h.ptr, -1 if capture is None else int(capture)) != 0:
         raise RuntimeError(h.error())
     c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-    p_loss, ref = c(p_loss), c(ref)
+    p_loss = c(p_loss)
+    if T is None and device_rng is None and th_u is not None:
+        T = np.shape(th_u)[1]
+    ref, T_ref = _loop_reference(h, "mc_run", ref, p_loss.shape[0], T, ref_id)
     if device_rng is not None:
         seed, first, w_bound = device_rng
         wb = None if w_bound is None else c(w_bound).reshape(h.nx)
         if lib().tmpc_mc_set_device_rng(h.ptr, 1, int(seed), int(first), None if wb is None else wb.ctypes.data) != 0:
             raise RuntimeError(h.error())
         th_u = ga_u = w = None
-        B, T = p_loss.shape[0], ref.shape[0]
+        B, T = p_loss.shape[0], T_ref
     else:
         if lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None) != 0:
             raise RuntimeError(h.error())
         th_u, ga_u, w = c(th_u), c(ga_u), c(w)
         B, T = th_u.shape
-        if ga_u.shape != (B, T) or w.shape != (B, T, h.nx) or p_loss.shape != (B,) or ref.shape != (T,):
-            raise ValueError("mc_run: inconsistent shapes")
+        if ga_u.shape != (B, T) or w.shape != (B, T, h.nx) or p_loss.shape != (B,) or (ref is not None and ref.shape != (T,)) or T_ref < T:
+            raise ValueError("mc_run: inconsistent shapes" + (f" (a constant full-state reference over T <= nx = {h.nx} steps is (1, nx): "
+                                                              "(nx,) is then read as the legacy (T,) form)" if ref is not None and ref.shape == (h.nx,) else ""))
     x0c = None if x0 is None else c(x0).reshape(B, h.nx)
     HZ = hZ = None
     rZ = 0
@@ -549,16 +626,18 @@ def _check_set(P, dim: int, who: str):
 
 
 def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=None, X=None, U=None, extended: bool = False,
-            warm_start: bool = False, capture=None, timing: bool = False, device_rng=None) -> dict:
-    """include/tmpc.h: tmpc_mc_open -- opens the stepped closed loop around a plant of the caller's.  p_loss (B,), ref (T,),
+            warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None) -> dict:
+    """include/tmpc.h: tmpc_mc_open -- opens the stepped closed loop around a plant of the caller's.  p_loss (B,), ref (T,)
+    or a full-state form (mc_run; (nx,) together with T: a constant full state -- the table of a session steered by ref_next),
     th_u / ga_u (B, T) loss uniforms (None with device_rng = (seed, first_trajectory[, ignored]): Philox block 0, the draws of
     mc_run), x0 (B, nx) or None; T: steps the session may take (default: len(ref)); Z / X / U: tube cross-section and the check
     sets for x_t / u_t (polytopes or None).  No disturbance is drawn: w is the plant's.  Returns what mc_close needs."""
     c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))      # noqa: E731
-    p_loss, ref = c(p_loss).reshape(-1), c(ref).reshape(-1)
+    p_loss = c(p_loss).reshape(-1)
     B = p_loss.shape[0]
-    T = ref.shape[0] if T is None else int(T)
-    if ref.shape[0] < T:
+    ref, T_ref = _loop_reference(h, "mc_open", ref, B, T, ref_id, flatten_legacy=True)
+    T = T_ref if T is None else int(T)
+    if (ref.shape[0] if ref is not None else T_ref) < T:
         raise ValueError("mc_open: ref must cover the T steps of the session")
     for call, arg in ((lib().tmpc_set_solve_timing, int(bool(timing))), (lib().tmpc_mc_set_warm_start, int(bool(warm_start))),
                       (lib().tmpc_mc_set_capture, -1 if capture is None else int(capture))):
@@ -583,13 +662,19 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
                             ptr(HZ), ptr(hZ), rZ, ptr(HX), ptr(hX), rX, ptr(HU), ptr(hU), rU)
     if rc != 0:
         raise RuntimeError(f"tmpc_mc_open failed ({rc}): {h.error()}")
-    return dict(B=B, T=T, capture=capture, timing=bool(timing))
+    return dict(B=B, T=T, capture=capture, timing=bool(timing), full_ref=ref is None)
 
 
-def mc_step(h: Handle, info: dict, x, u=None, stream=None):
+def mc_step(h: Handle, info: dict, x, u=None, stream=None, ref_next=None):
     """One step of the open session `info` = mc_open(...) describes.  x, u numpy (B, nx) / (B, nu): tmpc_mc_step, returns u when
     u_t is in place.  x, u integers: DEVICE addresses of B * nx / B * nu doubles for tmpc_mc_step_device, with `stream` the
-    caller's hipStream_t as an integer (None / 0: the caller synchronises on both sides); returns without synchronising."""
+    caller's hipStream_t as an integer (None / 0: the caller synchronises on both sides); returns without synchronising.
+    ref_next (sessions opened with a full-state reference): the reference of the NEXT solve, (B, nx) numpy with numpy x, a device
+    address with a device x (tmpc_mc_step_ref / tmpc_mc_step_device_ref); None: the next row of the schedule."""
+    if ref_next is not None and not info.get("full_ref", True):
+        raise RuntimeError("mc_step: ref_next needs a session opened with a full-state reference (a reference table: the (nx,) + T, "
+                           "(T, nx), (B, T, nx) or (K, T, nx) forms of `ref`)")
+    call = "tmpc_mc_step"
     if isinstance(x, np.ndarray):
         B = info["B"]
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -599,11 +684,22 @@ def mc_step(h: Handle, info: dict, x, u=None, stream=None):
             u = np.empty((B, h.nu))
         if not (isinstance(u, np.ndarray) and u.dtype == np.float64 and u.flags.c_contiguous and u.size == B * h.nu):
             raise ValueError("mc_step: u must be a contiguous float64 array of B * nu entries")
-        rc = lib().tmpc_mc_step(h.ptr, x.ctypes.data, u.ctypes.data)
-    else:
+        if ref_next is None:
+            rc = lib().tmpc_mc_step(h.ptr, x.ctypes.data, u.ctypes.data)
+        else:
+            r = np.ascontiguousarray(ref_next, dtype=np.float64)
+            if r.size != B * h.nx:
+                raise ValueError(f"mc_step: ref_next must hold B * nx = {B * h.nx} entries, got {r.size}")
+            call = "tmpc_mc_step_ref"
+            rc = lib().tmpc_mc_step_ref(h.ptr, x.ctypes.data, u.ctypes.data, r.ctypes.data)
+    elif ref_next is None:
+        call = "tmpc_mc_step_device"
         rc = lib().tmpc_mc_step_device(h.ptr, int(x), int(u), int(stream) if stream else None)
+    else:
+        call = "tmpc_mc_step_device_ref"
+        rc = lib().tmpc_mc_step_device_ref(h.ptr, int(x), int(u), int(ref_next), int(stream) if stream else None)
     if rc != 0:
-        raise RuntimeError(f"tmpc_mc_step failed ({rc}): {h.error()}")
+        raise RuntimeError(f"{call} failed ({rc}): {h.error()}")
     return u
 
 

@@ -151,7 +151,8 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     ExtendedTubeTrackingMPC that is told whether the previous plant packet arrived (gamma_{t-1}, :276), the
     estimator is the RobustEstimator (it also stores x_nom_0, :279) and the actuator adopts x_nom_0 (:133-147).
 
-    p_loss (B,), ref (T,) or (B,T) position reference, th_u/ga_u (B,T) uniforms, w (B,T,nx) disturbances.
+    p_loss (B,), ref (T,) or (B,T) position reference -- or (B,T,nx) full-state references: the solve of step t gets ref[:, t, :] and
+    the tracking error is sum_i (x_i - r_i)^2 (the device loop's tmpc_mc_set_reference_table) --, th_u/ga_u (B,T) uniforms, w (B,T,nx) disturbances.
     plant: None = the linear model x+ = A x + B u + w (:248); or a callable (x (B,nx), u (B,nu)) -> x+ (w is added to it),
     e.g. workloads.cartpole_step for the nonlinear cart-pole of results_nonlinear_system.py.
     capture: index of one trajectory whose x_t, nominal state of the tube check and u_t are recorded (the scripts' sample run,
@@ -165,7 +166,8 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     nb, T = th_u.shape
     nx = A.shape[0]
     p_loss = np.asarray(p_loss, dtype=np.float64).reshape(nb)
-    ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, or (B, T) per trajectory
+    ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, (B, T) per trajectory, or (B, T, nx) full states
+    full_ref = ref.ndim == 3                         # the solve gets ref[:, t, :], the error is sum_i (x_i - r_i)^2
 
     def ref_at(t):
         return ref[t] if ref.ndim == 1 else ref[:, t]
@@ -182,8 +184,11 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     gamma = np.ones(nb, dtype=np.int64)
     for t in range(T):
         theta = np.where(th_u[:, t] < p_loss, 0, 1) if t > 0 else np.ones(nb, dtype=np.int64)     # :211-226, strict <
-        r_t = np.zeros((nb, nx))
-        r_t[:, 0] = ref_at(t)
+        if full_ref:
+            r_t = np.ascontiguousarray(ref[:, t, :])
+        else:
+            r_t = np.zeros((nb, nx))
+            r_t[:, 0] = ref_at(t)
         q_t = est.get_qt()
         if extended:
             U_t, x_nom_0, status = packets_fn(est.get_estimate(), r_t, gamma.astype(np.uint8))     # RLX:276, gamma of step t-1
@@ -205,7 +210,10 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
         u, pkt = act.process(U_t, q_t, x, theta, x_nom_0 if extended else None)                    # :244
         if observer is not None:
             observer(t, dict(s=np.array(act.s).copy(), Theta=np.array(act.Theta).copy(), u=np.array(u).copy()))
-        err2 += (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1)                            # :291 (x_t, t = 0..T-1)
+        if full_ref:
+            err2 += (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1)        # (the order of the sum below)
+        else:
+            err2 += (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1)                        # :291 (x_t, t = 0..T-1)
         # :258 / results_linear_system_with_extendedMPC.py:310-318,331-333 -- x_traj[:, t] - x_nom_traj[:, t]: the nominal state
         # appended after the PREVIOUS step's process_packet, so for the extended controller the state before this step's
         # adoption of x_nom_0 (SmartActuator.py:219-222); for the plain tube MPC the two coincide
@@ -214,7 +222,10 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
             cap["x_traj"][t], cap["x_nom_traj"][t], cap["u_traj"][t] = x[capture], x_nom_now[capture], u[capture]
         if plant is not None and hasattr(plant, "trace"):
             xs = plant.trace(x, u)                                    # results_nonlinear_system.py:332-361: error over x_traj[:, 0:-1] at 500 Hz
-            err2_phys += np.sum((xs[:-1, :, 0] - ref_at(t)) ** 2 + np.sum(xs[:-1, :, 1:] ** 2, axis=2), axis=0)
+            if full_ref:
+                err2_phys += np.sum((xs[:-1, :, 0] - r_t[None, :, 0]) ** 2 + np.sum((xs[:-1, :, 1:] - r_t[None, :, 1:]) ** 2, axis=2), axis=0)
+            else:
+                err2_phys += np.sum((xs[:-1, :, 0] - ref_at(t)) ** 2 + np.sum(xs[:-1, :, 1:] ** 2, axis=2), axis=0)
             n_phys += xs.shape[0] - 1
             x = xs[-1] + w[:, t]
         else:
@@ -247,7 +258,8 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
     nb, T = th_u.shape
     nx = A.shape[0]
     p_loss = np.asarray(p_loss, dtype=np.float64).reshape(nb)
-    ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, or (B, T) per trajectory
+    ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, (B, T) per trajectory, or (B, T, nx) full states
+    full_ref = ref.ndim == 3                         # the solve gets ref[:, t, :], the error is sum_i (x_i - r_i)^2
 
     def ref_at(t):
         return ref[t] if ref.ndim == 1 else ref[:, t]
@@ -260,8 +272,11 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
     U_prev = None
     for t in range(T):
         theta = np.where(th_u[:, t] < p_loss, 0, 1) if t > 0 else np.ones(nb, dtype=np.int64)
-        r_t = np.zeros((nb, nx))
-        r_t[:, 0] = ref_at(t)
+        if full_ref:
+            r_t = np.ascontiguousarray(ref[:, t, :])
+        else:
+            r_t = np.zeros((nb, nx))
+            r_t[:, 0] = ref_at(t)
         q_t = est.get_qt()
         U_t, _, status = packets_fn(est.get_estimate(), r_t)
         newly = ~dead & (status >= 2)
@@ -273,7 +288,10 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
         act.x_nom = x.copy()
         u, pkt = act.process(U_t, q_t, x, theta)
         pkt = {"x_t": x.copy(), "s_t": pkt["s_t"]}
-        err2 += np.where(dead, 0.0, (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1))
+        if full_ref:
+            err2 += np.where(dead, 0.0, (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1))
+        else:
+            err2 += np.where(dead, 0.0, (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1))
         x = np.where(dead[:, None], x, x @ A.T + u @ Bm.T + w[:, t])
         gamma = np.where(ga_u[:, t] < p_loss, 0, 1) if t > 0 else np.ones(nb, dtype=np.int64)
         est.update(pkt, gamma)
@@ -298,7 +316,7 @@ def plant_callable(plant):
 
 def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240301, rank: int = 0, world: int = 1,
              extended: bool = False, device=None, on_device: bool = False, plant=None, warm_start: bool = False,
-             timing: bool = False, device_rng: bool = False, force_collective: bool = False):
+             timing: bool = False, device_rng: bool = False, force_collective: bool = False, ref_id=None):
     """The Monte-Carlo sweep of results_linear_system.py:147-301 (BASELINE config 4): len(p_loss) x n_mc
     trajectories of T steps, sharded over `world` ranks (one process per GPU, contiguous p_loss-balanced
     shards), every time step of a shard solved by one kernel launch, statistics all-gathered at the end.
@@ -306,7 +324,9 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     identical on every rank.  timing (device loop only): two more columns, the mean and the maximum device time of a
     trajectory's solves in seconds -- the computational times results_linear_system.py:305-315 reports.
     device_rng: Philox streams keyed by (seed, global trajectory index), drawn on the device in the device loop
-    (tmpc_mc_set_device_rng) and by draw_realisations_philox, the same numbers, in the host loops."""
+    (tmpc_mc_set_device_rng) and by draw_realisations_philox, the same numbers, in the host loops.
+    ref: a scalar or (T,) position reference; or (T, nx) one full-state schedule for every trajectory; or (K, T, nx) schedules
+    with ref_id (n_total,) naming each trajectory's -- sliced with the shard, so the sweep stays shard-invariant."""
     import torch
     p_loss = np.asarray(p_loss, dtype=np.float64)
     pi, _ = trajectory_table(p_loss, n_mc)
@@ -318,10 +338,20 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
         th, ga, w = draw_realisations_philox(hi - lo, T, model["w_bound"], seed=seed, first=lo)
     else:
         th, ga, w = draw_realisations(hi - lo, T, model["w_bound"], seed=seed, first=lo)
-    ref = np.broadcast_to(np.asarray(ref, dtype=np.float64), (T,))
+    ref = np.asarray(ref, dtype=np.float64)
+    ids = None
+    if ref.ndim >= 2:
+        ref = ref if ref.ndim == 3 else ref[None]
+        ids = np.zeros(n_total, dtype=np.int32) if ref_id is None else np.asarray(ref_id, dtype=np.int32).reshape(n_total)
+        ids = ids[lo:hi]
+        if not on_device:
+            ref = ref[ids, :T]                        # the host twins take one schedule per trajectory
+    else:
+        ref = np.broadcast_to(ref, (T,))
     if on_device:        # state machines on the GPU as well (tmpc_mc_run); otherwise the host loop around determine_packets
         out = mpc.run_closed_loop(p_loss[pi[lo:hi]], ref, th, ga, w, extended=extended, plant=plant, warm_start=warm_start,
-                                  timing=timing, device_rng=(seed, lo, model["w_bound"]) if device_rng else None)
+                                  timing=timing, device_rng=(seed, lo, model["w_bound"]) if device_rng else None, ref_id=ids,
+                                  T=T if ids is not None else None)
     elif getattr(mpc, "_smart_actuator", False):       # TrackingMPC: the comparator's loop (results_linear_system.py:262-287)
         out = run_remote_tracking_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(), mpc._N,
                                       p_loss[pi[lo:hi]], ref, th, ga, w)

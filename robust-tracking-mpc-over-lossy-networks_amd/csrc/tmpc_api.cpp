@@ -155,8 +155,10 @@ struct McSession {
     int32_t *ws[2] = {nullptr, nullptr}; // warm start: working sets per problem
     bool warm = false;
     std::vector<double> ref;
+    bool full_ref = false;               // opened with a reference table: st.ref_tab is set and the _ref steps are allowed
+    double *ref_stage = nullptr;         // device staging of tmpc_mc_step_ref's ref_next (full_ref)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;     // caller's stream -> handle's stream, and back
-    char *pin = nullptr;                 // pinned host block [x_t | u_t] of tmpc_mc_step (nullptr: copies from / to the caller's memory)
+    char *pin = nullptr;                 // pinned host block [x_t | u_t | ref_next] of tmpc_mc_step[_ref] (nullptr: copies from / to the caller's memory)
 };
 
 struct Variant {
@@ -224,6 +226,11 @@ struct tmpc_handle {
     uint64_t mc_rng_seed = 0;
     int64_t mc_rng_first = 0;
     std::vector<double> mc_w_bound;
+    // tmpc_mc_set_reference_table: K schedules of T_tab full-state references and the schedule of each of B trajectories (K = 0: none)
+    int32_t mc_ref_K = 0, mc_ref_T = 0;
+    int64_t mc_ref_B = 0;
+    std::vector<double> mc_ref_tab;
+    std::vector<int32_t> mc_ref_id;
     // closed-loop state: one grow-only arena (25 hipMalloc / hipFree per call cost several milliseconds), and what the last run
     // left in it
     Arena arena;
@@ -1203,6 +1210,41 @@ int tmpc_mc_get_physics_error(tmpc_handle *h, int64_t B, double *err2_phys) {
     return TMPC_OK;
 }
 
+int tmpc_mc_set_reference_table(tmpc_handle *h, int32_t K, int32_t T_tab, const double *table, int64_t B, const int32_t *ref_id) {
+    if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_reference_table")) return TMPC_E_INVALID;
+    if (h->regulator) { h->err = "tmpc_mc_set_reference_table: a regulator handle has no reference"; return TMPC_E_INVALID; }
+    if (K < 0) { h->err = "tmpc_mc_set_reference_table: K < 0"; return TMPC_E_INVALID; }
+    if (K == 0) {
+        h->mc_ref_K = h->mc_ref_T = 0;
+        h->mc_ref_B = 0;
+        h->mc_ref_tab.clear();
+        h->mc_ref_id.clear();
+        return TMPC_OK;
+    }
+    if (T_tab < 1 || B < 1) { h->err = "tmpc_mc_set_reference_table: need T_tab >= 1 and B >= 1"; return TMPC_E_INVALID; }
+    if (!table) { h->err = "tmpc_mc_set_reference_table: table is NULL"; return TMPC_E_INVALID; }
+    if (!ref_id && K != 1 && K != B) {
+        h->err = "tmpc_mc_set_reference_table: ref_id may be NULL only with K == 1 or K == B (K = " + std::to_string(K) + ", B = " + std::to_string(B) + ")";
+        return TMPC_E_INVALID;
+    }
+    std::vector<int32_t> ids(static_cast<size_t>(B));
+    for (int64_t b = 0; b < B; ++b) {
+        const int32_t id = ref_id ? ref_id[b] : (K == 1 ? 0 : static_cast<int32_t>(b));
+        if (id < 0 || id >= K) {
+            h->err = "tmpc_mc_set_reference_table: ref_id[" + std::to_string(b) + "] = " + std::to_string(id) + " is not in [0, " + std::to_string(K) + ")";
+            return TMPC_E_INVALID;
+        }
+        ids[static_cast<size_t>(b)] = id;
+    }
+    h->mc_ref_tab.assign(table, table + static_cast<size_t>(K) * static_cast<size_t>(T_tab) * static_cast<size_t>(h->nx));
+    h->mc_ref_id.swap(ids);
+    h->mc_ref_K = K;
+    h->mc_ref_T = T_tab;
+    h->mc_ref_B = B;
+    return TMPC_OK;
+}
+
 int tmpc_mc_set_warm_start(tmpc_handle *h, int on) {
     if (!h) return TMPC_E_INVALID;
     if (session_bars(h, "tmpc_mc_set_warm_start")) return TMPC_E_INVALID;
@@ -1230,6 +1272,25 @@ struct McReplay {
     int32_t *trace_i;           // host: [B][T][3]
 };
 
+// A loop of B trajectories and T steps under the handle's reference table (tmpc_mc_set_reference_table): does it fit?
+int reference_table_fits(tmpc_handle *h, const char *who, int64_t B, int32_t T) {
+    if (B != h->mc_ref_B) {
+        h->err = std::string(who) + ": B = " + std::to_string(B) + ", but the reference table was set for B = " + std::to_string(h->mc_ref_B) + " trajectories";
+        return TMPC_E_INVALID;
+    }
+    if (T > h->mc_ref_T) {
+        h->err = std::string(who) + ": T = " + std::to_string(T) + " steps, but the reference table has T_tab = " + std::to_string(h->mc_ref_T) + " rows";
+        return TMPC_E_INVALID;
+    }
+    return TMPC_OK;
+}
+// the table's pieces of a loop's arena (uploaded with the loop, as `ref` is)
+void reference_table_pieces(tmpc_handle *h, Arena &a, tmpc::McState &st) {
+    a.piece(&st.ref_tab, h->mc_ref_tab.size() * 8, h->mc_ref_tab.data());
+    a.piece(&st.ref_id, h->mc_ref_id.size() * 4, h->mc_ref_id.data());
+    st.ref_T = h->mc_ref_T;
+}
+
 int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double *p_loss, const double *ref,
                 const double *th_u, const double *ga_u, const double *w, const double *x0, const double *HZ, const double *hZ,
                 int32_t rZ, double *err2, int32_t *tube_viol, int32_t *not_optimal, double *x_final, double *consistent,
@@ -1237,13 +1298,19 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
     if (!h) return TMPC_E_INVALID;
     if (h->ses.open) { h->err = "tmpc_mc_run: a stepped closed loop is open on this handle (tmpc_mc_close first)"; return TMPC_E_INVALID; }
     const bool host_draws = rp != nullptr || !h->mc_rng_on;
-    if (B < 0 || T < 0 || !p_loss || !ref || (host_draws && (!th_u || !ga_u || !w)) || (rZ > 0 && (!HZ || !hZ))) { h->err = "tmpc_mc_run: NULL argument"; return TMPC_E_INVALID; }
+    const bool full_ref = !rp && h->mc_ref_K > 0;      // (tmpc_mc_replay solves nothing: it ignores the reference table)
+    if (B < 0 || T < 0 || !p_loss || (!ref && !full_ref) || (host_draws && (!th_u || !ga_u || !w)) || (rZ > 0 && (!HZ || !hZ))) { h->err = "tmpc_mc_run: NULL argument"; return TMPC_E_INVALID; }
     if (h->regulator) { h->err = "tmpc_mc_run: a regulator handle runs its loop with tmpc_reg_run"; return TMPC_E_INVALID; }
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
     if (extended && h->nvariants < 2) { h->err = "tmpc_mc_run: extended loop needs a problem created with extended = 1"; return TMPC_E_INVALID; }
     if (h->hK.empty() || h->hKanc.empty()) { h->err = "tmpc_mc_run: the problem description carries no gains K / K_anc"; return TMPC_E_INVALID; }
     if (h->nu > 16) { h->err = "tmpc_mc_run: nu <= 16"; return TMPC_E_UNSUPPORTED; }
+    if (full_ref)
+        if (const int r2 = reference_table_fits(h, "tmpc_mc_run", B, T)) return r2;
     if (B == 0 || T == 0) return TMPC_OK;
+    // full-reference mode: the scalar reference of the legacy mode is not read on the device; the launches get zeros
+    const std::vector<double> ref_unused(full_ref ? static_cast<size_t>(T) : 0, 0.0);
+    if (full_ref) ref = ref_unused.data();
     int rc = begin_loop(h, B);
     if (rc) return rc;
     const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(B), t_ = static_cast<size_t>(T);
@@ -1315,6 +1382,7 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
         int32_t *ws[2] = {nullptr, nullptr};
         if (h->mc_warm)
             for (int k = 0; k < (extended ? 2 : 1); ++k) a.piece(&ws[k], b * tmpc::WS_STRIDE * 4, nullptr, 0);
+        if (full_ref) reference_table_pieces(h, a, st);
         if (rp) {
             // (plain controller: the packets carry no x_nom_0; the state machines then never read it -- zeros)
             a.piece(&st.rp_U, b * t_ * (N + 1) * nu * 8, rp->U);
@@ -1506,7 +1574,8 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
     if (h->regulator) { h->err = "tmpc_mc_open: a regulator handle has no stepped loop"; return TMPC_E_INVALID; }
     const bool host_draws = !h->mc_rng_on;
     if (B <= 0 || T <= 0 || rZ < 0 || rX < 0 || rU < 0) { h->err = "tmpc_mc_open: need B > 0, T > 0 and row counts >= 0"; return TMPC_E_INVALID; }
-    if (!p_loss || !ref || (host_draws && (!th_u || !ga_u)) || (rZ > 0 && (!HZ || !hZ)) || (rX > 0 && (!HX || !hX)) || (rU > 0 && (!HU || !hU))) {
+    const bool full_ref = h->mc_ref_K > 0;
+    if (!p_loss || (!ref && !full_ref) || (host_draws && (!th_u || !ga_u)) || (rZ > 0 && (!HZ || !hZ)) || (rX > 0 && (!HX || !hX)) || (rU > 0 && (!HU || !hU))) {
         h->err = "tmpc_mc_open: NULL argument";
         return TMPC_E_INVALID;
     }
@@ -1514,6 +1583,8 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
     if (h->hK.empty() || h->hKanc.empty()) { h->err = "tmpc_mc_open: the problem description carries no gains K / K_anc"; return TMPC_E_INVALID; }
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
     if (h->nu > 16) { h->err = "tmpc_mc_open: nu <= 16"; return TMPC_E_UNSUPPORTED; }
+    if (full_ref)
+        if (const int r2 = reference_table_fits(h, "tmpc_mc_open", B, T)) return r2;
     int rc = begin_loop(h, B);
     if (rc) return rc;
     const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(B), t_ = static_cast<size_t>(T);
@@ -1571,14 +1642,18 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
         double *x_stage = nullptr, *u_stage = nullptr;
         a.piece(&x_stage, b * nx * 8, nullptr, 0);
         a.piece(&u_stage, b * nu * 8, nullptr, 0);
+        if (full_ref) {
+            reference_table_pieces(h, a, st);
+            a.piece(&s.ref_stage, b * nx * 8, nullptr, 0);
+        }
         HIP_TRY(h, a.carve(h->stream));
         ext.x_t = x_stage;
         ext.u_t = u_stage;
-        HIP_TRY(h, tmpc::launch_mc_pre(m, st, B, ref[0], h->stream));
+        HIP_TRY(h, tmpc::launch_mc_pre(m, st, B, full_ref ? 0.0 : ref[0], h->stream));
         HIP_TRY(h, hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
         HIP_TRY(h, hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
         // (the pinned block is a convenience: without it tmpc_mc_step copies from / to the caller's memory)
-        if (hipHostMalloc(reinterpret_cast<void **>(&s.pin), b * (nx + nu) * 8, hipHostMallocDefault) != hipSuccess) {
+        if (hipHostMalloc(reinterpret_cast<void **>(&s.pin), b * (nx + nu + (full_ref ? nx : 0)) * 8, hipHostMallocDefault) != hipSuccess) {
             s.pin = nullptr;
             (void)hipGetLastError();
         }
@@ -1591,7 +1666,9 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
         release_session(h);
         return rc;
     }
-    s.ref.assign(ref, ref + T);
+    if (full_ref) s.ref.assign(t_, 0.0);       // (not read on the device in full-reference mode)
+    else s.ref.assign(ref, ref + T);
+    s.full_ref = full_ref;
     s.B = B; s.T = T; s.t = 0; s.extended = extended ? 1 : 0;
     s.open = true;
     return TMPC_OK;
@@ -1600,7 +1677,8 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
 namespace {
 // One step of the open session on the handle's stream: the solve launch(es) on x_hat_t, then -- behind `caller` (a stream, or
 // nullptr) -- the state machines around the given x_t / u_t.
-int session_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t, hipStream_t caller) {
+// ref_next (device, or nullptr: the schedule's row) is read by the same launch as x_t.
+int session_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t, hipStream_t caller, const double *ref_next = nullptr) {
     McSession &s = h->ses;
     if (!s.open) { h->err = std::string(who) + ": no stepped closed loop is open on this handle (tmpc_mc_open)"; return TMPC_E_INVALID; }
     if (s.failed) { h->err = std::string(who) + ": an earlier step of the session failed on the device; only tmpc_mc_close is left"; return TMPC_E_INVALID; }
@@ -1621,6 +1699,7 @@ int session_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t
         tmpc::McExternal ext = s.ext;
         ext.x_t = x_t;
         ext.u_t = u_t;
+        ext.ref_next = ref_next;
         const int t = s.t;
         HIP_TRY(h, tmpc::launch_mc_step_external(s.m, st, ext, t, s.T, s.B, s.ref[t], s.ref[t + 1 < s.T ? t + 1 : t], h->d_u, h->d_x0, h->d_ss,
                                                  h->d_st, h->d_it, h->stream));
@@ -1642,10 +1721,38 @@ int tmpc_mc_step_device(tmpc_handle *h, const double *x_t, double *u_t, void *ca
     return session_step(h, "tmpc_mc_step_device", x_t, u_t, static_cast<hipStream_t>(caller_stream));
 }
 
+namespace {
+// the _ref steps need a session opened in full-reference mode; refusing one leaves the session as it is
+bool ref_step_barred(tmpc_handle *h, const char *who) {
+    if (!h->ses.open || h->ses.full_ref) return false;      // (no session: session_step's message)
+    h->err = std::string(who) + ": the session was opened without a reference table (tmpc_mc_set_reference_table before tmpc_mc_open)";
+    return true;
+}
+int host_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t, const double *ref_next);
+}  // namespace
+
+int tmpc_mc_step_device_ref(tmpc_handle *h, const double *x_t, double *u_t, const double *ref_next, void *caller_stream) {
+    if (!h) return TMPC_E_INVALID;
+    if (ref_step_barred(h, "tmpc_mc_step_device_ref")) return TMPC_E_INVALID;
+    return session_step(h, "tmpc_mc_step_device_ref", x_t, u_t, static_cast<hipStream_t>(caller_stream), ref_next);
+}
+
 int tmpc_mc_step(tmpc_handle *h, const double *x_t, double *u_t) {
     if (!h) return TMPC_E_INVALID;
+    return host_step(h, "tmpc_mc_step", x_t, u_t, nullptr);
+}
+
+int tmpc_mc_step_ref(tmpc_handle *h, const double *x_t, double *u_t, const double *ref_next) {
+    if (!h) return TMPC_E_INVALID;
+    if (ref_step_barred(h, "tmpc_mc_step_ref")) return TMPC_E_INVALID;
+    return host_step(h, "tmpc_mc_step_ref", x_t, u_t, ref_next);
+}
+
+namespace {
+// tmpc_mc_step[_ref]: HOST pointers, one DMA each way through the session's pinned block
+int host_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t, const double *ref_next) {
     McSession &s = h->ses;
-    if (!s.open || s.failed || !x_t || !u_t || s.t >= s.T) return session_step(h, "tmpc_mc_step", x_t, u_t, nullptr);     // (its message and code)
+    if (!s.open || s.failed || !x_t || !u_t || s.t >= s.T) return session_step(h, who, x_t, u_t, nullptr);     // (its message and code)
     const size_t xb = static_cast<size_t>(s.B) * h->nx * 8, ub = static_cast<size_t>(s.B) * h->nu * 8;
     double *const d_x = const_cast<double *>(s.ext.x_t), *const d_u = s.ext.u_t;
     auto copies = [&](bool in) -> int {
@@ -1653,6 +1760,10 @@ int tmpc_mc_step(tmpc_handle *h, const double *x_t, double *u_t) {
         if (in) {
             if (s.pin) std::memcpy(s.pin, x_t, xb);
             HIP_TRY(h, hipMemcpyAsync(d_x, s.pin ? static_cast<const void *>(s.pin) : x_t, xb, hipMemcpyHostToDevice, h->stream));
+            if (ref_next) {
+                if (s.pin) std::memcpy(s.pin + xb + ub, ref_next, xb);
+                HIP_TRY(h, hipMemcpyAsync(s.ref_stage, s.pin ? static_cast<const void *>(s.pin + xb + ub) : ref_next, xb, hipMemcpyHostToDevice, h->stream));
+            }
         } else {
             HIP_TRY(h, hipMemcpyAsync(s.pin ? static_cast<void *>(s.pin + xb) : u_t, d_u, ub, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, sync_lanes(h));
@@ -1661,11 +1772,12 @@ int tmpc_mc_step(tmpc_handle *h, const double *x_t, double *u_t) {
         return TMPC_OK;
     };
     int rc = copies(true);
-    if (rc == TMPC_OK) rc = session_step(h, "tmpc_mc_step", d_x, d_u, nullptr);
+    if (rc == TMPC_OK) rc = session_step(h, who, d_x, d_u, nullptr, ref_next ? s.ref_stage : nullptr);
     if (rc == TMPC_OK) rc = copies(false);
     if (rc != TMPC_OK) { s.failed = true; (void)sync_lanes(h); }
     return rc;
 }
+}  // namespace
 
 int tmpc_mc_close(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_viol, int32_t *u_viol, int32_t *not_optimal,
                   double *consistent, int32_t *iters_sum, int32_t *steps_done) {

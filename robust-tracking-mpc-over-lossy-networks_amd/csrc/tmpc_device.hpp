@@ -176,6 +176,10 @@ struct McState {                         // all [trajectory]-major device arrays
     const double *rp_xn0;                     // [B][T][nx]      x_nom_0 of the packets (extended controller)
     double *trace_f;                          // [B][T][3 nx + nu]: x_{t+1}, x_hat_{t+1}, nominal state of the plant's packet, u_t; or nullptr
     int32_t *trace_i;                         // [B][T][3]: s_t, Theta_t, q_t (the controller's packet)
+    // full-state reference schedules (tmpc_mc_set_reference_table), or nullptr: the reference of step t is [ref_t, 0, ..]
+    const double *ref_tab;                    // [K][ref_T][nx] schedules
+    const int32_t *ref_id;                    // [B] schedule of every trajectory
+    int ref_T;                                // rows of a schedule (>= T)
 };
 // The caller's side of the stepped closed loop (tmpc_mc_open / tmpc_mc_step_device, m.plant = TMPC_PLANT_EXTERNAL): the plant
 // state of this step comes from the caller and the applied input goes back; X and U are the caller's check sets for the two.
@@ -185,9 +189,10 @@ struct McExternal {
     int rX, rU;                          // rows of the check sets (0: no check)
     const double *HX, *hX, *HU, *hU;
     int32_t *x_viol, *u_viol;            // steps with x_t outside X / u_t outside U                           [B]
+    const double *ref_next;              // reference of the NEXT solve, given by the caller, or nullptr: the schedule's row  [B][nx]
 };
 hipError_t launch_mark_invalid_variants(const BatchIO &io, int nvariants, int nx, int nu, int N, hipStream_t stream);
-// one launch before the first solve (reference of step 0), then one launch per time step after the solve launch(es)
+// one launch before the first solve (reference of step 0: [ref_0, 0, ..], or row 0 of each trajectory's schedule), then one launch per time step after the solve launch(es)
 hipError_t launch_mc_pre(const McModel &m, const McState &st, int64_t B, double ref_0, hipStream_t stream);
 hipError_t launch_mc_step(const McModel &m, const McState &st, int t, int T, int64_t B, double ref_t, double ref_next, const double *u_nom,
                           const double *x_nom0, const double *xu_ss, const int32_t *status, const int32_t *iters, hipStream_t stream);

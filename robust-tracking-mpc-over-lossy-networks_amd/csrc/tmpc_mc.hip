@@ -27,10 +27,16 @@ namespace {
 
 using namespace mcstep;
 
-// reference handed to the first solve: ref = [ref_0, 0, ..] (:240); the later ones are written by mc_step_kernel
+// reference handed to the first solve: ref = [ref_0, 0, ..] (:240), or row 0 of the trajectory's schedule; the later ones are
+// written by mc_step_kernel
 __global__ void mc_pre_kernel(const McModel m, const McState st, const int64_t B, const double ref_0) {
     const int64_t b = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    if (st.ref_tab) {
+        const double *row = st.ref_tab + static_cast<int64_t>(st.ref_id[b]) * st.ref_T * m.nx;
+        for (int i = 0; i < m.nx; ++i) st.ref_k[b * m.nx + i] = row[i];
+        return;
+    }
     for (int i = 0; i < m.nx; ++i) st.ref_k[b * m.nx + i] = (i == 0) ? ref_0 : 0.0;
 }
 

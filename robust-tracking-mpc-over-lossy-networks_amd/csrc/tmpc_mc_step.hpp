@@ -100,6 +100,10 @@ enum { V_X = 0, V_XN, V_E, V_ET, V_U, V_UN, V_BASE, V_TMP, V_COUNT };
 // are checked against the caller's sets X and U, the nominal model and the estimator advance as ever, and no plant state and no
 // disturbance is read, drawn or written.  A template parameter, not a branch on m.plant: the solve kernels that inline this function
 // keep their code and their registers, and the caller's record is an argument of the one kernel that has a caller.
+//
+// st.ref_tab != nullptr (tmpc_mc_set_reference_table, "full-reference mode"): the reference of a solve is a full state, row t of the
+// trajectory's schedule st.ref_tab[st.ref_id[b]] (or, EXT, the caller's ext.ref_next), and the tracking error is |x_t - r_t|^2 over all
+// nx components against the reference the solve of step t used; ref_t / ref_next are then not read.  One wave-uniform branch.
 template <bool EXT, class ModelRec, class StateRec>
 __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &st, const int t, const int T, const int64_t b,
                                              const double ref_t, const double ref_next,
@@ -113,6 +117,9 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
         return false;
     }
     const bool replay = st.rp_U != nullptr;      // packets injected by the caller instead of solved (tmpc_mc_replay)
+    // full-state reference schedules (tmpc_mc_set_reference_table): wave-uniform.  Read here, beside the record's other fields: where
+    // the record is read through the constant address space (the fused kernels) the scalar load goes out with theirs
+    const bool full_ref = st.ref_tab != nullptr;
     const bool lx = lane < nx, lu = lane < nu;
     const double p = st.p_loss[b];
     double th_draw, ga_draw, w_l;
@@ -210,7 +217,35 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
         if (lu) c[2 * nx + lane] = u_l;
     }
     // ---- statistics (results_linear_system.py:258, 291)
-    if (lane == 0) {
+    double rn_l = 0.0;                                // full_ref: component `lane` of the next solve's reference
+    double rp[4] = {0.0, 0.0, 0.0, 0.0};              // full_ref, cart-pole plant: the reference of this step
+    if (full_ref) {
+        // r_t = the reference this step's solve used (st.ref_k as the step finds it), handed round through V_TMP (free until the
+        // estimator); the sum rounds like the legacy one when r_t = [ref_t, 0, ..]: x - 0 is exact, same order, same contraction
+        const double r_l = lx ? st.ref_k[b * nx + lane] : 0.0;
+        // the next reference: one coalesced load of nx doubles -- the caller's array, or row min(t+1, T-1) of the trajectory's
+        // schedule (b, the id and the row are wave-uniform: a scalar base, the lane as the offset)
+        const double *nxt;
+        bool given = false;
+        if constexpr (EXT) given = ext.ref_next != nullptr;
+        if (given) {
+            nxt = ext.ref_next + b * nx;
+        } else {
+            const int id = __builtin_amdgcn_readfirstlane(st.ref_id[b]);
+            nxt = st.ref_tab + (static_cast<int64_t>(id) * st.ref_T + (t + 1 < T ? t + 1 : t)) * nx;
+        }
+        if (lx) rn_l = nxt[lane];
+        if (lane < MAXN) S[V_TMP][lane] = r_l;
+        mc_fence();
+        if (lane == 0) {
+            double a = (S[V_X][0] - S[V_TMP][0]) * (S[V_X][0] - S[V_TMP][0]);
+            for (int i = 1; i < nx; ++i) a += (S[V_X][i] - S[V_TMP][i]) * (S[V_X][i] - S[V_TMP][i]);
+            st.err2[b] += a;
+        }
+        if (!EXT && m.plant == TMPC_PLANT_CARTPOLE)
+            for (int i = 0; i < 4; ++i) rp[i] = S[V_TMP][i];
+        mc_fence();
+    } else if (lane == 0) {
         double a = (S[V_X][0] - ref_t) * (S[V_X][0] - ref_t);
         for (int i = 1; i < nx; ++i) a += S[V_X][i] * S[V_X][i];
         st.err2[b] += a;
@@ -267,7 +302,13 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
         double aphys = 0.0;       // tracking error at the physics rate (results_nonlinear_system.py:361: x_traj[:, 0:-1], 500 Hz)
         for (int sstep = 0; sstep < m.substeps; ++sstep) {
             double k1[4], k2[4], k3[4], k4[4], yt[4];
-            aphys += (y[0] - ref_t) * (y[0] - ref_t) + y[1] * y[1] + y[2] * y[2] + y[3] * y[3];
+            if (full_ref) {
+                // the legacy sum below as the compiler contracts it -- the first term a product, the others fused onto it in index
+                // order -- spelled out: left to the compiler, d0 d0 + d1 d1 becomes fma(d0, d0, d1 d1), which rounds the other product
+                double e = (y[0] - rp[0]) * (y[0] - rp[0]);
+                for (int i = 1; i < 4; ++i) e = fma(y[i] - rp[i], y[i] - rp[i], e);
+                aphys += e;
+            } else aphys += (y[0] - ref_t) * (y[0] - ref_t) + y[1] * y[1] + y[2] * y[2] + y[3] * y[3];
             cartpole_rhs(par, y, u0, k1);
             for (int i = 0; i < 4; ++i) yt[i] = y[i] + 0.5 * dt * k1[i];
             cartpole_rhs(par, yt, u0, k2);
@@ -322,7 +363,8 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
         }
     }
     if (lane == 0) (gamma_out ? gamma_out : st.gamma)[b] = static_cast<uint8_t>(gamma);
-    if (lx) st.ref_k[b * nx + lane] = (lane == 0) ? ref_next : 0.0;      // ref = [ref_{t+1}, 0, ..] of the next solve (:240)
+    if (full_ref) { if (lx) st.ref_k[b * nx + lane] = rn_l; }             // the schedule's (or the caller's) reference of the next solve
+    else if (lx) st.ref_k[b * nx + lane] = (lane == 0) ? ref_next : 0.0;      // ref = [ref_{t+1}, 0, ..] of the next solve (:240)
     if (!EXT && st.trace_f) {
         // every step of every trajectory (tmpc_mc_replay): x_{t+1}, x_hat_{t+1}, the nominal state of the plant's packet, u_t;
         // s_t, Theta_t and the q_t the controller put into its packet
