@@ -509,6 +509,46 @@ int tmpc_mc_set_reference_table(tmpc_handle *h, int32_t K, int32_t T_tab, const 
 int tmpc_mc_step_device_ref(tmpc_handle *h, const double *x_t, double *u_t, const double *ref_next, void *caller_stream);
 int tmpc_mc_step_ref(tmpc_handle *h, const double *x_t, double *u_t, const double *ref_next);
 /*
+ * Bursty packet loss: a two-state Markov (Gilbert-Elliott) channel per link, and per-trajectory link statistics.
+ *
+ * The model.  Each of the two links of a trajectory (controller -> plant, plant -> controller) has a state in {G, B}.  Trajectory b
+ * has four parameters, shared by its two links as p_loss is:
+ *   p_gb = P(B at t | G at t-1),  p_bg = P(G at t | B at t-1),  e_g / e_b = loss probability in state G / B.
+ * One uniform u per link and step decides the transition and the loss -- the step's th_u / ga_u entry, or its Philox block-0 words
+ * (tmpc_mc_set_device_rng): the draw layout and every stream are those of the Bernoulli model.  With a = P(B | previous state),
+ * i.e. p_gb after G and 1 - p_bg after B:
+ *   u < a e_b                 (B, lost)
+ *   else u < a                (B, arrives)
+ *   else u < a + (1 - a) e_g  (G, lost)
+ *   else                      (G, arrives)
+ * The comparisons are strict, like the Bernoulli model's u < p_loss.  Both links start in G.  At t = 0 the packet arrives and the
+ * state does not move (the draw of t = 0 is ignored, as ever).  A failed solve (status >= 2) still sends nothing (theta = 0), but
+ * the channel's state follows the draw alone.  The three thresholds per previous state -- thr[b][prev][0..3) = a e_b, a,
+ * a + (1 - a) e_g with prev = 0 (G), 1 (B) -- are computed once per trajectory on the host, every product and sum rounded on its
+ * own (no fused multiply-add); the device only compares.  Hence p_gb = 0, e_g = p gives (0, 0, p) after G: the Bernoulli flags of
+ * p_loss = p, bit for bit; and p_gb = 1, p_bg = 0, e_b = 1 loses every packet after step 0.
+ *
+ * tmpc_mc_set_channel: p_gb, p_bg, e_g, e_b are HOST arrays of B entries, copied.  B == 0 clears the setting (the arrays are then
+ * ignored).  Works on a host-only handle.  While a channel is set, tmpc_mc_run and tmpc_mc_open need their B equal to the channel's
+ * (TMPC_E_INVALID otherwise) and do not read p_loss, which may be NULL; a session honours the channel as set when it was opened.
+ * tmpc_mc_replay takes its arrival flags as given and ignores the channel; regulator handles have no network.
+ * TMPC_E_INVALID: a regulator handle, an open session, B < 0, a NULL array with B > 0, a probability outside [0, 1] or NaN.
+ *
+ * tmpc_mc_get_channel: the thresholds as they are uploaded, thr[B][2][3] (B * 6 doubles); TMPC_E_INVALID unless B is the channel's.
+ *
+ * tmpc_mc_get_link_stats: per trajectory of the last tmpc_mc_run, or of the session tmpc_mc_close just ended -- kept with either
+ * loss model, any pointer may be NULL:
+ *   lost_up    steps t > 0 whose controller -> plant packet the CHANNEL dropped (a packet withheld after a failed solve is not counted)
+ *   lost_down  the same for the plant -> controller packet
+ *   max_gap    max_t (t - s_t): the largest age of the sequence the actuator played
+ *   overrun    steps with t - s_t >= N: the buffered sequence was exhausted and the terminal law Ub[N] - K x_nom applied
+ * A trajectory of the smart actuator that has stopped counts nothing from the step of its infeasible solve on.
+ * TMPC_E_INVALID: no such run, or another B.  Added without an ABI bump.
+ */
+int tmpc_mc_set_channel(tmpc_handle *h, int64_t B, const double *p_gb, const double *p_bg, const double *e_g, const double *e_b);
+int tmpc_mc_get_channel(tmpc_handle *h, int64_t B, double *thr);
+int tmpc_mc_get_link_stats(tmpc_handle *h, int64_t B, int32_t *lost_up, int32_t *lost_down, int32_t *max_gap, int32_t *overrun);
+/*
  * With a nonlinear plant tmpc_mc_run also sums |x - ref|^2 over the T * substeps physics steps (the state at the start of
  * every physics step, i.e. x_traj[:, 0:-1] of results_nonlinear_system.py:361, whose tracking error is taken at 500 Hz);
  * copied out per trajectory by tmpc_mc_get_physics_error (NaN for an R-MPC trajectory that stopped).

@@ -133,6 +133,12 @@ def lib():
         L.tmpc_mc_step_device_ref.restype = C.c_int
         L.tmpc_mc_step_ref.argtypes = [C.c_void_p] * 4
         L.tmpc_mc_step_ref.restype = C.c_int
+        L.tmpc_mc_set_channel.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+        L.tmpc_mc_set_channel.restype = C.c_int
+        L.tmpc_mc_get_channel.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.tmpc_mc_get_channel.restype = C.c_int
+        L.tmpc_mc_get_link_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+        L.tmpc_mc_get_link_stats.restype = C.c_int
         L.tmpc_mc_close.argtypes = [C.c_void_p] * 9
         L.tmpc_mc_close.restype = C.c_int
         L.tmpc_mc_replay.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 8
@@ -530,11 +536,72 @@ def _loop_reference(h: Handle, who: str, ref, B: int, T, ref_id, flatten_legacy:
     return legacy, T
 
 
+def mc_set_channel(h: Handle, channel=None, B=None):
+    """include/tmpc.h: tmpc_mc_set_channel -- the Gilbert-Elliott loss channel of the next closed loops.  channel: a dict with
+    p_gb, p_bg, e_g, e_b (montecarlo.burst_channel returns one) or these four in a sequence, each a scalar or (B,); B: the batch of
+    the loops (default: the longest parameter).  None clears the setting: independent losses with probability p_loss.  Returns the
+    channel's batch size (None when cleared)."""
+    if channel is None:
+        if lib().tmpc_mc_set_channel(h.ptr, 0, None, None, None, None) != 0:
+            raise RuntimeError(h.error())
+        return None
+    from .montecarlo import channel_parameters
+    par = channel_parameters(channel, B)
+    rc = lib().tmpc_mc_set_channel(h.ptr, par[0].shape[0], *[v.ctypes.data for v in par])
+    if rc != 0:
+        raise RuntimeError(f"tmpc_mc_set_channel failed ({rc}): {h.error()}")
+    return par[0].shape[0]
+
+
+def loop_batch(who: str, p_loss, channel, th_u=None, x0=None, ref_id=None, nx=None):
+    """The batch of a closed loop and its loss model -> (p_loss (B,) or None, the channel's four (B,) arrays or None, B).  Without a
+    channel p_loss gives B.  With one p_loss is not used, and B comes from p_loss if given, else from the rows of th_u, of x0, the
+    length of ref_id, or the longest channel parameter; a channel of scalars with none of these has no batch: ValueError.  Nothing is
+    set on a handle here: the loops set the channel once their other arguments have been checked."""
+    from .montecarlo import channel_parameters
+    if channel is None:
+        if p_loss is None:
+            raise ValueError(f"{who}: p_loss or channel")
+        p_loss = np.ascontiguousarray(np.asarray(p_loss, dtype=np.float64))
+        return p_loss, None, p_loss.shape[0] if p_loss.ndim else 1
+    B = None
+    if p_loss is not None:
+        B = np.asarray(p_loss).size
+    elif th_u is not None:
+        B = np.shape(th_u)[0]
+    elif x0 is not None:
+        B = np.asarray(x0).reshape(-1, nx).shape[0] if nx else np.shape(x0)[0]
+    elif ref_id is not None:
+        B = np.asarray(ref_id).size
+    par = channel_parameters(channel, B)
+    if B is None and par[0].shape[0] == 1 and all(np.ndim(v) == 0 for v in (channel.values() if isinstance(channel, dict) else channel)):
+        raise ValueError(f"{who}: a channel of scalars does not say how many trajectories to run: give p_loss, th_u, x0 or ref_id, or "
+                         "one of the channel's parameters per trajectory")
+    return None, par, par[0].shape[0]
+
+
+def mc_get_channel(h: Handle, B: int):
+    """include/tmpc.h: tmpc_mc_get_channel -- the thresholds (B, 2, 3) of the channel that is set, as the device compares them."""
+    thr = np.empty((int(B), 2, 3))
+    if lib().tmpc_mc_get_channel(h.ptr, int(B), thr.ctypes.data) != 0:
+        raise RuntimeError(h.error())
+    return thr
+
+
+def mc_link_stats(h: Handle, B: int) -> dict:
+    """include/tmpc.h: tmpc_mc_get_link_stats -- lost_up, lost_down, max_gap, overrun (B,) int32 of the last loop."""
+    out = {k: np.empty(int(B), np.int32) for k in ("lost_up", "lost_down", "max_gap", "overrun")}
+    if lib().tmpc_mc_get_link_stats(h.ptr, int(B), *[v.ctypes.data for v in out.values()]) != 0:
+        raise RuntimeError(h.error())
+    return out
+
+
 MC_FUSED = {"off": 0, "on": 1, "auto": 2, False: 0, True: 1, None: 2}      # include/tmpc.h: TMPC_MC_FUSED_*
 
 
 def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: bool = False, warm_start: bool = False,
-           capture=None, timing: bool = False, physics_substeps: int = 0, device_rng=None, fused=None, ref_id=None, T=None) -> dict:
+           capture=None, timing: bool = False, physics_substeps: int = 0, device_rng=None, fused=None, ref_id=None, T=None,
+           channel=None) -> dict:
     """include/tmpc.h: tmpc_mc_run -- the closed loop over the lossy network, resident on the device.
     warm_start: tmpc_mc_set_warm_start for this call; capture: index of a trajectory to record (tmpc_mc_set_capture) ->
     x_traj (T, nx), x_nom_traj (T, nx), u_traj (T, nu) in the result; timing: per trajectory the mean and the maximum
@@ -549,7 +616,10 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     ref: (T,) position reference of the whole batch (the solve gets [ref_t, 0, ..]); or full-state references through
     tmpc_mc_set_reference_table -- (T, nx) one schedule, (B, T, nx) one per trajectory, (K, T, nx) with ref_id (B,) K shared
     schedules, (nx,) together with T (more than nx steps) a constant full state; the tracking error is then |x_t - r_t| over
-    all states.  A (T,) call clears an earlier table.  T: the steps (default: the draws' or the reference's)."""
+    all states.  A (T,) call clears an earlier table.  T: the steps (default: the draws' or the reference's).
+    channel: the Gilbert-Elliott loss channel of this call (mc_set_channel; None: independent losses with probability p_loss, and
+    an earlier channel is cleared); p_loss is then not read and may be None.  The result carries the link statistics lost_up,
+    lost_down, max_gap, overrun (also as the dict link_stats) with either loss model."""
     if lib().tmpc_set_solve_timing(h.ptr, int(bool(timing))) != 0:
         raise RuntimeError(h.error())
     if lib().tmpc_mc_set_fused(h.ptr, MC_FUSED[fused]) != 0:
@@ -559,23 +629,25 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     if lib().tmpc_mc_set_capture(h.ptr, -1 if capture is None else int(capture)) != 0:
         raise RuntimeError(h.error())
     c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-    p_loss = c(p_loss)
+    p_loss, ch_par, n_traj = loop_batch("mc_run", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if T is None and device_rng is None and th_u is not None:
         T = np.shape(th_u)[1]
-    ref, T_ref = _loop_reference(h, "mc_run", ref, p_loss.shape[0], T, ref_id)
+    ref, T_ref = _loop_reference(h, "mc_run", ref, n_traj, T, ref_id)
     if device_rng is not None:
         seed, first, w_bound = device_rng
         wb = None if w_bound is None else c(w_bound).reshape(h.nx)
         if lib().tmpc_mc_set_device_rng(h.ptr, 1, int(seed), int(first), None if wb is None else wb.ctypes.data) != 0:
             raise RuntimeError(h.error())
         th_u = ga_u = w = None
-        B, T = p_loss.shape[0], T_ref
+        B, T = n_traj, T_ref
     else:
         if lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None) != 0:
             raise RuntimeError(h.error())
         th_u, ga_u, w = c(th_u), c(ga_u), c(w)
         B, T = th_u.shape
-        if ga_u.shape != (B, T) or w.shape != (B, T, h.nx) or p_loss.shape != (B,) or (ref is not None and ref.shape != (T,)) or T_ref < T:
+        if ch_par is not None and ch_par[0].shape[0] != B:
+            raise ValueError(f"mc_run: the channel holds {ch_par[0].shape[0]} trajectories, the draws {B}")
+        if ga_u.shape != (B, T) or w.shape != (B, T, h.nx) or (p_loss is not None and p_loss.shape != (B,)) or (ref is not None and ref.shape != (T,)) or T_ref < T:
             raise ValueError("mc_run: inconsistent shapes" + (f" (a constant full-state reference over T <= nx = {h.nx} steps is (1, nx): "
                                                               "(nx,) is then read as the legacy (T,) form)" if ref is not None and ref.shape == (h.nx,) else ""))
     x0c = None if x0 is None else c(x0).reshape(B, h.nx)
@@ -587,11 +659,14 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     out = dict(err2=np.empty(B), tube_violations=np.empty(B, np.int32), not_optimal=np.empty(B, np.int32),
                x_final=np.empty((B, h.nx)), consistent=np.empty(B), iters_sum=np.empty(B, np.int32))
     ptr = lambda a: None if a is None else a.ctypes.data
+    mc_set_channel(h, ch_par)            # (None clears an earlier one; set last, so that no refused call leaves its channel behind)
     rc = lib().tmpc_mc_run(h.ptr, B, T, int(bool(extended)), ptr(p_loss), ptr(ref), ptr(th_u), ptr(ga_u), ptr(w), ptr(x0c),
                            ptr(HZ), ptr(hZ), rZ, ptr(out["err2"]), ptr(out["tube_violations"]), ptr(out["not_optimal"]),
                            ptr(out["x_final"]), ptr(out["consistent"]), ptr(out["iters_sum"]))
     if rc != 0:
-        raise RuntimeError(f"tmpc_mc_run failed ({rc}): {h.error()}")
+        msg = h.error()
+        mc_set_channel(h, None)          # a refused loop leaves no channel behind
+        raise RuntimeError(f"tmpc_mc_run failed ({rc}): {msg}")
     if capture is not None:
         out["x_traj"], out["x_nom_traj"], out["u_traj"] = np.empty((T, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))
         if lib().tmpc_mc_get_capture(h.ptr, T, ptr(out["x_traj"]), ptr(out["x_nom_traj"]), ptr(out["u_traj"])) != 0:
@@ -606,6 +681,8 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
         if lib().tmpc_mc_get_physics_error(h.ptr, B, ptr(out["err2_physics"])) != 0:
             raise RuntimeError(h.error())
         out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * physics_substeps)
+    out["link_stats"] = mc_link_stats(h, B)
+    out.update(out["link_stats"])
     out["loop_mode"] = int(lib().tmpc_mc_last_fused(h.ptr))       # 1: one launch per sweep; 2: one launch per problem and step; 0: + a state-machine launch
     out["fused"] = out["loop_mode"] == 1
     out["tracking_error"] = np.sqrt(out["err2"]) / T
@@ -626,15 +703,18 @@ def _check_set(P, dim: int, who: str):
 
 
 def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=None, X=None, U=None, extended: bool = False,
-            warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None) -> dict:
+            warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, channel=None) -> dict:
     """include/tmpc.h: tmpc_mc_open -- opens the stepped closed loop around a plant of the caller's.  p_loss (B,), ref (T,)
     or a full-state form (mc_run; (nx,) together with T: a constant full state -- the table of a session steered by ref_next),
     th_u / ga_u (B, T) loss uniforms (None with device_rng = (seed, first_trajectory[, ignored]): Philox block 0, the draws of
     mc_run), x0 (B, nx) or None; T: steps the session may take (default: len(ref)); Z / X / U: tube cross-section and the check
-    sets for x_t / u_t (polytopes or None).  No disturbance is drawn: w is the plant's.  Returns what mc_close needs."""
+    sets for x_t / u_t (polytopes or None).  No disturbance is drawn: w is the plant's.  channel: the Gilbert-Elliott loss channel of
+    the session (mc_run; p_loss may then be None).  Returns what mc_close needs."""
     c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))      # noqa: E731
-    p_loss = c(p_loss).reshape(-1)
-    B = p_loss.shape[0]
+    p_loss, ch_par, B = loop_batch("mc_open", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
+    if p_loss is not None:
+        p_loss = p_loss.reshape(-1)
+        B = p_loss.shape[0]
     ref, T_ref = _loop_reference(h, "mc_open", ref, B, T, ref_id, flatten_legacy=True)
     T = T_ref if T is None else int(T)
     if (ref.shape[0] if ref is not None else T_ref) < T:
@@ -658,10 +738,13 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
     HX, hX, rX = _check_set(X, h.nx, "mc_open")
     HU, hU, rU = _check_set(U, h.nu, "mc_open")
     ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+    mc_set_channel(h, ch_par)            # (as in mc_run: last)
     rc = lib().tmpc_mc_open(h.ptr, B, T, int(bool(extended)), ptr(p_loss), ptr(ref), ptr(th_u), ptr(ga_u), ptr(x0c),
                             ptr(HZ), ptr(hZ), rZ, ptr(HX), ptr(hX), rX, ptr(HU), ptr(hU), rU)
     if rc != 0:
-        raise RuntimeError(f"tmpc_mc_open failed ({rc}): {h.error()}")
+        msg = h.error()
+        mc_set_channel(h, None)          # (no session was opened: the setter is free)
+        raise RuntimeError(f"tmpc_mc_open failed ({rc}): {msg}")
     return dict(B=B, T=T, capture=capture, timing=bool(timing), full_ref=ref is None)
 
 
@@ -715,6 +798,8 @@ def mc_close(h: Handle, info: dict) -> dict:
                                                                    "not_optimal", "consistent", "iters_sum")], C.addressof(steps))
     if rc != 0:
         raise RuntimeError(f"tmpc_mc_close failed ({rc}): {h.error()}")
+    out["link_stats"] = mc_link_stats(h, B)
+    out.update(out["link_stats"])
     n = out["steps"] = int(steps.value)
     if info.get("capture") is not None:
         xt, xn, ut = np.empty((T, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))

@@ -139,8 +139,111 @@ def draw_realisations_reference_order(p_loss, n_mc: int, T: int, w_bound, seeds=
     return np.repeat(p_loss, int(n_mc)), th, ga, w
 
 
+# --------------------------------------------------------------------------- bursty losses: the Gilbert-Elliott channel
+def channel_parameters(channel, n_traj=None):
+    """The `channel` argument of the closed loops -> (p_gb, p_bg, e_g, e_b), four float64 arrays of n_traj entries: a dict with these
+    keys (burst_channel returns one) or a sequence in this order; scalars are shared by the batch."""
+    if isinstance(channel, dict):
+        channel = [channel[k] for k in ("p_gb", "p_bg", "e_g", "e_b")]
+    par = [np.asarray(v, dtype=np.float64).reshape(-1) for v in channel]
+    if len(par) != 4:
+        raise ValueError("channel: (p_gb, p_bg, e_g, e_b)")
+    n = max(v.size for v in par) if n_traj is None else int(n_traj)
+    if any(v.size not in (1, n) for v in par):
+        raise ValueError(f"channel: every parameter is a scalar or holds one entry per trajectory ({n})")
+    par = [np.ascontiguousarray(np.broadcast_to(v, (n,))) for v in par]
+    if any(not np.all((v >= 0.0) & (v <= 1.0)) for v in par):
+        raise ValueError("channel: p_gb, p_bg, e_g, e_b are probabilities")
+    return tuple(par)
+
+
+def gilbert_elliott_thresholds(p_gb, p_bg, e_g, e_b):
+    """The thresholds the device compares a link's uniform against (include/tmpc.h: tmpc_mc_set_channel), (n, 2, 3): with
+    a = P(B | previous state) = p_gb after G (index 0), 1 - p_bg after B (index 1), thr = [a e_b, a, a + (1 - a) e_g]; every product
+    and sum rounded on its own, as the library computes them (tmpc_mc_get_channel returns the same bits)."""
+    p_gb, p_bg, e_g, e_b = channel_parameters((p_gb, p_bg, e_g, e_b))
+    a = np.stack([p_gb, 1.0 - p_bg], axis=1)                                   # (n, 2)
+    return np.ascontiguousarray(np.stack([a * e_b[:, None], a, a + (1.0 - a) * e_g[:, None]], axis=2))
+
+
+def channel_arrivals(channel, th_u, ga_u):
+    """The numpy twin of the device's loss channel: channel (see channel_parameters) and the uniforms th_u, ga_u (B, T) of the two
+    links -> dict(theta, gamma: arrival flags (B, T), 1 = arrives; state_up, state_down: the links' states after the draw of step t
+    (B, T), 0 = G, 1 = B).  u < thr[0]: (B, lost); else u < thr[1]: (B, arrives); else u < thr[2]: (G, lost); else (G, arrives) --
+    strict comparisons; both links start in G; at t = 0 the packet arrives and the state stays."""
+    th_u, ga_u = np.asarray(th_u, dtype=np.float64), np.asarray(ga_u, dtype=np.float64)
+    nb, T = th_u.shape
+    thr = gilbert_elliott_thresholds(*channel_parameters(channel, nb))
+    rows = np.arange(nb)
+    out = {}
+    for name, sname, u in (("theta", "state_up", th_u), ("gamma", "state_down", ga_u)):
+        flag = np.ones((nb, T), dtype=np.uint8)
+        state = np.zeros((nb, T), dtype=np.uint8)
+        if nb < 8:                                # a few long chains: plain Python floats, a trajectory at a time -- the table below, entry for entry
+            for b in range(nb):
+                tb, ub, s = thr[b].tolist(), u[b].tolist(), 0
+                for t in range(1, T):
+                    r, v = tb[s], ub[t]
+                    lost = 1 if v < r[0] else (0 if v < r[1] else (1 if v < r[2] else 0))
+                    s = 1 if (v < r[0] or v < r[1]) else 0
+                    flag[b, t], state[b, t] = 1 - lost, s
+            out[name], out[sname] = flag, state
+            continue
+        s = np.zeros(nb, dtype=np.int64)
+        for t in range(1, T):
+            r = thr[rows, s]                                                   # (B, 3): the thresholds of the previous state
+            lost = np.where(u[:, t] < r[:, 0], 1, np.where(u[:, t] < r[:, 1], 0, np.where(u[:, t] < r[:, 2], 1, 0)))
+            s = ((u[:, t] < r[:, 0]) | (u[:, t] < r[:, 1])).astype(np.int64)
+            flag[:, t], state[:, t] = 1 - lost, s
+        out[name], out[sname] = flag, state
+    return out
+
+
+def burst_channel(loss_rate, mean_burst):
+    """The simple Gilbert channel (e_g = 0, e_b = 1: every packet in B is lost, none in G) with stationary loss rate
+    p_gb / (p_gb + p_bg) = loss_rate and mean burst length 1 / p_bg = mean_burst, as the `channel` dict of the closed loops.
+    mean_burst = 1 / (1 - loss_rate) gives independent losses."""
+    loss_rate, mean_burst = np.broadcast_arrays(np.asarray(loss_rate, dtype=np.float64), np.asarray(mean_burst, dtype=np.float64))
+    if np.any(mean_burst < 1.0) or np.any((loss_rate < 0.0) | (loss_rate >= 1.0)):
+        raise ValueError("burst_channel: need mean_burst >= 1 and 0 <= loss_rate < 1")
+    p_bg = 1.0 / mean_burst
+    p_gb = loss_rate * p_bg / (1.0 - loss_rate)
+    if np.any(p_gb > 1.0):
+        raise ValueError("burst_channel: this loss rate needs longer bursts (p_gb = loss_rate / ((1 - loss_rate) mean_burst) > 1)")
+    return dict(p_gb=p_gb.reshape(-1).copy(), p_bg=p_bg.reshape(-1).copy(), e_g=np.zeros(p_gb.size), e_b=np.ones(p_gb.size))
+
+
+def _loss_flags(channel, p_loss, th_u, ga_u):
+    """Arrival flags (B, T) of the two links as the loops draw them: the channel's, or the Bernoulli model's u >= p_loss; t = 0 arrives."""
+    if channel is not None:
+        arr = channel_arrivals(channel, th_u, ga_u)
+        return arr["theta"].astype(np.int64), arr["gamma"].astype(np.int64)
+    theta = np.where(th_u < p_loss[:, None], 0, 1)                             # :211-226, strict <
+    gamma = np.where(ga_u < p_loss[:, None], 0, 1)
+    theta[:, 0] = gamma[:, 0] = 1
+    return theta, gamma
+
+
+class _LinkStats:
+    """The four link statistics of the closed loops (include/tmpc.h: tmpc_mc_get_link_stats), kept by the host twins."""
+
+    def __init__(self, nb: int, N: int):
+        self.N = int(N)
+        self.lost_up, self.lost_down, self.max_gap, self.overrun = (np.zeros(nb, dtype=np.int32) for _ in range(4))
+
+    def step(self, t: int, alive, theta_drawn, gamma_drawn, s):
+        gap = t - np.asarray(s, dtype=np.int64)
+        self.lost_up += (alive & (theta_drawn == 0)).astype(np.int32)
+        self.lost_down += (alive & (gamma_drawn == 0)).astype(np.int32)
+        self.max_gap = np.where(alive, np.maximum(self.max_gap, gap), self.max_gap).astype(np.int32)
+        self.overrun += (alive & (gap >= self.N)).astype(np.int32)
+
+    def result(self):
+        return dict(lost_up=self.lost_up, lost_down=self.lost_down, max_gap=self.max_gap, overrun=self.overrun)
+
+
 def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, ga_u, w, x0=None, extended: bool = False,
-                        plant=None, capture=None, observer=None):
+                        plant=None, capture=None, observer=None, channel=None):
     """Closed loop of the remote tube-based MPC over a lossy network for a batch of trajectories:
     the body of the reference's Monte-Carlo loop (results_linear_system.py:209-259, 291) with the
     per-trajectory objects replaced by the batched state machines and the QP solves of one time
@@ -158,14 +261,19 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     capture: index of one trajectory whose x_t, nominal state of the tube check and u_t are recorded (the scripts' sample run,
     :298-301) -> 'x_traj' (T, nx), 'x_nom_traj' (T, nx), 'u_traj' (T, nu).
     observer: optional callable (t, {'s', 'Theta', 'u'}) called after the actuator of step t (copies of its s_t, Theta_t and u_t).
-    Returns a dict of per-trajectory statistics."""
+    channel: None = independent losses with probability p_loss; or the Gilbert-Elliott channel (channel_parameters, e.g.
+    burst_channel(..)) driven by the same uniforms -- p_loss is then not read and may be None.
+    Returns a dict of per-trajectory statistics, the link statistics lost_up, lost_down, max_gap, overrun among them."""
     from .Estimator import BatchedEstimator
     from .SmartActuator import BatchedConsistentActuator
     A = np.asarray(A, dtype=np.float64)
     Bm = np.asarray(B, dtype=np.float64)
     nb, T = th_u.shape
     nx = A.shape[0]
-    p_loss = np.asarray(p_loss, dtype=np.float64).reshape(nb)
+    p_loss = None if channel is not None else np.asarray(p_loss, dtype=np.float64).reshape(nb)
+    theta_all, gamma_all = _loss_flags(channel, p_loss, th_u, ga_u)
+    link = _LinkStats(nb, N)
+    every = np.ones(nb, dtype=bool)
     ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, (B, T) per trajectory, or (B, T, nx) full states
     full_ref = ref.ndim == 3                         # the solve gets ref[:, t, :], the error is sum_i (x_i - r_i)^2
 
@@ -183,7 +291,7 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     U_prev = x0_prev = None
     gamma = np.ones(nb, dtype=np.int64)
     for t in range(T):
-        theta = np.where(th_u[:, t] < p_loss, 0, 1) if t > 0 else np.ones(nb, dtype=np.int64)     # :211-226, strict <
+        theta = theta_all[:, t]                                                                    # :211-226, strict <
         if full_ref:
             r_t = np.ascontiguousarray(ref[:, t, :])
         else:
@@ -208,6 +316,7 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
             est.store_x_nom_0(x_nom_0)                                                             # RLX:279
         x_nom_now = act.x_nom.copy()       # the nominal state the scripts test against: column t of x_nom_traj, i.e. BEFORE process_packet
         u, pkt = act.process(U_t, q_t, x, theta, x_nom_0 if extended else None)                    # :244
+        link.step(t, every, theta_all[:, t], gamma_all[:, t], act.s)      # (what the channel dropped: theta before a failed solve's 0)
         if observer is not None:
             observer(t, dict(s=np.array(act.s).copy(), Theta=np.array(act.Theta).copy(), u=np.array(u).copy()))
         if full_ref:
@@ -230,7 +339,7 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
             x = xs[-1] + w[:, t]
         else:
             x = (x @ A.T + u @ Bm.T if plant is None else plant(x, u)) + w[:, t]                  # :248
-        gamma = np.where(ga_u[:, t] < p_loss, 0, 1) if t > 0 else np.ones(nb, dtype=np.int64)     # :218-226
+        gamma = gamma_all[:, t]                                                                    # :218-226
         est.update(pkt, gamma)                                                                     # :254
         # Proposition 1 of the paper: whenever the actuator is consistent and the plant packet arrives,
         # the estimate equals the nominal plant state
@@ -238,7 +347,7 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
         if ok.any():
             consistent_err = max(consistent_err, float(np.max(np.abs(est.x_hat[ok] - act.x_nom[ok]))))
     out = dict(tracking_error=np.sqrt(err2) / T, tube_violations=tube_viol, not_optimal=not_optimal,
-               consistent_estimate_error=consistent_err, x_final=x)
+               consistent_estimate_error=consistent_err, x_final=x, **link.result())
     if n_phys:
         out["tracking_error_physics"] = np.sqrt(err2_phys) / n_phys
     if cap is not None:
@@ -246,18 +355,20 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     return out
 
 
-def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, x0=None):
+def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, x0=None, channel=None):
     """Closed loop of the non-robust comparator (R-MPC) over the lossy network: TrackingMPC + Estimator + plain
     SmartActuator (results_linear_system.py:198-205, 262-287).  A trajectory whose solve is infeasible stops there
-    (track_feasible = False, :268-270) and reports a NaN tracking error (:297).  Same conventions as
-    run_remote_tube_mpc otherwise."""
+    (track_feasible = False, :268-270) and reports a NaN tracking error (:297), and its link statistics stop at that step.  Same
+    conventions as run_remote_tube_mpc otherwise (`channel` included)."""
     from .Estimator import BatchedEstimator
     from .SmartActuator import BatchedConsistentActuator
     A = np.asarray(A, dtype=np.float64)
     Bm = np.asarray(B, dtype=np.float64)
     nb, T = th_u.shape
     nx = A.shape[0]
-    p_loss = np.asarray(p_loss, dtype=np.float64).reshape(nb)
+    p_loss = None if channel is not None else np.asarray(p_loss, dtype=np.float64).reshape(nb)
+    theta_all, gamma_all = _loss_flags(channel, p_loss, th_u, ga_u)
+    link = _LinkStats(nb, N)
     ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, (B, T) per trajectory, or (B, T, nx) full states
     full_ref = ref.ndim == 3                         # the solve gets ref[:, t, :], the error is sum_i (x_i - r_i)^2
 
@@ -271,7 +382,7 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
     not_optimal = np.zeros(nb, dtype=np.int32)
     U_prev = None
     for t in range(T):
-        theta = np.where(th_u[:, t] < p_loss, 0, 1) if t > 0 else np.ones(nb, dtype=np.int64)
+        theta = theta_all[:, t]
         if full_ref:
             r_t = np.ascontiguousarray(ref[:, t, :])
         else:
@@ -288,16 +399,17 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
         act.x_nom = x.copy()
         u, pkt = act.process(U_t, q_t, x, theta)
         pkt = {"x_t": x.copy(), "s_t": pkt["s_t"]}
+        link.step(t, ~dead, theta_all[:, t], gamma_all[:, t], act.s)
         if full_ref:
             err2 += np.where(dead, 0.0, (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1))
         else:
             err2 += np.where(dead, 0.0, (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1))
         x = np.where(dead[:, None], x, x @ A.T + u @ Bm.T + w[:, t])
-        gamma = np.where(ga_u[:, t] < p_loss, 0, 1) if t > 0 else np.ones(nb, dtype=np.int64)
+        gamma = gamma_all[:, t]
         est.update(pkt, gamma)
     te = np.sqrt(err2) / T
     te[dead] = np.nan
-    return dict(tracking_error=te, not_optimal=not_optimal, infeasible=dead, x_final=x)
+    return dict(tracking_error=te, not_optimal=not_optimal, infeasible=dead, x_final=x, **link.result())
 
 
 def plant_callable(plant):
@@ -316,7 +428,8 @@ def plant_callable(plant):
 
 def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240301, rank: int = 0, world: int = 1,
              extended: bool = False, device=None, on_device: bool = False, plant=None, warm_start: bool = False,
-             timing: bool = False, device_rng: bool = False, force_collective: bool = False, ref_id=None):
+             timing: bool = False, device_rng: bool = False, force_collective: bool = False, ref_id=None, mean_burst=None,
+             link_stats: bool = False):
     """The Monte-Carlo sweep of results_linear_system.py:147-301 (BASELINE config 4): len(p_loss) x n_mc
     trajectories of T steps, sharded over `world` ranks (one process per GPU, contiguous p_loss-balanced
     shards), every time step of a shard solved by one kernel launch, statistics all-gathered at the end.
@@ -326,7 +439,9 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     device_rng: Philox streams keyed by (seed, global trajectory index), drawn on the device in the device loop
     (tmpc_mc_set_device_rng) and by draw_realisations_philox, the same numbers, in the host loops.
     ref: a scalar or (T,) position reference; or (T, nx) one full-state schedule for every trajectory; or (K, T, nx) schedules
-    with ref_id (n_total,) naming each trajectory's -- sliced with the shard, so the sweep stays shard-invariant."""
+    with ref_id (n_total,) naming each trajectory's -- sliced with the shard, so the sweep stays shard-invariant.
+    mean_burst: None -- independent losses; else every loss rate p as the stationary rate of burst_channel(p, mean_burst), on the
+    same uniforms (a rate above 1 - 1 / mean_burst keeps independent losses, whose bursts last 1 / (1 - p) on average; every rate must be below 1).  link_stats: four more columns at the end of the table: lost_up, lost_down, max_gap, overrun."""
     import torch
     p_loss = np.asarray(p_loss, dtype=np.float64)
     pi, _ = trajectory_table(p_loss, n_mc)
@@ -348,21 +463,29 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
             ref = ref[ids, :T]                        # the host twins take one schedule per trajectory
     else:
         ref = np.broadcast_to(ref, (T,))
+    channel = None
+    if mean_burst is not None:
+        if np.any(p_loss >= 1.0):
+            raise ValueError("mc_sweep: mean_burst needs every loss rate below 1 (a channel that loses every packet has no bursts)")
+        rate = p_loss[pi[lo:hi]]
+        channel = burst_channel(rate, np.maximum(float(mean_burst), 1.0 / (1.0 - rate)))
     if on_device:        # state machines on the GPU as well (tmpc_mc_run); otherwise the host loop around determine_packets
         out = mpc.run_closed_loop(p_loss[pi[lo:hi]], ref, th, ga, w, extended=extended, plant=plant, warm_start=warm_start,
                                   timing=timing, device_rng=(seed, lo, model["w_bound"]) if device_rng else None, ref_id=ids,
-                                  T=T if ids is not None else None)
+                                  T=T if ids is not None else None, channel=channel)
     elif getattr(mpc, "_smart_actuator", False):       # TrackingMPC: the comparator's loop (results_linear_system.py:262-287)
         out = run_remote_tracking_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(), mpc._N,
-                                      p_loss[pi[lo:hi]], ref, th, ga, w)
+                                      p_loss[pi[lo:hi]], ref, th, ga, w, channel=channel)
         out["tube_violations"] = np.zeros(hi - lo, dtype=np.int32)
     else:
         out = run_remote_tube_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(),
                                   mpc.get_ancillary_controller_gain(), mpc._N, mpc._Z, p_loss[pi[lo:hi]], ref, th, ga, w,
-                                  extended=extended, plant=None if plant is None else plant_callable(plant))
+                                  extended=extended, plant=None if plant is None else plant_callable(plant), channel=channel)
     cols = [out["tracking_error"], out["tube_violations"], out["not_optimal"]]
     if timing and on_device:
         cols += [out["solve_time_mean"], out["solve_time_max"]]
+    if link_stats:
+        cols += [out[k] for k in ("lost_up", "lost_down", "max_gap", "overrun")]
     local = torch.tensor(np.column_stack(cols), dtype=torch.float64)
     if device is not None:
         local = local.to(device)

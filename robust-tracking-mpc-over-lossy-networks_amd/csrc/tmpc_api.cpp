@@ -118,6 +118,8 @@ struct LoopRecords {
     double *err2_phys = nullptr; // physics-rate error (nonlinear plant)
     int64_t phys_B = 0;
     int fused = 0;               // tmpc_mc_last_fused
+    std::vector<int32_t> link;   // link statistics [4][link_B]: lost_up, lost_down, max_gap, overrun -- a HOST copy, fetched with the loop's
+    int64_t link_B = 0;          // other outputs (tmpc_mc_get_link_stats then costs no device call); 0: no loop has finished
 };
 
 // One launch lane of a device handle: a non-blocking stream and everything a solve launch on it mutates, so that launches on
@@ -231,6 +233,9 @@ struct tmpc_handle {
     int64_t mc_ref_B = 0;
     std::vector<double> mc_ref_tab;
     std::vector<int32_t> mc_ref_id;
+    // tmpc_mc_set_channel: the Gilbert-Elliott thresholds [B][2][3] as the device compares them (mc_ch_B = 0: the Bernoulli model)
+    int64_t mc_ch_B = 0;
+    std::vector<double> mc_ch_thr;
     // closed-loop state: one grow-only arena (25 hipMalloc / hipFree per call cost several milliseconds), and what the last run
     // left in it
     Arena arena;
@@ -1245,6 +1250,59 @@ int tmpc_mc_set_reference_table(tmpc_handle *h, int32_t K, int32_t T_tab, const 
     return TMPC_OK;
 }
 
+int tmpc_mc_set_channel(tmpc_handle *h, int64_t B, const double *p_gb, const double *p_bg, const double *e_g, const double *e_b) {
+    if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, "tmpc_mc_set_channel")) return TMPC_E_INVALID;
+    if (h->regulator) { h->err = "tmpc_mc_set_channel: a regulator handle has no network"; return TMPC_E_INVALID; }
+    if (B < 0) { h->err = "tmpc_mc_set_channel: B < 0"; return TMPC_E_INVALID; }
+    if (B == 0) {
+        h->mc_ch_B = 0;
+        h->mc_ch_thr.clear();
+        return TMPC_OK;
+    }
+    if (!p_gb || !p_bg || !e_g || !e_b) { h->err = "tmpc_mc_set_channel: NULL argument"; return TMPC_E_INVALID; }
+    const struct { const char *name; const double *v; } par[4] = {{"p_gb", p_gb}, {"p_bg", p_bg}, {"e_g", e_g}, {"e_b", e_b}};
+    for (const auto &q : par)
+        for (int64_t b = 0; b < B; ++b)
+            if (!(q.v[b] >= 0.0 && q.v[b] <= 1.0)) {      // (NaN fails both)
+                h->err = std::string("tmpc_mc_set_channel: ") + q.name + "[" + std::to_string(b) + "] = " + std::to_string(q.v[b]) + " is no probability";
+                return TMPC_E_INVALID;
+            }
+    std::vector<double> thr(static_cast<size_t>(B) * 6);
+    for (int64_t b = 0; b < B; ++b)
+        for (int prev = 0; prev < 2; ++prev) {
+            // a = P(B | previous state); every product and sum is rounded on its own (volatile: no contraction into a fused
+            // multiply-add, whatever the host compiler's setting -- montecarlo.gilbert_elliott_thresholds is the numpy twin)
+            const double a = prev == 0 ? p_gb[b] : 1.0 - p_bg[b];
+            volatile double lost_b = a * e_b[b];
+            volatile double good = 1.0 - a;
+            volatile double lost_g = good * e_g[b];
+            volatile double top = a + lost_g;
+            double *r = thr.data() + (static_cast<size_t>(b) * 2 + prev) * 3;
+            r[0] = lost_b; r[1] = a; r[2] = top;
+        }
+    h->mc_ch_thr.swap(thr);
+    h->mc_ch_B = B;
+    return TMPC_OK;
+}
+
+int tmpc_mc_get_channel(tmpc_handle *h, int64_t B, double *thr) {
+    if (!h || !thr) return TMPC_E_INVALID;
+    if (h->mc_ch_B == 0 || B != h->mc_ch_B) { h->err = "tmpc_mc_get_channel: no channel of this batch size is set (tmpc_mc_set_channel)"; return TMPC_E_INVALID; }
+    std::memcpy(thr, h->mc_ch_thr.data(), h->mc_ch_thr.size() * sizeof(double));
+    return TMPC_OK;
+}
+
+int tmpc_mc_get_link_stats(tmpc_handle *h, int64_t B, int32_t *lost_up, int32_t *lost_down, int32_t *max_gap, int32_t *overrun) {
+    if (!h) return TMPC_E_INVALID;
+    if (h->rec.link_B == 0 || B != h->rec.link_B) { h->err = "tmpc_mc_get_link_stats: no closed loop of this batch size has run (tmpc_mc_run, tmpc_mc_close)"; return TMPC_E_INVALID; }
+    int32_t *const out[4] = {lost_up, lost_down, max_gap, overrun};
+    const size_t b = static_cast<size_t>(B);
+    for (size_t k = 0; k < 4; ++k)
+        if (out[k]) std::memcpy(out[k], h->rec.link.data() + k * b, b * sizeof(int32_t));
+    return TMPC_OK;
+}
+
 int tmpc_mc_set_warm_start(tmpc_handle *h, int on) {
     if (!h) return TMPC_E_INVALID;
     if (session_bars(h, "tmpc_mc_set_warm_start")) return TMPC_E_INVALID;
@@ -1291,6 +1349,32 @@ void reference_table_pieces(tmpc_handle *h, Arena &a, tmpc::McState &st) {
     st.ref_T = h->mc_ref_T;
 }
 
+// A loop of B trajectories under the handle's loss channel (tmpc_mc_set_channel): does it fit?
+int channel_fits(tmpc_handle *h, const char *who, int64_t B) {
+    if (B == h->mc_ch_B) return TMPC_OK;
+    h->err = std::string(who) + ": B = " + std::to_string(B) + ", but the loss channel was set for B = " + std::to_string(h->mc_ch_B) + " trajectories";
+    return TMPC_E_INVALID;
+}
+// the loss model's and the link statistics' pieces of a loop's arena: the channel's thresholds and link states (both links start
+// in G) or p_loss, and the four counters -- one block [4][B], so that one copy brings them back (link_block_carved, fetch_link_stats)
+void link_pieces(tmpc_handle *h, Arena &a, tmpc::McState &st, bool channel, size_t b, const double *p_loss) {
+    if (channel) {
+        a.piece(&st.ch_thr, h->mc_ch_thr.size() * 8, h->mc_ch_thr.data());
+        a.piece(&st.ch_state, b * 2, nullptr, 0);
+    } else {
+        a.piece(&st.p_loss, b * 8, p_loss);
+    }
+    a.piece(&st.lost_up, b * 4 * 4, nullptr, 0);
+}
+void link_block_carved(tmpc::McState &st, size_t b) {
+    st.lost_down = st.lost_up + b; st.max_gap = st.lost_up + 2 * b; st.overrun = st.lost_up + 3 * b;
+}
+// enqueues the copy of the counters into the handle's record; the caller synchronises and then sets rec.link_B
+hipError_t fetch_link_stats(tmpc_handle *h, const tmpc::McState &st, size_t b) {
+    h->rec.link.resize(4 * b);
+    return hipMemcpyAsync(h->rec.link.data(), st.lost_up, b * 4 * 4, hipMemcpyDeviceToHost, h->stream);
+}
+
 int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double *p_loss, const double *ref,
                 const double *th_u, const double *ga_u, const double *w, const double *x0, const double *HZ, const double *hZ,
                 int32_t rZ, double *err2, int32_t *tube_viol, int32_t *not_optimal, double *x_final, double *consistent,
@@ -1299,8 +1383,11 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
     if (h->ses.open) { h->err = "tmpc_mc_run: a stepped closed loop is open on this handle (tmpc_mc_close first)"; return TMPC_E_INVALID; }
     const bool host_draws = rp != nullptr || !h->mc_rng_on;
     const bool full_ref = !rp && h->mc_ref_K > 0;      // (tmpc_mc_replay solves nothing: it ignores the reference table)
-    if (B < 0 || T < 0 || !p_loss || (!ref && !full_ref) || (host_draws && (!th_u || !ga_u || !w)) || (rZ > 0 && (!HZ || !hZ))) { h->err = "tmpc_mc_run: NULL argument"; return TMPC_E_INVALID; }
+    const bool channel = !rp && h->mc_ch_B > 0;        // (tmpc_mc_replay is given its arrival flags: it ignores the channel)
+    if (B < 0 || T < 0 || (!p_loss && !channel) || (!ref && !full_ref) || (host_draws && (!th_u || !ga_u || !w)) || (rZ > 0 && (!HZ || !hZ))) { h->err = "tmpc_mc_run: NULL argument"; return TMPC_E_INVALID; }
     if (h->regulator) { h->err = "tmpc_mc_run: a regulator handle runs its loop with tmpc_reg_run"; return TMPC_E_INVALID; }
+    if (channel)         // (an argument error: reported on a host-only handle too)
+        if (const int r2 = channel_fits(h, "tmpc_mc_run", B)) return r2;
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
     if (extended && h->nvariants < 2) { h->err = "tmpc_mc_run: extended loop needs a problem created with extended = 1"; return TMPC_E_INVALID; }
     if (h->hK.empty() || h->hKanc.empty()) { h->err = "tmpc_mc_run: the problem description carries no gains K / K_anc"; return TMPC_E_INVALID; }
@@ -1346,7 +1433,7 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
         a.piece(&m.K_anc, nu * nx * 8, h->hKanc.data());
         a.piece(&m.HZ, static_cast<size_t>(rZ) * nx * 8, HZ);
         a.piece(&m.hZ, static_cast<size_t>(rZ) * 8, hZ);
-        a.piece(&st.p_loss, b * 8, p_loss);
+        link_pieces(h, a, st, channel, b, p_loss);
         if (host_draws) {
             a.piece(&st.th_u, b * t_ * 8, th_u);
             a.piece(&st.ga_u, b * t_ * 8, ga_u);
@@ -1398,6 +1485,7 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
             a.piece(&d_mf, sizeof(mf));
         }
         HIP_TRY(h, a.carve(h->stream));
+        link_block_carved(st, b);
         gam[0] = st.gamma;
         if (st.cap) { h->rec.cap = st.cap; h->rec.cap_T = T; }
         if (st.err2_phys) { h->rec.err2_phys = st.err2_phys; h->rec.phys_B = B; }
@@ -1452,7 +1540,9 @@ int mc_run_impl(tmpc_handle *h, int64_t B, int32_t T, int extended, const double
         if (x_final) HIP_TRY(h, hipMemcpyAsync(x_final, st.x, b * nx * 8, hipMemcpyDeviceToHost, h->stream));
         if (consistent) HIP_TRY(h, hipMemcpyAsync(consistent, st.consistent, b * 8, hipMemcpyDeviceToHost, h->stream));
         if (iters_sum) HIP_TRY(h, hipMemcpyAsync(iters_sum, st.iters_sum, b * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, fetch_link_stats(h, st, b));
         HIP_TRY(h, sync_lanes(h));
+        h->rec.link_B = B;
         return TMPC_OK;
     };
     rc = run();
@@ -1575,10 +1665,13 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
     const bool host_draws = !h->mc_rng_on;
     if (B <= 0 || T <= 0 || rZ < 0 || rX < 0 || rU < 0) { h->err = "tmpc_mc_open: need B > 0, T > 0 and row counts >= 0"; return TMPC_E_INVALID; }
     const bool full_ref = h->mc_ref_K > 0;
-    if (!p_loss || (!ref && !full_ref) || (host_draws && (!th_u || !ga_u)) || (rZ > 0 && (!HZ || !hZ)) || (rX > 0 && (!HX || !hX)) || (rU > 0 && (!HU || !hU))) {
+    const bool channel = h->mc_ch_B > 0;
+    if ((!p_loss && !channel) || (!ref && !full_ref) || (host_draws && (!th_u || !ga_u)) || (rZ > 0 && (!HZ || !hZ)) || (rX > 0 && (!HX || !hX)) || (rU > 0 && (!HU || !hU))) {
         h->err = "tmpc_mc_open: NULL argument";
         return TMPC_E_INVALID;
     }
+    if (channel)
+        if (const int r2 = channel_fits(h, "tmpc_mc_open", B)) return r2;
     if (extended && h->nvariants < 2) { h->err = "tmpc_mc_open: extended loop needs a problem created with extended = 1"; return TMPC_E_INVALID; }
     if (h->hK.empty() || h->hKanc.empty()) { h->err = "tmpc_mc_open: the problem description carries no gains K / K_anc"; return TMPC_E_INVALID; }
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
@@ -1608,7 +1701,7 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
         a.piece(&ext.hX, static_cast<size_t>(rX) * 8, hX);
         a.piece(&ext.HU, static_cast<size_t>(rU) * nu * 8, HU);
         a.piece(&ext.hU, static_cast<size_t>(rU) * 8, hU);
-        a.piece(&st.p_loss, b * 8, p_loss);
+        link_pieces(h, a, st, channel, b, p_loss);
         if (host_draws) {
             a.piece(&st.th_u, b * t_ * 8, th_u);
             a.piece(&st.ga_u, b * t_ * 8, ga_u);
@@ -1647,6 +1740,7 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
             a.piece(&s.ref_stage, b * nx * 8, nullptr, 0);
         }
         HIP_TRY(h, a.carve(h->stream));
+        link_block_carved(st, b);
         ext.x_t = x_stage;
         ext.u_t = u_stage;
         HIP_TRY(h, tmpc::launch_mc_pre(m, st, B, full_ref ? 0.0 : ref[0], h->stream));
@@ -1794,6 +1888,7 @@ int tmpc_mc_close(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_v
             {tube_viol, st.tube_viol}, {x_viol, s.ext.x_viol}, {u_viol, s.ext.u_viol}, {not_optimal, st.not_optimal}, {iters_sum, st.iters_sum}};
         for (const auto &c : counters)
             if (c.host) HIP_TRY(h, hipMemcpyAsync(c.host, c.dev, b * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, fetch_link_stats(h, st, b));
         HIP_TRY(h, sync_lanes(h));
         return TMPC_OK;
     };
@@ -1803,6 +1898,7 @@ int tmpc_mc_close(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_v
     // what the getters read, as after a run (the arena stays as it is until the next loop)
     if (rc == TMPC_OK && s.st.cap) { h->rec.cap = s.st.cap; h->rec.cap_T = s.T; }
     if (rc == TMPC_OK && s.st.tick_sum) { h->rec.tick_sum = s.st.tick_sum; h->rec.tick_max = s.st.tick_max; h->rec.tick_B = s.B; }
+    if (rc == TMPC_OK) h->rec.link_B = s.B;
     release_session(h);
     return rc;
 }

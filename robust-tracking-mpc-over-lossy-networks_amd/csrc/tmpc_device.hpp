@@ -180,6 +180,13 @@ struct McState {                         // all [trajectory]-major device arrays
     const double *ref_tab;                    // [K][ref_T][nx] schedules
     const int32_t *ref_id;                    // [B] schedule of every trajectory
     int ref_T;                                // rows of a schedule (>= T)
+    // Gilbert-Elliott loss channel (tmpc_mc_set_channel), or nullptr: the Bernoulli model on p_loss (which is then the one not read)
+    const double *ch_thr;                     // [B][2][3] thresholds by the link's previous state (G, B): (B, lost) | (B, arrives) | (G, lost)
+    uint8_t *ch_state;                        // [B][2] state of the controller->plant / plant->controller link (0: G, 1: B)
+    // link statistics (tmpc_mc_get_link_stats), all four or none (lost_up == nullptr: not recorded); the host carves them as one
+    // block [4][B] in this order and fetches it with the loop's other outputs                                           [B]
+    int32_t *lost_up, *lost_down;             // steps t > 0 whose controller->plant / plant->controller packet the channel dropped
+    int32_t *max_gap, *overrun;               // max_t (t - s_t); steps with t - s_t >= N (the buffer exhausted: the terminal law)
 };
 // The caller's side of the stepped closed loop (tmpc_mc_open / tmpc_mc_step_device, m.plant = TMPC_PLANT_EXTERNAL): the plant
 // state of this step comes from the caller and the applied input goes back; X and U are the caller's check sets for the two.

@@ -77,6 +77,17 @@ __device__ __forceinline__ void mc_draws(const StateRec &st, int64_t b, int t, i
     w = comp < nx ? st.w_bound[comp] * (2.0 * u01(rc) - 1.0) : 0.0;
 }
 
+// One link of the Gilbert-Elliott loss channel (include/tmpc.h: tmpc_mc_set_channel) at a step t > 0: the step's uniform against the three
+// thresholds of the link's previous state, computed on the host -- u < thr[0]: (B, lost); else u < thr[1]: (B, arrives); else u < thr[2]:
+// (G, lost); else (G, arrives).  Strict comparisons, like the Bernoulli model's <.  `state` (0: G, 1: B; wave-uniform) is replaced by the
+// new one; returns 1 if the packet is lost.
+__device__ __forceinline__ int channel_link(const double *thr, const int64_t b, const double u, int &state) {
+    const double *r = thr + b * 6 + state * 3;
+    const double t0 = r[0], t1 = r[1], t2 = r[2];
+    state = (u < t0 || u < t1) ? 1 : 0;
+    return u < t0 ? 1 : (u < t1 ? 0 : (u < t2 ? 1 : 0));
+}
+
 // Orders one wave's LDS traffic for the compiler (the hardware runs the DS instructions of a wave in issue order).
 #ifdef TMPC_HOST_SIM
 __device__ __forceinline__ void mc_fence() { sim::wave_fence(); }      // (tests/wavesim: an LDS hand-over between lanes is a rendezvous)
@@ -104,6 +115,10 @@ enum { V_X = 0, V_XN, V_E, V_ET, V_U, V_UN, V_BASE, V_TMP, V_COUNT };
 // st.ref_tab != nullptr (tmpc_mc_set_reference_table, "full-reference mode"): the reference of a solve is a full state, row t of the
 // trajectory's schedule st.ref_tab[st.ref_id[b]] (or, EXT, the caller's ext.ref_next), and the tracking error is |x_t - r_t|^2 over all
 // nx components against the reference the solve of step t used; ref_t / ref_next are then not read.  One wave-uniform branch.
+//
+// st.ch_thr != nullptr (tmpc_mc_set_channel): the two loss tests are those of the Gilbert-Elliott channel, whose link states live in
+// st.ch_state; p_loss is then not read.  One wave-uniform branch per link.  A failed solve forces theta = 0 as ever and leaves the
+// channel's state to the draw.  st.lost_up != nullptr: lane 0 keeps the link statistics, with either loss model.
 template <bool EXT, class ModelRec, class StateRec>
 __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &st, const int t, const int T, const int64_t b,
                                              const double ref_t, const double ref_next,
@@ -121,10 +136,20 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
     // the record is read through the constant address space (the fused kernels) the scalar load goes out with theirs
     const bool full_ref = st.ref_tab != nullptr;
     const bool lx = lane < nx, lu = lane < nu;
-    const double p = st.p_loss[b];
+    // the loss channel (tmpc_mc_set_channel), wave-uniform; the field is read again at the plant's packet, not carried there
+    const bool chan_u = st.ch_thr != nullptr;
+    const double p = chan_u ? 0.0 : st.p_loss[b];
     double th_draw, ga_draw, w_l;
     mc_draws<!EXT>(st, b, t, T, nx, lane, th_draw, ga_draw, w_l);
-    int theta = (t > 0 && th_draw < p) ? 0 : 1;                                          // strict <, first packet always arrives
+    int lost_u, ch_u = 0;                                                                // the channel dropped the controller's packet; its link's state
+    if (chan_u) {
+        lost_u = 0;                                                                      // t = 0: the packet arrives, the state stays
+        if (t > 0) {
+            ch_u = __builtin_amdgcn_readfirstlane(static_cast<int>(st.ch_state[b * 2]));
+            lost_u = channel_link(st.ch_thr, b, th_draw, ch_u);
+        }
+    } else lost_u = (t > 0 && th_draw < p) ? 1 : 0;                                      // strict <, first packet always arrives
+    int theta = lost_u ? 0 : 1;
     const int stat = replay ? 0 : status[b];
     const bool bad = stat >= 2;
     if (lane == 0) {
@@ -170,11 +195,26 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
     // ---- consistent actuator (SmartActuator.py:57-107, 174-231)
     const int q_before = st.q_est[b];
     int last_lost = st.last_lost[b], q_act = st.q_act[b], s_t = st.s[b];
+    // the link statistics' counters, read here so that their latency passes with that of the loads above; written back by lane 0
+    // below (read where they are updated, each update waited for a load of its own: 2.4 - 2.8 us per step in the latency-bound
+    // loops, against 0.8 us this way -- DESIGN.md 7g)
+    const bool links = st.lost_up != nullptr;
+    int n_up = 0, n_down = 0, n_gap = 0, n_over = 0;
+    if (links) { n_up = st.lost_up[b]; n_down = st.lost_down[b]; n_gap = st.max_gap[b]; n_over = st.overrun[b]; }
     if (theta == 0) last_lost = t;
     if (theta == 1) q_act = q_before;
     const int Theta = (theta == 1 && last_lost <= q_act) ? 1 : 0;
     if (Theta) s_t = t;
-    if (lane == 0) { st.last_lost[b] = last_lost; st.q_act[b] = q_act; st.Theta[b] = Theta; st.s[b] = s_t; }
+    if (lane == 0) {
+        st.last_lost[b] = last_lost; st.q_act[b] = q_act; st.Theta[b] = Theta; st.s[b] = s_t;
+        if (chan_u && t > 0) st.ch_state[b * 2] = static_cast<uint8_t>(ch_u);
+        if (links) {                                           // link statistics: what the channel dropped, the age of the sequence played
+            const int gap = t - s_t;
+            st.lost_up[b] = n_up + lost_u;
+            if (gap > n_gap) st.max_gap[b] = gap;
+            if (gap >= N) st.overrun[b] = n_over + 1;          // the buffer is exhausted: the terminal law below (!inside)
+        }
+    }
     double *Ub = st.Ubuf + b * (N + 1) * nu;                  // [i][j], i = 0..N
     if (Theta) {
         for (int i = lane; i < N * nu; i += WAVE_MC) Ub[i] = pk_u[i];
@@ -327,7 +367,17 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
         st.x_nom[b * nx + lane] = xnp_l;
     }
     // ---- estimator (Estimator.py:43-98; robust: :113-156)
-    const int gamma = (t > 0 && ga_draw < p) ? 0 : 1;
+    int lost_d;
+    if (st.ch_thr != nullptr) {
+        lost_d = 0;
+        if (t > 0) {
+            int ch_d = __builtin_amdgcn_readfirstlane(static_cast<int>(st.ch_state[b * 2 + 1]));
+            lost_d = channel_link(st.ch_thr, b, ga_draw, ch_d);
+            if (lane == 0) st.ch_state[b * 2 + 1] = static_cast<uint8_t>(ch_d);
+        }
+    } else lost_d = (t > 0 && ga_draw < p) ? 1 : 0;
+    const int gamma = lost_d ? 0 : 1;
+    if (lane == 0 && links) st.lost_down[b] = n_down + lost_d;
     double xh_l = 0.0;
     if (gamma) {
         // packet {'x_t', 's_t'[, 'x_nom_t']}: x_t = nominal state (consistent actuator) or plant state (extended);

@@ -30,6 +30,10 @@ def main():
                                                           "results_linear_system.py:305-315 prints")
     ap.add_argument("--device-rng", action="store_true", help="draw the realisations on the device (tmpc_mc_set_device_rng, Philox keyed "
                                                               "by the global trajectory index) instead of uploading them")
+    ap.add_argument("--mean-burst", type=float, default=None, metavar="L",
+                    help="losses in bursts of L steps on average at the same stationary loss rates (tmpc_mc_set_channel: the Gilbert "
+                         "channel of montecarlo.burst_channel; a rate above 1 - 1 / L keeps independent losses); adds the "
+                         "link statistics to the table")
     ap.add_argument("--host-loop", action="store_true", help="state machines in numpy on the host instead of on the device")
     ap.add_argument("--all-controllers", action="store_true",
                     help="tube MPC, extended tube MPC and the tracking MPC one after the other on the SAME realisations "
@@ -61,6 +65,8 @@ def main():
         mpc, model = workloads.make_controller("cartpole", args.N, True, extended=extended, device=local, tracking=rmpc)
         t0 = time.time()
         if args.reference_streams:
+            if args.mean_burst is not None:
+                raise SystemExit("--mean-burst goes with the per-trajectory streams, not with --reference-streams")
             if world != 1:
                 raise SystemExit("--reference-streams keeps the reference's draw order and cannot be sharded")
             pl, th, ga, wd = montecarlo.draw_realisations_reference_order(p_loss, args.n_mc, args.T, model["w_bound"])
@@ -73,7 +79,8 @@ def main():
             # one seed for every controller: the same loss patterns and disturbances (per-trajectory streams)
             table, pi = montecarlo.mc_sweep(mpc, model, p_loss, args.n_mc, args.T, args.ref, rank=rank, world=world,
                                             extended=extended, device=device, on_device=not args.host_loop, warm_start=args.warm_start,
-                                            timing=args.timing and not args.host_loop, device_rng=args.device_rng, force_collective=use_pg)
+                                            timing=args.timing and not args.host_loop, device_rng=args.device_rng, force_collective=use_pg,
+                                            mean_burst=args.mean_burst, link_stats=args.mean_burst is not None)
         dt = time.time() - t0
         if rank == 0:
             report(label, table, pi, p_loss, dt, world, args)
@@ -93,6 +100,11 @@ def report(label, table, pi, p_loss, dt, world, args):
         dead = int(np.isnan(te).sum())                       # R-MPC: a run whose QP became infeasible stops (NaN tracking error, :297)
         mean_te = float(np.nanmean(te)) if dead < m.sum() else float("nan")
         print(f"{p:5.1f}   {mean_te:.6f}            {int(table[m, 1].sum()):6d}            {int(table[m, 2].sum()):6d}            {dead:6d}")
+    if args.mean_burst is not None:                              # the last four columns: lost_up, lost_down, max_gap, overrun
+        print(f"mean burst {args.mean_burst:g}:  packets lost   largest max_gap   steps past the buffer's end (overrun)")
+        for i, p in enumerate(p_loss):
+            lk = table[pi == i, -4:]
+            print(f"{p:5.1f}              {lk[:, :2].sum() / (2.0 * len(lk) * max(args.T - 1, 1)):.4f}         {int(lk[:, 2].max()):6d}            {int(lk[:, 3].sum()):6d}")
     if args.timing and table.shape[1] >= 5:                      # results_linear_system.py:305-315, in milliseconds
         mean_ms, max_ms = 1e3 * table[:, 3], 1e3 * table[:, 4]
         print(f"device time per MPC solve (one instance of a batched launch), {n} trajectory means: max of all solves {max_ms.max():.3f} ms, "
