@@ -428,6 +428,18 @@ int tmpc_mc_set_device_rng(tmpc_handle *h, int on, uint64_t seed, int64_t first_
 #define TMPC_PLANT_CARTPOLE 1
 #define TMPC_PLANT_EXTERNAL 2   /* the caller's plant: set by a stepped session (tmpc_mc_open) only, refused by tmpc_mc_set_plant */
 int tmpc_mc_set_plant(tmpc_handle *h, int kind, const double *par7, int substeps);
+/*
+ * A plant model per trajectory for the regulator loop (tmpc_reg_run): the plant of trajectory b differs from the controller's model,
+ * which is the point -- the gain and the QP stay the handle's (A, B).
+ *   kind    TMPC_PLANT_LINEAR.  models is B x nx x (nx + nu), row-major: row i of trajectory b is [A_b[i, :] | B_b[i, :]], its plant
+ *           x+ = A_b x + B_b u + w.  substeps is ignored.
+ * B == 0 clears the models.  models is HOST memory, copied; the copy lives on the host (the setter works on a host-only handle) and
+ * is uploaded with each loop.  While models are set, tmpc_reg_run needs its B equal to the models' B (TMPC_E_INVALID otherwise, before
+ * anything is launched).  TMPC_E_INVALID, the message naming trajectory and entry: B < 0, models == NULL with B > 0, another kind, a
+ * non-finite entry.  A refused call changes nothing.  Tracking handles: TMPC_E_UNSUPPORTED -- tmpc_mc_run, tmpc_mc_replay and the
+ * stepped sessions simulate the handle's one plant (tmpc_mc_set_plant).  Added without an ABI bump: a new export.
+ */
+int tmpc_mc_set_plant_models(tmpc_handle *h, int kind, int64_t B, const double *models, int substeps);
 
 /*
  * Stepped closed loop around a plant the CALLER owns: the per-trajectory state machines and the solve kernels of tmpc_mc_run,
@@ -714,6 +726,19 @@ int tmpc_estimate_w(int device, int32_t nx, int32_t nu, const double *A, const d
                     int32_t n_rank, const int64_t *ranks, double settle_tol,
                     double *order_stats, double *w_min, double *w_max, int64_t *n_samples, int64_t *n_nonfinite,
                     int64_t *not_settled, double *x_final_norm_max, double *x0_used, double *samples, float *kernel_ms);
+
+/*
+ * tmpc_estimate_w with a plant per trajectory: par_traj is n_traj x 7 (HOST memory), row b the cart-pole of trajectory b; NULL: par7 for
+ * every trajectory (tmpc_estimate_w is this call with NULL; par7 may be NULL when par_traj is given).  A, B and K stay nominal, so
+ * w_k = x_k - (A - B K) x_{k-1} contains the parametric mismatch of the family: a box estimated this way covers it.  The rows are
+ * validated (TMPC_E_INVALID naming trajectory and field: a non-finite entry, M, m, l or Th <= 0, I or b < 0).  Added without an ABI bump: a new export.
+ */
+int tmpc_estimate_w_models(int device, int32_t nx, int32_t nu, const double *A, const double *B, const double *K,
+                           int plant, const double *par7, const double *par_traj, int32_t substeps, int64_t n_traj, int32_t T,
+                           const double *x0, const double *x0_lo, const double *x0_hi, uint64_t seed, int64_t first_trajectory,
+                           int32_t n_rank, const int64_t *ranks, double settle_tol,
+                           double *order_stats, double *w_min, double *w_max, int64_t *n_samples, int64_t *n_nonfinite,
+                           int64_t *not_settled, double *x_final_norm_max, double *x0_used, double *samples, float *kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -117,7 +117,7 @@ class RegulatorMPC:
         return None
 
     def run_closed_loop(self, x0, T: int, w=None, seed=None, first_trajectory: int = 0, w_bound=None, check_sets=None,
-                        capture=None) -> dict:
+                        capture=None, plant=None) -> dict:
         """The loop of the reference's example scripts for a batch of trajectories, resident on the device
         (include/tmpc.h: tmpc_reg_run): per step one solve launch over all trajectories and one step-kernel launch that applies
         u_t = u_nom_0 - K (x_t - x_nom_0) (plain regulator: u_t = u_nom_0), updates x_{t+1} = A x_t + B u_t + w_t and sums the
@@ -126,7 +126,8 @@ class RegulatorMPC:
         regulator) -- the stream of montecarlo.draw_realisations_philox(B, T, w_bound, seed, first_trajectory); neither: no
         disturbance.  check_sets: {"X": polytope, "U": ..., "Z": ...} (None entries: not checked; default: the
         un-tightened X and U, and Z for the tube regulator).  capture: index of one trajectory whose x_traj (T+1, nx),
-        x_nom_traj (T, nx) and u_traj (T, nu) are returned.
+        x_nom_traj (T, nx) and u_traj (T, nu) are returned.  plant: None, or a linear montecarlo.plant_family -- trajectory b then
+        runs on x+ = A_b x + B_b u + w while the controller keeps its (A, B) (tmpc_mc_set_plant_models).
         Returns per trajectory cost (sum of x'Qx + u'Ru), x_viol, u_viol, tube_viol (steps outside the check sets),
         not_optimal, fail_step (first step with an infeasible solve, -1: none; the trajectory is frozen from there), x_final,
         iters_sum."""
@@ -143,7 +144,7 @@ class RegulatorMPC:
                 raise ValueError("run_closed_loop: device-drawn disturbances need w_bound")
             device_rng = (int(seed), int(first_trajectory), np.asarray(w_bound, dtype=np.float64).reshape(self._nx))
         return _native.reg_run(self._handle, x0, T, w=w, device_rng=device_rng, X=sets.get("X"), U=sets.get("U"),
-                               Z=sets.get("Z"), capture=capture)
+                               Z=sets.get("Z"), capture=capture, plant=plant)
 
     # ------------------------------------------------------------------ device and handle
     def set_device(self, device: int):

@@ -147,6 +147,8 @@ def lib():
         L.tmpc_mc_set_actuator.restype = C.c_int
         L.tmpc_mc_set_plant.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int]
         L.tmpc_mc_set_plant.restype = C.c_int
+        L.tmpc_mc_set_plant_models.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int]
+        L.tmpc_mc_set_plant_models.restype = C.c_int
         L.tmpc_lp_batch.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmpc_lp_batch.restype = C.c_int
@@ -155,6 +157,9 @@ def lib():
         L.tmpc_estimate_w.argtypes = ([C.c_int, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_int32]
                                       + [C.c_void_p] * 3 + [C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_double] + [C.c_void_p] * 10)
         L.tmpc_estimate_w.restype = C.c_int
+        L.tmpc_estimate_w_models.argtypes = ([C.c_int, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32]
+                                             + [C.c_void_p] * 3 + [C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_double] + [C.c_void_p] * 10)
+        L.tmpc_estimate_w_models.restype = C.c_int
         L.tmpc_synchronize.argtypes = [C.c_void_p]
         L.tmpc_synchronize.restype = C.c_int
         L.tmpc_set_call_overlap.argtypes = [C.c_void_p, C.c_int]
@@ -471,6 +476,26 @@ def mc_set_plant(h: Handle, plant=None, Th: float = 0.02, substeps: int = 10):
         raise ValueError(f"unknown plant {plant!r}")
     if rc != 0:
         raise RuntimeError(h.error())
+
+
+def mc_set_plant_models(h: Handle, kind, models=None, substeps: int = 10):
+    """include/tmpc.h: tmpc_mc_set_plant_models -- a plant per trajectory of the next tmpc_reg_run of a regulator handle.  kind
+    'linear': models (B, nx, nx + nu), rows [A_b[i, :] | B_b[i, :]].  models None clears them.  Returns the models' batch size (None
+    when cleared)."""
+    if models is None:
+        if lib().tmpc_mc_set_plant_models(h.ptr, 0, 0, None, 0) != 0:
+            raise RuntimeError(h.error())
+        return None
+    if kind not in ("linear", "cartpole"):
+        raise ValueError(f"unknown plant {kind!r}")
+    m = np.ascontiguousarray(np.asarray(models, dtype=np.float64))
+    want = (7,) if kind == "cartpole" else (h.nx, h.nx + h.nu)
+    if m.ndim != len(want) + 1 or m.shape[1:] != want:
+        raise ValueError(f"mc_set_plant_models: {kind} models are (B,) + {want}, got {m.shape}")
+    rc = lib().tmpc_mc_set_plant_models(h.ptr, PLANT_KIND[kind], m.shape[0], m.ctypes.data, int(substeps))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_mc_set_plant_models failed ({rc}): {h.error()}")
+    return m.shape[0]
 
 
 def mc_set_reference(h: Handle, table=None, ref_id=None, B=None):
@@ -819,12 +844,16 @@ def mc_close(h: Handle, info: dict) -> dict:
     return out
 
 
-def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=None, capture=None) -> dict:
+def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=None, capture=None, plant=None) -> dict:
     """include/tmpc.h: tmpc_reg_run -- the closed loop of a regulator handle on the device.  x0 (B, nx); w (B, T, nx) or None;
     device_rng = (seed, first_trajectory, w_bound): w drawn on the device (tmpc_mc_set_device_rng; the w of
     montecarlo.draw_realisations_philox); neither: no disturbance.  X, U, Z: check sets (polytopes) or None.  capture: index of
-    a trajectory whose x_traj (T+1, nx), x_nom_traj (T, nx), u_traj (T, nu) are returned."""
+    a trajectory whose x_traj (T+1, nx), x_nom_traj (T, nx), u_traj (T, nu) are returned.  plant: None -- the model's (A, B); or a
+    linear montecarlo.PlantFamily, a plant per trajectory (tmpc_mc_set_plant_models)."""
     c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))      # noqa: E731
+    if plant is not None and getattr(plant, "kind", None) != "linear":
+        raise ValueError("reg_run: plant is None or a linear plant family")
+    mc_set_plant_models(h, "linear", None if plant is None else plant.models)      # (None clears what an earlier call left)
     x0 = c(x0).reshape(-1, h.nx)
     B, T = x0.shape[0], int(T)
     if w is not None:
@@ -947,10 +976,11 @@ PLANT_KIND = {None: 0, "linear": 0, "cartpole": 1}         # include/tmpc.h: TMP
 
 
 def estimate_w(A, B, K, T: int, x0=None, x0_box=None, n_traj=None, seed: int = 0, first: int = 0, ranks=(), settle_tol: float = 1e-3,
-               plant="cartpole", Th: float = 0.02, substeps: int = 10, device: int = 0, want_samples: bool = False) -> dict:
+               plant="cartpole", Th: float = 0.02, substeps: int = 10, device: int = 0, want_samples: bool = False, par=None) -> dict:
     """Closed loops u = -K x on the nonlinear plant, the samples w_k = x_k - (A - B K) x_{k-1} and their order statistics, all on the
     device (include/tmpc.h: tmpc_estimate_w).  Initial states: the array x0 (n_traj x nx), or drawn on the device from
-    x0_box = (lo, hi) for trajectories first .. first + n_traj - 1 of the stream `seed`."""
+    x0_box = (lo, hi) for trajectories first .. first + n_traj - 1 of the stream `seed`.  par: (n_traj, 7) rows {M, m, b, I, g, l, Th},
+    a cart-pole per trajectory (tmpc_estimate_w_models), or None: workloads.CARTPOLE_PARAMS and Th for everybody."""
     from .workloads import CARTPOLE_PARAMS as P
     L = lib()
     A = np.ascontiguousarray(A, dtype=np.float64)
@@ -971,6 +1001,11 @@ def estimate_w(A, B, K, T: int, x0=None, x0_box=None, n_traj=None, seed: int = 0
     n_traj, T = int(n_traj), int(T)
     if plant not in PLANT_KIND:
         raise ValueError(f"unknown plant {plant!r}")
+    par_traj = None
+    if par is not None:
+        par_traj = np.ascontiguousarray(par, dtype=np.float64)
+        if par_traj.shape != (n_traj, 7):
+            raise ValueError(f"estimate_w: par is (n_traj, 7) = {(n_traj, 7)}, got {par_traj.shape}")
     par = np.array([P["M"], P["m"], P["b"], P["I"], P["g"], P["l"], float(Th)])
     rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
     nper = max(T - 1, 0)
@@ -983,10 +1018,14 @@ def estimate_w(A, B, K, T: int, x0=None, x0_box=None, n_traj=None, seed: int = 0
     smp = np.empty((nx, nper, max(n_traj, 0))) if want_samples else None
     ms = (C.c_float * 2)()
     ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    rc = L.tmpc_estimate_w(int(device), nx, nu, ptr(A), ptr(B), ptr(K), PLANT_KIND[plant], ptr(par), int(substeps), n_traj, T,
-                           ptr(x0), ptr(lo), ptr(hi), int(seed), int(first), rk.size, ptr(rk), float(settle_tol),
-                           ptr(stats), ptr(wmin), ptr(wmax), C.cast(C.byref(ns), C.c_void_p), ptr(nf), C.cast(C.byref(bad), C.c_void_p),
-                           C.cast(C.byref(worst), C.c_void_p), ptr(x0u), ptr(smp), C.cast(ms, C.c_void_p))
+    tail = (ptr(x0), ptr(lo), ptr(hi), int(seed), int(first), rk.size, ptr(rk), float(settle_tol),
+            ptr(stats), ptr(wmin), ptr(wmax), C.cast(C.byref(ns), C.c_void_p), ptr(nf), C.cast(C.byref(bad), C.c_void_p),
+            C.cast(C.byref(worst), C.c_void_p), ptr(x0u), ptr(smp), C.cast(ms, C.c_void_p))
+    if par_traj is None:
+        rc = L.tmpc_estimate_w(int(device), nx, nu, ptr(A), ptr(B), ptr(K), PLANT_KIND[plant], ptr(par), int(substeps), n_traj, T, *tail)
+    else:
+        rc = L.tmpc_estimate_w_models(int(device), nx, nu, ptr(A), ptr(B), ptr(K), PLANT_KIND[plant], ptr(par), ptr(par_traj), int(substeps),
+                                      n_traj, T, *tail)
     if rc != 0:
         raise RuntimeError(f"tmpc_estimate_w failed ({rc}): {L.tmpc_last_error(None).decode()}")
     out = {"order_stats": stats, "w_min": wmin, "w_max": wmax, "n_samples": ns.value, "n_nonfinite": nf, "not_settled": bad.value,

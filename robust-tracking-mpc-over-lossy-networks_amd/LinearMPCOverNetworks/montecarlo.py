@@ -412,8 +412,109 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
     return dict(tracking_error=te, not_optimal=not_optimal, infeasible=dead, x_final=x, **link.result())
 
 
+CARTPOLE_KEYS = ("M", "m", "b", "I", "g", "l")      # the order of a cart-pole row {M, m, b, I, g, l, Th} (include/tmpc.h)
+PLANT_STREAM = 0x706c616e74                          # second counter word of the Philox block sample_cartpole draws from
+
+
+class PlantFamily:
+    """A plant per trajectory for the host loops, the regulators' device loop (include/tmpc.h: tmpc_mc_set_plant_models) and the W
+    estimate (tmpc_estimate_w_models) -- what plant_family returns.
+    kind "linear": A (B, nx, nx), B (B, nx, nu), the plant of trajectory b is x+ = A_b x + B_b u; kind "cartpole": par (B, 7) rows
+    {M, m, b, I, g, l, Th}, the RK4 cart-pole of workloads.cartpole_trace with `substeps` steps per period.  The controller's model
+    stays the nominal one.  models: the C layout; family(x, u) -> x+ for x (B, nx), u (B, nu) (the host loops add w); family[slice]:
+    the plants of a shard; len(family): B."""
+
+    def __init__(self, kind, par=None, A=None, B=None, substeps: int = 10):
+        self.kind, self.substeps = kind, int(substeps)
+        self.par = self.A = self.B = None
+        if kind == "cartpole":
+            self.par = np.ascontiguousarray(par, dtype=np.float64).reshape(-1, 7)
+            self.trace = self._trace          # (the host loops take the physics-rate tracking error from a plant that has one)
+        elif kind == "linear":
+            self.A = np.ascontiguousarray(A, dtype=np.float64)
+            self.B = np.ascontiguousarray(B, dtype=np.float64)
+            if self.A.ndim != 3 or self.B.ndim != 3 or self.A.shape[1] != self.A.shape[2] or self.B.shape[:2] != self.A.shape[:2]:
+                raise ValueError("plant_family: A is (B, nx, nx) and B is (B, nx, nu)")
+        else:
+            raise ValueError(f"plant_family: unknown kind {kind!r}")
+
+    def __len__(self):
+        return (self.par if self.kind == "cartpole" else self.A).shape[0]
+
+    @property
+    def models(self):
+        """(B, 7), or (B, nx, nx + nu) rows [A_b[i, :] | B_b[i, :]]: what tmpc_mc_set_plant_models takes."""
+        return self.par if self.kind == "cartpole" else np.ascontiguousarray(np.concatenate([self.A, self.B], axis=2))
+
+    def __getitem__(self, idx):
+        if not isinstance(idx, slice):
+            idx = np.atleast_1d(idx)
+        if self.kind == "cartpole":
+            return PlantFamily("cartpole", par=self.par[idx], substeps=self.substeps)
+        return PlantFamily("linear", A=self.A[idx], B=self.B[idx])
+
+    def _trace(self, x, u):
+        from . import workloads
+        par = {k: self.par[:, i] for i, k in enumerate(CARTPOLE_KEYS)}
+        return workloads.cartpole_trace(x, np.asarray(u, dtype=np.float64).reshape(len(self), -1)[:, 0], self.par[:, 6], self.substeps, par)
+
+    def __call__(self, x, u):
+        if self.kind == "cartpole":
+            return self._trace(x, u)[-1]
+        return np.einsum("bij,bj->bi", self.A, x) + np.einsum("bij,bj->bi", self.B, u)
+
+
+def plant_family(kind, *, par=None, A=None, B=None, Th=0.02, substeps: int = 10):
+    """A plant per trajectory for the closed loops and the W estimate (PlantFamily).  kind "cartpole": par is a dict over
+    workloads.CARTPOLE_PARAMS' keys, each a scalar or (B,) -- missing keys take the nominal value, the period is Th --, or a (B, 7)
+    array of rows {M, m, b, I, g, l, Th}.  kind "linear": A (B, nx, nx), B (B, nx, nu)."""
+    if kind == "cartpole":
+        from .workloads import CARTPOLE_PARAMS
+        if par is None:
+            par = {}
+        if isinstance(par, dict):
+            unknown = set(par) - set(CARTPOLE_KEYS)
+            if unknown:
+                raise ValueError(f"plant_family: unknown cart-pole parameters {sorted(unknown)}")
+            cols = np.broadcast_arrays(*[np.atleast_1d(np.asarray(par.get(k, CARTPOLE_PARAMS[k]), dtype=np.float64)) for k in CARTPOLE_KEYS],
+                                       np.atleast_1d(np.asarray(Th, dtype=np.float64)))
+            par = np.stack(cols, axis=1)
+        return PlantFamily("cartpole", par=par, substeps=substeps)
+    return PlantFamily(kind, A=A, B=B)
+
+
+def sample_cartpole(n: int, spread: float, seed: int, first: int = 0, Th: float = 0.02, substeps: int = 10):
+    """n cart-poles around workloads.CARTPOLE_PARAMS: M, m and l are the nominal value times 1 + spread U(-1, 1), the cart's friction b
+    is spread U(0, 1); I and g stay.  Trajectory first + i takes the four words of Philox4x64-10 with key (seed, first + i) and counter
+    (0, PLANT_STREAM) as (M, m, l, b), u = (word >> 11) 2^-53: a trajectory's plant does not depend on how a sweep is sharded."""
+    from .workloads import CARTPOLE_PARAMS as P
+    g = np.uint64(first) + np.arange(n, dtype=np.uint64)
+    words = philox4x64(np.uint64(0), np.uint64(PLANT_STREAM), np.uint64(seed), g)                # (4, n)
+    u = (words >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    rel = 1.0 + float(spread) * (2.0 * u[:3] - 1.0)
+    return plant_family("cartpole", par=dict(M=P["M"] * rel[0], m=P["m"] * rel[1], l=P["l"] * rel[2], b=float(spread) * u[3]), Th=Th,
+                        substeps=substeps)
+
+
+plant_family.sample_cartpole = sample_cartpole
+
+
+def cartpole_rows(par, n: int, Th: float = 0.02):
+    """par= of the W estimates -> (n, 7) rows {M, m, b, I, g, l, Th}: a cart-pole PlantFamily, a dict as plant_family takes it, or rows."""
+    fam = par if isinstance(par, PlantFamily) else plant_family("cartpole", par=par, Th=Th)
+    if fam.kind != "cartpole":
+        raise ValueError("the W estimate runs cart-pole plants")
+    rows = fam.par
+    if rows.shape[0] == 1 and n != 1:
+        rows = np.repeat(rows, n, axis=0)
+    if rows.shape[0] != n:
+        raise ValueError(f"par holds {rows.shape[0]} plants, the estimate {n} trajectories")
+    return np.ascontiguousarray(rows)
+
+
 def plant_callable(plant):
-    """'cartpole' -> the numpy counterpart of the device plant (workloads.cartpole_step); callables pass through."""
+    """'cartpole' -> the numpy counterpart of the device plant (workloads.cartpole_step); callables -- a PlantFamily among them -- pass
+    through."""
     if callable(plant):
         return plant
     if plant == "cartpole":
@@ -440,6 +541,8 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     (tmpc_mc_set_device_rng) and by draw_realisations_philox, the same numbers, in the host loops.
     ref: a scalar or (T,) position reference; or (T, nx) one full-state schedule for every trajectory; or (K, T, nx) schedules
     with ref_id (n_total,) naming each trajectory's -- sliced with the shard, so the sweep stays shard-invariant.
+    plant: None / "cartpole"; in the host loop (on_device=False) also a PlantFamily of n_total plants (plant_family, sample_cartpole),
+    sliced with the shard.
     mean_burst: None -- independent losses; else every loss rate p as the stationary rate of burst_channel(p, mean_burst), on the
     same uniforms (a rate above 1 - 1 / mean_burst keeps independent losses, whose bursts last 1 / (1 - p) on average; every rate must be below 1).  link_stats: four more columns at the end of the table: lost_up, lost_down, max_gap, overrun."""
     import torch
@@ -469,6 +572,12 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
             raise ValueError("mc_sweep: mean_burst needs every loss rate below 1 (a channel that loses every packet has no bursts)")
         rate = p_loss[pi[lo:hi]]
         channel = burst_channel(rate, np.maximum(float(mean_burst), 1.0 / (1.0 - rate)))
+    if isinstance(plant, PlantFamily):                # a plant per trajectory of the whole sweep: the shard's
+        if len(plant) != n_total:
+            raise ValueError(f"mc_sweep: the plant family holds {len(plant)} plants, the sweep {n_total} trajectories")
+        plant = plant[lo:hi]
+        if on_device:
+            raise ValueError("mc_sweep: the device loop simulates one plant for the batch; a plant family goes with on_device=False")
     if on_device:        # state machines on the GPU as well (tmpc_mc_run); otherwise the host loop around determine_packets
         out = mpc.run_closed_loop(p_loss[pi[lo:hi]], ref, th, ga, w, extended=extended, plant=plant, warm_start=warm_start,
                                   timing=timing, device_rng=(seed, lo, model["w_bound"]) if device_rng else None, ref_id=ids,
@@ -543,7 +652,7 @@ def _box_result(samples, lo, hi, wmin, wmax, n_nonfinite, not_settled, x_final_n
 
 
 def estimate_disturbance_box_host(A, B, K, x0, T: int, discard: float = 0.025, plant="cartpole", Th: float = 0.02, substeps: int = 10,
-                                  settle_tol: float = 1e-3):
+                                  settle_tol: float = 1e-3, par=None):
     """The reference's estimate of the disturbance set (Results/estimate_W_for_Cartpole.py) on the numpy twin of the device plant
     (workloads.cartpole_step: the closed-form cart-pole, RK4 at the physics rate -- NOT the reference's PyBullet model, so the numbers
     are those of this plant and no replication of the reference's): closed loops u = -K x from the initial states x0 (n x 4) over T
@@ -552,6 +661,9 @@ def estimate_disturbance_box_host(A, B, K, x0, T: int, discard: float = 0.025, p
 
     The reference starts its sample list with one all-zero column (:77) that takes part in its quantiles; this function does not add
     it (at the reference's size, 39 900 samples, that changes the fourth significant digit of the box).
+
+    par: None -- every trajectory on workloads.CARTPOLE_PARAMS; or a cart-pole per trajectory (a PlantFamily, a dict as plant_family
+    takes it, or (n, 7) rows): A, B and K stay the nominal ones, so the samples contain the parametric mismatch of the family.
 
     Returns dict(samples (4, T - 1, n), lo, hi, w_bound = max(|lo|, |hi|), min, max, n_samples, n_nonfinite, not_settled: the number
     of trajectories with |x_T|_2 > settle_tol (:110), x_final_norm_max).  Non-finite samples are counted per component; a component
@@ -565,13 +677,14 @@ def estimate_disturbance_box_host(A, B, K, x0, T: int, discard: float = 0.025, p
     Acl = A - B @ K
     x = np.array(x0, dtype=np.float64).reshape(-1, 4)
     n = x.shape[0]
+    step = (lambda xk, uk: cartpole_step(xk, uk, Th, substeps)) if par is None else plant_family("cartpole", par=cartpole_rows(par, n, Th), substeps=substeps)
     samples = np.empty((4, T - 1, n))
     for k in range(T):
         xp = x
         u = np.zeros(n)
         for i in range(4):                                # the sums run in index order, as on the device
             u = u - K[0, i] * xp[:, i]
-        x = cartpole_step(xp, u, Th, substeps)
+        x = step(xp, u)
         if k + 1 < T:
             for c in range(4):
                 s = Acl[c, 0] * xp[:, 0]
@@ -595,12 +708,13 @@ def estimate_disturbance_box_host(A, B, K, x0, T: int, discard: float = 0.025, p
 
 def estimate_disturbance_box(A, B, K, x0=None, T: int = 400, discard: float = 0.025, plant="cartpole", x0_box=None, n_traj=None,
                              seed: int = 456, first: int = 0, Th: float = 0.02, substeps: int = 10, settle_tol: float = 1e-3,
-                             device: int = 0, want_samples: bool = False):
+                             device: int = 0, want_samples: bool = False, par=None):
     """estimate_disturbance_box_host on the device (include/tmpc.h: tmpc_estimate_w; csrc/tmpc_west.hip): one lane per trajectory,
     the samples stay in device memory (8 * 4 * (T - 1) * n_traj bytes), and the four order statistics behind the two quantiles of each
     component -- the neighbours floor and ceil of q (n - 1) -- are selected there exactly; the interpolation between them is numpy's.
     Initial states: x0 (n x 4), or x0_box = (lo, hi) with n_traj and seed: drawn on the device, trajectory first + i from the stream
     of draw_initial_states_philox.  Like the host twin -- and unlike the reference -- no all-zero sample is added in front.
+    par: a cart-pole per trajectory, as estimate_disturbance_box_host takes it (tmpc_estimate_w_models).
     Same return values (samples: None unless want_samples), and rollout_ms / selection_ms, the device times of the two stages."""
     from . import _native
     if x0 is not None:
@@ -610,7 +724,8 @@ def estimate_disturbance_box(A, B, K, x0=None, T: int = 400, discard: float = 0.
     n = int(n_traj) * (int(T) - 1)
     ranks, gam = quantile_ranks(max(n, 1), discard)
     out = _native.estimate_w(A, B, K, T, x0=x0, x0_box=x0_box, n_traj=n_traj, seed=seed, first=first, ranks=ranks, settle_tol=settle_tol,
-                             plant=plant, Th=Th, substeps=substeps, device=device, want_samples=want_samples)
+                             plant=plant, Th=Th, substeps=substeps, device=device, want_samples=want_samples,
+                             par=None if par is None else cartpole_rows(par, int(n_traj), Th))
     st = out["order_stats"]
     lo, hi = np.full(4, np.nan), np.full(4, np.nan)
     for c in range(4):

@@ -14,16 +14,44 @@ from .control_lite import c2d
 from .polytope_lite import Polytope, box2poly
 
 
+def cartpole_linearisation(par=None, Th=0.02):
+    """(A, B) of the cart-pole linearised about the upright position and sampled with a zero-order hold over Th: the (Ac, Bc) of
+    results_linear_system.py:35-47 pushed through c2d.  par: the mechanism -- None (CARTPOLE_PARAMS), a dict over its keys (scalars, or
+    arrays that broadcast against each other), or an array (..., 6) / (..., 7) of rows M, m, b, I, g, l[, Th] (a row's Th wins).
+    Batched over the leading axes: A (..., 4, 4), B (..., 4, 1).
+
+    This is the Jacobian of cartpole_rhs at the origin.  The reference writes the friction entry of the angular acceleration as
+    -m l b / p beside a Bc whose angle row is -m l / p; the equations of motion give +m l b / p there (the friction force enters like
+    -F).  With the reference's b = 0 the two agree -- cartpole() returns the bytes it always did -- and for b > 0 the sign here is
+    the one the nonlinear plant has."""
+    keys = ("M", "m", "b", "I", "g", "l")
+    if par is None:
+        par = CARTPOLE_PARAMS
+    if isinstance(par, dict):
+        cols = np.broadcast_arrays(*[np.asarray(par[k], dtype=np.float64) for k in keys], np.asarray(Th, dtype=np.float64))
+    else:
+        rows = np.asarray(par, dtype=np.float64)
+        if rows.shape[-1] not in (6, 7):
+            raise ValueError("cartpole_linearisation: rows of M, m, b, I, g, l[, Th]")
+        cols = [rows[..., i] for i in range(6)] + [rows[..., 6] if rows.shape[-1] == 7 else np.broadcast_to(np.float64(Th), rows.shape[:-1])]
+    lead = cols[0].shape
+    flat = [np.reshape(c, -1) for c in cols]
+    As, Bs = np.empty((flat[0].size, 4, 4)), np.empty((flat[0].size, 4, 1))
+    for k in range(flat[0].size):
+        M, m, b, I, g, l, th = (float(c[k]) for c in flat)
+        p = I * (M + m) + M * m * l ** 2
+        Ac = np.array([[0, 1, 0, 0],
+                       [0, -(I + m * l ** 2) * b / p, -(m ** 2 * g * l ** 2) / p, 0],
+                       [0, 0, 0, 1],
+                       [0, (m * l * b) / p, m * g * l * (M + m) / p, 0]], dtype=np.float64)
+        Bc = np.array([[0], [(I + m * l ** 2) / p], [0], [-m * l / p]], dtype=np.float64)
+        As[k], Bs[k] = c2d(Ac, Bc, th)
+    return As.reshape(lead + (4, 4)), Bs.reshape(lead + (4, 1))
+
+
 def cartpole(Th: float = 0.02):
     """Returns dict(A,B,Q,R,X,U,W) for the linearised cartpole (n=4, m=1)."""
-    M, m, b, I, g, l = 1.0, 0.1, 0.0, 0.001, 9.8, 0.5
-    p = I * (M + m) + M * m * l ** 2
-    Ac = np.array([[0, 1, 0, 0],
-                   [0, -(I + m * l ** 2) * b / p, -(m ** 2 * g * l ** 2) / p, 0],
-                   [0, 0, 0, 1],
-                   [0, -(m * l * b) / p, m * g * l * (M + m) / p, 0]], dtype=np.float64)
-    Bc = np.array([[0], [(I + m * l ** 2) / p], [0], [-m * l / p]], dtype=np.float64)
-    A, B = c2d(Ac, Bc, Th)
+    A, B = cartpole_linearisation(dict(M=1.0, m=0.1, b=0.0, I=0.001, g=9.8, l=0.5), Th)
     Q = np.diag([100.0, 10.0, 100.0, 10.0])
     R = 0.1 * np.eye(1)
     w = np.array([0.0001, 0.0027, 0.0003, 0.043])
@@ -86,9 +114,12 @@ def cartpole_rhs(x, F, par=CARTPOLE_PARAMS):
 def cartpole_trace(x, F, Th: float = 0.02, substeps: int = 10, par=CARTPOLE_PARAMS):
     """Zero-order hold of the force over one sampling period Th, classical RK4 with `substeps` steps (500 Hz for
     Th = 20 ms, the reference's physics rate, results_nonlinear_system.py:30-37).  Returns the states at the physics
-    steps, (substeps + 1, ...): [0] = x, [-1] = the state one sampling period later."""
+    steps, (substeps + 1, ...): [0] = x, [-1] = the state one sampling period later.  The entries of par, and Th, may be arrays
+    over the batch: a mechanism per trajectory."""
     x = np.array(x, dtype=np.float64)
     dt = Th / substeps
+    if np.ndim(dt):                   # a sampling period per trajectory (montecarlo.plant_family): against the state axis
+        dt = np.asarray(dt, dtype=np.float64)[..., None]
     xs = [x]
     for _ in range(substeps):
         k1 = cartpole_rhs(x, F, par)

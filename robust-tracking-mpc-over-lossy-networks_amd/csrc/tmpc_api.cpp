@@ -236,6 +236,9 @@ struct tmpc_handle {
     // tmpc_mc_set_channel: the Gilbert-Elliott thresholds [B][2][3] as the device compares them (mc_ch_B = 0: the Bernoulli model)
     int64_t mc_ch_B = 0;
     std::vector<double> mc_ch_thr;
+    // tmpc_mc_set_plant_models (regulator handles): a linear plant per trajectory, [B][nx][nx + nu] (mc_pm_B = 0: none)
+    int64_t mc_pm_B = 0;
+    std::vector<double> mc_pm;
     // closed-loop state: one grow-only arena (25 hipMalloc / hipFree per call cost several milliseconds), and what the last run
     // left in it
     Arena arena;
@@ -940,6 +943,22 @@ bool session_bars(tmpc_handle *h, const char *who) {
     return true;
 }
 
+// The cart-pole rows {M, m, b, I, g, l, Th} of n trajectories (tmpc_estimate_w_models): empty if every row
+// describes a plant, otherwise the message, which names trajectory and field.
+std::string cartpole_rows_error(const char *who, const double *rows, int64_t n) {
+    static const char *const field[7] = {"M", "m", "b", "I", "g", "l", "Th"};
+    for (int64_t b = 0; b < n; ++b)
+        for (int i = 0; i < 7; ++i) {
+            const double v = rows[b * 7 + i];
+            const char *why = nullptr;
+            if (!std::isfinite(v)) why = "is not finite";
+            else if ((i == 0 || i == 1 || i == 5 || i == 6) && !(v > 0.0)) why = "must be > 0";
+            else if ((i == 2 || i == 3) && v < 0.0) why = "must be >= 0";
+            if (why) return std::string(who) + ": " + field[i] + " of trajectory " + std::to_string(b) + " = " + std::to_string(v) + " " + why;
+        }
+    return std::string();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1138,6 +1157,35 @@ int tmpc_mc_set_plant(tmpc_handle *h, int kind, const double *par7, int substeps
     for (int i = 0; i < 7; ++i) h->plant_par[i] = par7[i];
     h->plant = kind;
     h->plant_substeps = substeps;
+    return TMPC_OK;
+}
+
+int tmpc_mc_set_plant_models(tmpc_handle *h, int kind, int64_t B, const double *models, int substeps) {
+    if (!h) return TMPC_E_INVALID;
+    const char *who = "tmpc_mc_set_plant_models";
+    (void)substeps;
+    if (session_bars(h, who)) return TMPC_E_INVALID;
+    if (!h->regulator) { h->err = std::string(who) + ": only regulator handles (tmpc_reg_run) take a plant per trajectory"; return TMPC_E_UNSUPPORTED; }
+    if (B < 0) { h->err = std::string(who) + ": B < 0"; return TMPC_E_INVALID; }
+    if (B == 0) {
+        h->mc_pm_B = 0;
+        h->mc_pm.clear();
+        return TMPC_OK;
+    }
+    if (kind == TMPC_PLANT_CARTPOLE) { h->err = std::string(who) + ": a regulator handle runs linear plants only"; return TMPC_E_INVALID; }
+    if (kind != TMPC_PLANT_LINEAR) { h->err = std::string(who) + ": kind is TMPC_PLANT_LINEAR"; return TMPC_E_INVALID; }
+    if (!models) { h->err = std::string(who) + ": models is NULL"; return TMPC_E_INVALID; }
+    const int64_t nx = h->nx, wid = h->nx + h->nu;
+    for (int64_t b = 0; b < B; ++b)
+        for (int64_t i = 0; i < nx; ++i)
+            for (int64_t j = 0; j < wid; ++j)
+                if (!std::isfinite(models[(b * nx + i) * wid + j])) {
+                    h->err = std::string(who) + ": " + (j < nx ? "A" : "B") + "[" + std::to_string(i) + ", " + std::to_string(j < nx ? j : j - nx) +
+                             "] of trajectory " + std::to_string(b) + " is not finite";
+                    return TMPC_E_INVALID;
+                }
+    h->mc_pm.assign(models, models + static_cast<size_t>(B) * static_cast<size_t>(nx * wid));
+    h->mc_pm_B = B;
     return TMPC_OK;
 }
 
@@ -1353,6 +1401,12 @@ void reference_table_pieces(tmpc_handle *h, Arena &a, tmpc::McState &st) {
 int channel_fits(tmpc_handle *h, const char *who, int64_t B) {
     if (B == h->mc_ch_B) return TMPC_OK;
     h->err = std::string(who) + ": B = " + std::to_string(B) + ", but the loss channel was set for B = " + std::to_string(h->mc_ch_B) + " trajectories";
+    return TMPC_E_INVALID;
+}
+// A loop of B trajectories under the handle's plant models (tmpc_mc_set_plant_models): does it fit?
+int plant_models_fit(tmpc_handle *h, const char *who, int64_t B) {
+    if (h->mc_pm_B == 0 || B == h->mc_pm_B) return TMPC_OK;
+    h->err = std::string(who) + ": B = " + std::to_string(B) + ", but the plant models were set for B = " + std::to_string(h->mc_pm_B) + " trajectories";
     return TMPC_E_INVALID;
 }
 // the loss model's and the link statistics' pieces of a loop's arena: the channel's thresholds and link states (both links start
@@ -1587,6 +1641,7 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
         return TMPC_E_INVALID;
     }
     if (h->reg_tube && h->hK.empty()) { h->err = "tmpc_reg_run: the tube regulator needs its gain K"; return TMPC_E_INVALID; }
+    if (const int r2 = plant_models_fit(h, "tmpc_reg_run", B)) return r2;
     if (h->device < 0) { h->err = "host-only handle (device < 0): nothing can be solved without the GPU"; return TMPC_E_DEVICE; }
     if (h->nu > 16) { h->err = "tmpc_reg_run: nu <= 16"; return TMPC_E_UNSUPPORTED; }
     if (B == 0 || T == 0) return TMPC_OK;
@@ -1614,6 +1669,7 @@ int tmpc_reg_run(tmpc_handle *h, int64_t B, int32_t T, const double *x0, const d
         a.piece(&m.hZ, 8 * static_cast<size_t>(rZ), hZ);
         a.piece(&st.x, 8 * b * nx, x0);
         a.piece(&st.cost, 8 * b, nullptr, 0);
+        if (h->mc_pm_B > 0) a.piece(&st.plant_lin, 8 * h->mc_pm.size(), h->mc_pm.data());      // (a regulator handle's models are linear)
         int32_t **counters[] = {&st.x_viol, &st.u_viol, &st.tube_viol, &st.not_optimal, &st.fail_step, &st.iters_sum};
         for (int32_t **c : counters) a.piece(c, 4 * b, nullptr, c == &st.fail_step ? 0xFF : 0);      // (0xFF bytes: fail_step = -1)
         if (host_w) {
@@ -2243,12 +2299,23 @@ int tmpc_estimate_w(int device, int32_t nx, int32_t nu, const double *A, const d
                     int64_t first_trajectory, int32_t n_rank, const int64_t *ranks, double settle_tol, double *order_stats, double *w_min,
                     double *w_max, int64_t *n_samples, int64_t *n_nonfinite, int64_t *not_settled, double *x_final_norm_max,
                     double *x0_used, double *samples, float *kernel_ms) {
+    if (!par7) { g_create_error = "tmpc_estimate_w: NULL argument"; return TMPC_E_INVALID; }
+    return tmpc_estimate_w_models(device, nx, nu, A, B, K, plant, par7, nullptr, substeps, n_traj, T, x0, x0_lo, x0_hi, seed, first_trajectory, n_rank,
+                                  ranks, settle_tol, order_stats, w_min, w_max, n_samples, n_nonfinite, not_settled, x_final_norm_max, x0_used,
+                                  samples, kernel_ms);
+}
+
+int tmpc_estimate_w_models(int device, int32_t nx, int32_t nu, const double *A, const double *B, const double *K, int plant, const double *par7,
+                           const double *par_traj, int32_t substeps, int64_t n_traj, int32_t T, const double *x0, const double *x0_lo,
+                           const double *x0_hi, uint64_t seed, int64_t first_trajectory, int32_t n_rank, const int64_t *ranks, double settle_tol,
+                           double *order_stats, double *w_min, double *w_max, int64_t *n_samples, int64_t *n_nonfinite, int64_t *not_settled,
+                           double *x_final_norm_max, double *x0_used, double *samples, float *kernel_ms) {
     const char *who = "tmpc_estimate_w";
     if (plant != TMPC_PLANT_CARTPOLE || nx != tmpc::WEST_NX || nu != 1) {
         g_create_error = "tmpc_estimate_w: only TMPC_PLANT_CARTPOLE (nx = 4, nu = 1) is supported";
         return TMPC_E_UNSUPPORTED;
     }
-    if (!A || !B || !K || !par7 || (!x0 && (!x0_lo || !x0_hi)) || (n_rank > 0 && !ranks)) { g_create_error = "tmpc_estimate_w: NULL argument"; return TMPC_E_INVALID; }
+    if (!A || !B || !K || (!par7 && !par_traj) || (!x0 && (!x0_lo || !x0_hi)) || (n_rank > 0 && !ranks)) { g_create_error = "tmpc_estimate_w: NULL argument"; return TMPC_E_INVALID; }
     if (n_traj < 1 || T < 2 || substeps < 1 || n_rank < 0 || first_trajectory < 0) {
         g_create_error = "tmpc_estimate_w: need n_traj >= 1, T >= 2, substeps >= 1, n_rank >= 0, first_trajectory >= 0";
         return TMPC_E_INVALID;
@@ -2256,6 +2323,10 @@ int tmpc_estimate_w(int device, int32_t nx, int32_t nu, const double *A, const d
     const int64_t n = n_traj * static_cast<int64_t>(T - 1);
     for (int32_t r = 0; r < n_rank; ++r)
         if (ranks[r] < 0 || ranks[r] >= n) { g_create_error = "tmpc_estimate_w: rank out of range [0, n_traj (T - 1))"; return TMPC_E_INVALID; }
+    if (par_traj) {
+        const std::string bad = cartpole_rows_error("tmpc_estimate_w_models", par_traj, n_traj);
+        if (!bad.empty()) { g_create_error = bad; return TMPC_E_INVALID; }
+    }
     constexpr int NX = tmpc::WEST_NX;
     tmpc::WestRollout a{};
     {
@@ -2267,14 +2338,14 @@ int tmpc_estimate_w(int device, int32_t nx, int32_t nu, const double *A, const d
             }
     }
     for (int i = 0; i < NX; ++i) { a.K[i] = K[i]; a.lo[i] = x0 ? 0.0 : x0_lo[i]; a.hi[i] = x0 ? 0.0 : x0_hi[i]; }
-    for (int i = 0; i < 7; ++i) a.par[i] = par7[i];
+    for (int i = 0; i < 7; ++i) a.par[i] = par7 ? par7[i] : par_traj[i];
     a.substeps = substeps; a.T = T; a.draw = x0 ? 0 : 1;
     a.n_traj = n_traj; a.first = first_trajectory; a.seed = seed;
 
     WEST_TRY(hipSetDevice(device));
     WestMem mem;
     const size_t nt = static_cast<size_t>(n_traj);
-    double *d_samples = nullptr, *d_x0 = nullptr, *d_x0u = nullptr, *d_norm = nullptr;
+    double *d_samples = nullptr, *d_x0 = nullptr, *d_x0u = nullptr, *d_norm = nullptr, *d_par = nullptr;
     unsigned long long *d_mm = nullptr;
     if (mem.get(&d_samples, static_cast<size_t>(n) * NX * 8) != hipSuccess) {
         (void)hipGetLastError();
@@ -2288,9 +2359,13 @@ int tmpc_estimate_w(int device, int32_t nx, int32_t nu, const double *A, const d
         WEST_TRY(mem.get(&d_x0, nt * NX * 8));
         WEST_TRY(hipMemcpy(d_x0, x0, nt * NX * 8, hipMemcpyHostToDevice));
     }
+    if (par_traj) {
+        WEST_TRY(mem.get(&d_par, nt * 7 * 8));
+        WEST_TRY(hipMemcpy(d_par, par_traj, nt * 7 * 8, hipMemcpyHostToDevice));
+    }
     WEST_TRY(hipMemset(d_mm, 0xff, NX * 8));
     WEST_TRY(hipMemset(d_mm + NX, 0, NX * 8));
-    a.x0 = d_x0; a.x0_used = d_x0u; a.samples = d_samples; a.xnorm = d_norm; a.minmax = d_mm;
+    a.x0 = d_x0; a.x0_used = d_x0u; a.samples = d_samples; a.xnorm = d_norm; a.minmax = d_mm; a.par_traj = d_par;
     WestEvents ev;
     for (hipEvent_t &e : ev.ev) WEST_TRY(hipEventCreate(&e));
     WEST_TRY(hipEventRecord(ev.ev[0], nullptr));

@@ -246,6 +246,7 @@ struct RegState {                        // [trajectory]-major device arrays
     const double *w_bound;               // [nx]
     long long cap_index;                 // recorded trajectory (-1: none)
     double *cap_x, *cap_xn, *cap_u;      // [T+1][nx], [T][nx], [T][nu]
+    const double *plant_lin;             // [B][nx][nx + nu] a plant per trajectory, rows [A_b[i, :] | B_b[i, :]] (tmpc_mc_set_plant_models), or nullptr: the model's (A, B)
 };
 hipError_t launch_reg_step(const RegModel &m, const RegState &st, int t, int T, int64_t B, const double *u_nom, const double *x_nom0,
                            const int32_t *status, const int32_t *iters, hipStream_t stream);

@@ -5,7 +5,8 @@
 //   applies   u_t = u_nom_0 - K (x_t - x_nom_0)        (the reference's sign: K is the LQR gain of u = -K x; plain: u_t = u_nom_0)
 //   checks    x_t in X, u_t in U, x_t - x_nom_0 in Z   (the rows of each set spread over the lanes)
 //   sums      x_t'Q x_t + u_t'R u_t
-//   updates   x_{t+1} = A x_t + B u_t + w_t           (w: host array, or the Philox stream of tmpc_mc_set_device_rng)
+//   updates   x_{t+1} = A x_t + B u_t + w_t           (w: host array, or the Philox stream of tmpc_mc_set_device_rng; A, B: the model's, or
+//                                                      the trajectory's own plant of tmpc_mc_set_plant_models -- the solve keeps the model's)
 // and writes x_{t+1} in place, where the next solve reads its x_k.
 //
 // Form as mc_step_wave (tmpc_mc_step.hpp): one wavefront per trajectory, component i of every state-sized vector on lane i,
@@ -125,9 +126,15 @@ __global__ __launch_bounds__(RWAVE * REG_WPB) void reg_step_kernel(const RegMode
     // ---- plant
     double xp_l = 0.0;
     if (lx) {
+        // row `lane` of the model's (A, B), or of the trajectory's own plant [A_b | B_b] (tmpc_mc_set_plant_models): one arithmetic path
+        const double *ap = m.A + lane * nx, *bp = m.B + lane * nu;
+        if (st.plant_lin != nullptr) {
+            ap = st.plant_lin + (b * nx + lane) * static_cast<int64_t>(nx + nu);
+            bp = ap + nx;
+        }
         double v = 0.0;
-        for (int k = 0; k < nx; ++k) v += m.A[lane * nx + k] * S[R_X][k];
-        for (int j = 0; j < nu; ++j) v += m.B[lane * nu + j] * S[R_U][j];
+        for (int k = 0; k < nx; ++k) v += ap[k] * S[R_X][k];
+        for (int j = 0; j < nu; ++j) v += bp[j] * S[R_U][j];
         xp_l = v + w_l;
         st.x[b * nx + lane] = xp_l;
     }

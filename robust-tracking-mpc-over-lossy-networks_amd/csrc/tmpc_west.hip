@@ -92,7 +92,15 @@ __global__ __launch_bounds__(WEST_ROLL_THREADS) void west_rollout_kernel(WestRol
     double mn[4], mx[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { mn[i] = INFINITY; mx[i] = -INFINITY; }
-    const double dt = a.par[6] / a.substeps;
+    // the plant of the lane's trajectory: the call's, or the lane's own seven numbers (tmpc_estimate_w_models); Acl and K stay the model's
+    double par[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) par[i] = a.par[i];
+    if (a.par_traj != nullptr && live) {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) par[i] = a.par_traj[b * 7 + i];
+    }
+    const double dt = par[6] / a.substeps;
     const int64_t per_comp = static_cast<int64_t>(a.T - 1) * a.n_traj;
     if (live) {
         for (int k = 0; k < a.T; ++k) {
@@ -103,13 +111,13 @@ __global__ __launch_bounds__(WEST_ROLL_THREADS) void west_rollout_kernel(WestRol
             // zero-order hold of u over the sampling period, RK4 at the physics rate: the hold of mcstep::mc_step_wave, operation for operation
             for (int sstep = 0; sstep < a.substeps; ++sstep) {
                 double k1[4], k2[4], k3[4], k4[4], yt[4];
-                mcstep::cartpole_rhs(a.par, x, u0, k1);
+                mcstep::cartpole_rhs(par, x, u0, k1);
                 for (int i = 0; i < 4; ++i) yt[i] = x[i] + 0.5 * dt * k1[i];
-                mcstep::cartpole_rhs(a.par, yt, u0, k2);
+                mcstep::cartpole_rhs(par, yt, u0, k2);
                 for (int i = 0; i < 4; ++i) yt[i] = x[i] + 0.5 * dt * k2[i];
-                mcstep::cartpole_rhs(a.par, yt, u0, k3);
+                mcstep::cartpole_rhs(par, yt, u0, k3);
                 for (int i = 0; i < 4; ++i) yt[i] = x[i] + dt * k3[i];
-                mcstep::cartpole_rhs(a.par, yt, u0, k4);
+                mcstep::cartpole_rhs(par, yt, u0, k4);
                 for (int i = 0; i < 4; ++i) x[i] += dt / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
             }
             // the state after the last period is not sampled (estimate_W_for_Cartpole.py:94-107: w is formed when the NEXT input is)

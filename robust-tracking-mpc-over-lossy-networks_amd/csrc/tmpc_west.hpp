@@ -26,6 +26,7 @@ struct WestRollout {
     double *samples;                     // [4][T - 1][n_traj]
     double *xnorm;                       // [n_traj]  |x_T|_2
     unsigned long long *minmax;          // [8] order-preserving keys: min of the four components (start: all ones), max (start: 0)
+    const double *par_traj;              // [n_traj][7] the cart-pole of every trajectory (tmpc_estimate_w_models), or nullptr: par
 };
 
 hipError_t launch_west_rollout(const WestRollout &a, hipStream_t stream);

@@ -34,6 +34,10 @@ def main():
                     help="losses in bursts of L steps on average at the same stationary loss rates (tmpc_mc_set_channel: the Gilbert "
                          "channel of montecarlo.burst_channel; a rate above 1 - 1 / L keeps independent losses); adds the "
                          "link statistics to the table")
+    ap.add_argument("--plant-spread", type=float, default=None, metavar="S",
+                    help="with --host-loop: a cart-pole per trajectory instead of the controller's model: M, m, l within "
+                         "+-S of nominal, cart friction up to S (montecarlo.sample_cartpole, keyed by the global trajectory index); "
+                         "the controller keeps the nominal model")
     ap.add_argument("--host-loop", action="store_true", help="state machines in numpy on the host instead of on the device")
     ap.add_argument("--all-controllers", action="store_true",
                     help="tube MPC, extended tube MPC and the tracking MPC one after the other on the SAME realisations "
@@ -60,6 +64,13 @@ def main():
         controllers = [("tube MPC", False, False), ("extended tube MPC", True, False), ("tracking MPC (non-robust)", False, True)]
     else:
         controllers = [("tracking MPC (non-robust)" if args.rmpc else ("extended tube MPC" if args.extended else "tube MPC"), args.extended, args.rmpc)]
+    plant = None
+    if args.plant_spread is not None:
+        if args.reference_streams:
+            raise SystemExit("--plant-spread goes with the per-trajectory streams, not with --reference-streams")
+        if not args.host_loop:
+            raise SystemExit("--plant-spread needs --host-loop: the device loop simulates one plant for the whole batch")
+        plant = montecarlo.sample_cartpole(len(p_loss) * args.n_mc, args.plant_spread, seed=20240301)
     for label, extended, rmpc in controllers:
         # controller set up in the package: offline sets through the batched LP kernel on this rank's device (0.2 s)
         mpc, model = workloads.make_controller("cartpole", args.N, True, extended=extended, device=local, tracking=rmpc)
@@ -80,7 +91,7 @@ def main():
             table, pi = montecarlo.mc_sweep(mpc, model, p_loss, args.n_mc, args.T, args.ref, rank=rank, world=world,
                                             extended=extended, device=device, on_device=not args.host_loop, warm_start=args.warm_start,
                                             timing=args.timing and not args.host_loop, device_rng=args.device_rng, force_collective=use_pg,
-                                            mean_burst=args.mean_burst, link_stats=args.mean_burst is not None)
+                                            mean_burst=args.mean_burst, link_stats=args.mean_burst is not None, plant=plant)
         dt = time.time() - t0
         if rank == 0:
             report(label, table, pi, p_loss, dt, world, args)
@@ -92,6 +103,8 @@ def main():
 
 def report(label, table, pi, p_loss, dt, world, args):
     n = len(pi)
+    if args.plant_spread is not None:
+        label += f", nonlinear cart-poles of spread {args.plant_spread:g}"
     print(f"== {label}: {n} trajectories x {args.T} steps = {n * args.T} solves in {dt:.2f} s on {world} GPU(s): {n * args.T / dt:.3e} MPC steps/s (end to end)")
     print("p_loss  mean tracking error   tube violations   non-optimal solves   infeasible runs")
     for i, p in enumerate(p_loss):
