@@ -624,6 +624,73 @@ def mc_link_stats(h: Handle, B: int) -> dict:
 MC_FUSED = {"off": 0, "on": 1, "auto": 2, False: 0, True: 1, None: 2}      # include/tmpc.h: TMPC_MC_FUSED_*
 
 
+def _contiguous(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _set_loop_options(h: Handle, timing, warm_start, capture, fused="keep"):
+    """The per-call settings of a tracking loop (mc_run, mc_open): tmpc_set_solve_timing, tmpc_mc_set_warm_start, tmpc_mc_set_capture
+    and -- mc_run; a session has one launch form and leaves the setting alone -- tmpc_mc_set_fused.  THE place where a new per-call
+    loop option is set."""
+    calls = [(lib().tmpc_set_solve_timing, int(bool(timing))), (lib().tmpc_mc_set_warm_start, int(bool(warm_start))),
+             (lib().tmpc_mc_set_capture, -1 if capture is None else int(capture))]
+    if fused != "keep":
+        calls.insert(1, (lib().tmpc_mc_set_fused, MC_FUSED[fused]))
+    for call, arg in calls:
+        if call(h.ptr, arg) != 0:
+            raise RuntimeError(h.error())
+
+
+def _set_device_rng(h: Handle, device_rng=None, draws_w: bool = True):
+    """tmpc_mc_set_device_rng: on with device_rng = (seed, first_trajectory, w_bound), off with None.  draws_w False (the session: w is
+    the plant's): (seed, first_trajectory[, ignored])."""
+    args = (0, 0, 0, None)
+    if device_rng is not None:
+        seed, first, w_bound = device_rng if draws_w else (device_rng[0], device_rng[1], None)
+        wb = None if w_bound is None else _contiguous(w_bound).reshape(h.nx)
+        args = (1, int(seed), int(first), _ptr(wb))
+    if lib().tmpc_mc_set_device_rng(h.ptr, *args) != 0:
+        raise RuntimeError(h.error())
+
+
+def _check_set(P, dim: int, who: str):
+    """(H, h, rows) of a check polytope, or (None, None, 0)."""
+    if P is None:
+        return None, None, 0
+    HA, hb = _contiguous(P.A), _contiguous(P.b).reshape(-1)
+    if HA.ndim != 2 or HA.shape[1] != dim or hb.size != HA.shape[0]:
+        raise ValueError(f"{who}: a check set has the wrong dimension")
+    return HA, hb, HA.shape[0]
+
+
+def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode: int, capture, timing) -> dict:
+    """Completes the result of a tracking loop (mc_run, mc_close) over the `steps` steps taken of T: the recorded trajectory, the
+    solve times, the link statistics and the derived statistics.  THE place where a new loop output is fetched."""
+    n = steps
+    if capture is not None:
+        xt, xn, ut = np.empty((T, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))
+        if lib().tmpc_mc_get_capture(h.ptr, T, xt.ctypes.data, xn.ctypes.data, ut.ctypes.data) != 0:
+            raise RuntimeError(h.error())
+        out["x_traj"], out["x_nom_traj"], out["u_traj"] = xt[:n], xn[:n], ut[:n]
+    if timing:
+        tsum, tmax = np.empty(B, np.int64), np.empty(B, np.int64)
+        if lib().tmpc_mc_get_solve_ticks(h.ptr, B, tsum.ctypes.data, tmax.ctypes.data) != 0:
+            raise RuntimeError(h.error())
+        out["solve_time_mean"], out["solve_time_max"] = tsum * (TICK_SECONDS / max(n, 1)), tmax * TICK_SECONDS
+    out["link_stats"] = mc_link_stats(h, B)
+    out.update(out["link_stats"])
+    out["loop_mode"] = loop_mode      # 1: one launch per sweep; 2: one launch per problem and step; 0: solve launches + a state-machine launch per step
+    out["fused"] = loop_mode == 1
+    out["tracking_error"] = np.sqrt(out["err2"]) / max(n, 1)
+    out["consistent_estimate_error"] = float(out["consistent"].max()) if B else 0.0
+    out["iters_mean"] = float(out["iters_sum"].sum()) / max(B * n, 1)            # interior-point iterations per solve
+    return out
+
+
 def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: bool = False, warm_start: bool = False,
            capture=None, timing: bool = False, physics_substeps: int = 0, device_rng=None, fused=None, ref_id=None, T=None,
            channel=None) -> dict:
@@ -645,29 +712,17 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     channel: the Gilbert-Elliott loss channel of this call (mc_set_channel; None: independent losses with probability p_loss, and
     an earlier channel is cleared); p_loss is then not read and may be None.  The result carries the link statistics lost_up,
     lost_down, max_gap, overrun (also as the dict link_stats) with either loss model."""
-    if lib().tmpc_set_solve_timing(h.ptr, int(bool(timing))) != 0:
-        raise RuntimeError(h.error())
-    if lib().tmpc_mc_set_fused(h.ptr, MC_FUSED[fused]) != 0:
-        raise RuntimeError(h.error())
-    if lib().tmpc_mc_set_warm_start(h.ptr, int(bool(warm_start))) != 0:
-        raise RuntimeError(h.error())
-    if lib().tmpc_mc_set_capture(h.ptr, -1 if capture is None else int(capture)) != 0:
-        raise RuntimeError(h.error())
-    c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    _set_loop_options(h, timing, warm_start, capture, fused)
+    c, ptr = _contiguous, _ptr
     p_loss, ch_par, n_traj = loop_batch("mc_run", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if T is None and device_rng is None and th_u is not None:
         T = np.shape(th_u)[1]
     ref, T_ref = _loop_reference(h, "mc_run", ref, n_traj, T, ref_id)
+    _set_device_rng(h, device_rng)
     if device_rng is not None:
-        seed, first, w_bound = device_rng
-        wb = None if w_bound is None else c(w_bound).reshape(h.nx)
-        if lib().tmpc_mc_set_device_rng(h.ptr, 1, int(seed), int(first), None if wb is None else wb.ctypes.data) != 0:
-            raise RuntimeError(h.error())
         th_u = ga_u = w = None
         B, T = n_traj, T_ref
     else:
-        if lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None) != 0:
-            raise RuntimeError(h.error())
         th_u, ga_u, w = c(th_u), c(ga_u), c(w)
         B, T = th_u.shape
         if ch_par is not None and ch_par[0].shape[0] != B:
@@ -676,14 +731,9 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
             raise ValueError("mc_run: inconsistent shapes" + (f" (a constant full-state reference over T <= nx = {h.nx} steps is (1, nx): "
                                                               "(nx,) is then read as the legacy (T,) form)" if ref is not None and ref.shape == (h.nx,) else ""))
     x0c = None if x0 is None else c(x0).reshape(B, h.nx)
-    HZ = hZ = None
-    rZ = 0
-    if Z is not None:
-        HZ, hZ = c(Z.A), c(Z.b)
-        rZ = HZ.shape[0]
+    HZ, hZ, rZ = _check_set(Z, h.nx, "mc_run")
     out = dict(err2=np.empty(B), tube_violations=np.empty(B, np.int32), not_optimal=np.empty(B, np.int32),
                x_final=np.empty((B, h.nx)), consistent=np.empty(B), iters_sum=np.empty(B, np.int32))
-    ptr = lambda a: None if a is None else a.ctypes.data
     mc_set_channel(h, ch_par)            # (None clears an earlier one; set last, so that no refused call leaves its channel behind)
     rc = lib().tmpc_mc_run(h.ptr, B, T, int(bool(extended)), ptr(p_loss), ptr(ref), ptr(th_u), ptr(ga_u), ptr(w), ptr(x0c),
                            ptr(HZ), ptr(hZ), rZ, ptr(out["err2"]), ptr(out["tube_violations"]), ptr(out["not_optimal"]),
@@ -692,39 +742,12 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
         msg = h.error()
         mc_set_channel(h, None)          # a refused loop leaves no channel behind
         raise RuntimeError(f"tmpc_mc_run failed ({rc}): {msg}")
-    if capture is not None:
-        out["x_traj"], out["x_nom_traj"], out["u_traj"] = np.empty((T, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))
-        if lib().tmpc_mc_get_capture(h.ptr, T, ptr(out["x_traj"]), ptr(out["x_nom_traj"]), ptr(out["u_traj"])) != 0:
-            raise RuntimeError(h.error())
-    if timing:
-        tsum, tmax = np.empty(B, np.int64), np.empty(B, np.int64)
-        if lib().tmpc_mc_get_solve_ticks(h.ptr, B, tsum.ctypes.data, tmax.ctypes.data) != 0:
-            raise RuntimeError(h.error())
-        out["solve_time_mean"], out["solve_time_max"] = tsum * (TICK_SECONDS / max(T, 1)), tmax * TICK_SECONDS
     if physics_substeps > 0:
         out["err2_physics"] = np.empty(B)
         if lib().tmpc_mc_get_physics_error(h.ptr, B, ptr(out["err2_physics"])) != 0:
             raise RuntimeError(h.error())
         out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * physics_substeps)
-    out["link_stats"] = mc_link_stats(h, B)
-    out.update(out["link_stats"])
-    out["loop_mode"] = int(lib().tmpc_mc_last_fused(h.ptr))       # 1: one launch per sweep; 2: one launch per problem and step; 0: + a state-machine launch
-    out["fused"] = out["loop_mode"] == 1
-    out["tracking_error"] = np.sqrt(out["err2"]) / T
-    out["consistent_estimate_error"] = float(out["consistent"].max()) if B else 0.0
-    out["iters_mean"] = float(out["iters_sum"].sum()) / max(B * T, 1)            # interior-point iterations per solve
-    return out
-
-
-def _check_set(P, dim: int, who: str):
-    """(H, h, rows) of a check polytope, or (None, None, 0)."""
-    if P is None:
-        return None, None, 0
-    HA = np.ascontiguousarray(np.asarray(P.A, dtype=np.float64))
-    hb = np.ascontiguousarray(np.asarray(P.b, dtype=np.float64)).reshape(-1)
-    if HA.ndim != 2 or HA.shape[1] != dim or hb.size != HA.shape[0]:
-        raise ValueError(f"{who}: a check set has the wrong dimension")
-    return HA, hb, HA.shape[0]
+    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing)
 
 
 def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=None, X=None, U=None, extended: bool = False,
@@ -735,7 +758,7 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
     mc_run), x0 (B, nx) or None; T: steps the session may take (default: len(ref)); Z / X / U: tube cross-section and the check
     sets for x_t / u_t (polytopes or None).  No disturbance is drawn: w is the plant's.  channel: the Gilbert-Elliott loss channel of
     the session (mc_run; p_loss may then be None).  Returns what mc_close needs."""
-    c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))      # noqa: E731
+    c, ptr = _contiguous, _ptr
     p_loss, ch_par, B = loop_batch("mc_open", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if p_loss is not None:
         p_loss = p_loss.reshape(-1)
@@ -744,17 +767,11 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
     T = T_ref if T is None else int(T)
     if (ref.shape[0] if ref is not None else T_ref) < T:
         raise ValueError("mc_open: ref must cover the T steps of the session")
-    for call, arg in ((lib().tmpc_set_solve_timing, int(bool(timing))), (lib().tmpc_mc_set_warm_start, int(bool(warm_start))),
-                      (lib().tmpc_mc_set_capture, -1 if capture is None else int(capture))):
-        if call(h.ptr, arg) != 0:
-            raise RuntimeError(h.error())
+    _set_loop_options(h, timing, warm_start, capture)
+    _set_device_rng(h, device_rng, draws_w=False)
     if device_rng is not None:
-        if lib().tmpc_mc_set_device_rng(h.ptr, 1, int(device_rng[0]), int(device_rng[1]), None) != 0:
-            raise RuntimeError(h.error())
         th_u = ga_u = None
     else:
-        if lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None) != 0:
-            raise RuntimeError(h.error())
         th_u, ga_u = c(th_u), c(ga_u)
         if th_u.shape != (B, T) or ga_u.shape != (B, T):
             raise ValueError(f"mc_open: th_u and ga_u must be (B, T) = {(B, T)}")
@@ -762,7 +779,6 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
     HZ, hZ, rZ = _check_set(Z, h.nx, "mc_open")
     HX, hX, rX = _check_set(X, h.nx, "mc_open")
     HU, hU, rU = _check_set(U, h.nu, "mc_open")
-    ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
     mc_set_channel(h, ch_par)            # (as in mc_run: last)
     rc = lib().tmpc_mc_open(h.ptr, B, T, int(bool(extended)), ptr(p_loss), ptr(ref), ptr(th_u), ptr(ga_u), ptr(x0c),
                             ptr(HZ), ptr(hZ), rZ, ptr(HX), ptr(hX), rX, ptr(HU), ptr(hU), rU)
@@ -823,25 +839,8 @@ def mc_close(h: Handle, info: dict) -> dict:
                                                                    "not_optimal", "consistent", "iters_sum")], C.addressof(steps))
     if rc != 0:
         raise RuntimeError(f"tmpc_mc_close failed ({rc}): {h.error()}")
-    out["link_stats"] = mc_link_stats(h, B)
-    out.update(out["link_stats"])
-    n = out["steps"] = int(steps.value)
-    if info.get("capture") is not None:
-        xt, xn, ut = np.empty((T, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))
-        if lib().tmpc_mc_get_capture(h.ptr, T, xt.ctypes.data, xn.ctypes.data, ut.ctypes.data) != 0:
-            raise RuntimeError(h.error())
-        out["x_traj"], out["x_nom_traj"], out["u_traj"] = xt[:n], xn[:n], ut[:n]
-    if info.get("timing"):
-        tsum, tmax = np.empty(B, np.int64), np.empty(B, np.int64)
-        if lib().tmpc_mc_get_solve_ticks(h.ptr, B, tsum.ctypes.data, tmax.ctypes.data) != 0:
-            raise RuntimeError(h.error())
-        out["solve_time_mean"], out["solve_time_max"] = tsum * (TICK_SECONDS / max(n, 1)), tmax * TICK_SECONDS
-    out["loop_mode"] = 0          # solve launches + a state-machine launch per step
-    out["fused"] = False
-    out["tracking_error"] = np.sqrt(out["err2"]) / max(n, 1)
-    out["consistent_estimate_error"] = float(out["consistent"].max()) if B else 0.0
-    out["iters_mean"] = float(out["iters_sum"].sum()) / max(B * n, 1)
-    return out
+    out["steps"] = int(steps.value)
+    return _tracking_result(h, out, B, T, out["steps"], 0, info.get("capture"), info.get("timing"))
 
 
 def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=None, capture=None, plant=None) -> dict:
@@ -850,7 +849,7 @@ def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=No
     montecarlo.draw_realisations_philox); neither: no disturbance.  X, U, Z: check sets (polytopes) or None.  capture: index of
     a trajectory whose x_traj (T+1, nx), x_nom_traj (T, nx), u_traj (T, nu) are returned.  plant: None -- the model's (A, B); or a
     linear montecarlo.PlantFamily, a plant per trajectory (tmpc_mc_set_plant_models)."""
-    c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))      # noqa: E731
+    c, ptr = _contiguous, _ptr
     if plant is not None and getattr(plant, "kind", None) != "linear":
         raise ValueError("reg_run: plant is None or a linear plant family")
     mc_set_plant_models(h, "linear", None if plant is None else plant.models)      # (None clears what an earlier call left)
@@ -860,30 +859,13 @@ def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=No
         w = c(w)
         if w.shape != (B, T, h.nx):
             raise ValueError(f"reg_run: w must be (B, T, nx) = {(B, T, h.nx)}, got {w.shape}")
-        rc = lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None)
-    elif device_rng is not None:
-        seed, first, w_bound = device_rng
-        wb = c(w_bound).reshape(h.nx)
-        rc = lib().tmpc_mc_set_device_rng(h.ptr, 1, int(seed), int(first), wb.ctypes.data)
-    else:
-        rc = lib().tmpc_mc_set_device_rng(h.ptr, 0, 0, 0, None)
-    if rc != 0:
-        raise RuntimeError(h.error())
-    sets = []
-    for P, dim in ((X, h.nx), (U, h.nu), (Z, h.nx)):
-        if P is None:
-            sets += [None, None, 0]
-        else:
-            HA, hb = c(P.A), c(P.b).reshape(-1)
-            if HA.ndim != 2 or HA.shape[1] != dim or hb.size != HA.shape[0]:
-                raise ValueError("reg_run: a check set has the wrong dimension")
-            sets += [HA, hb, HA.shape[0]]
+    _set_device_rng(h, None if w is not None else device_rng)
+    sets = [v for P, dim in ((X, h.nx), (U, h.nu), (Z, h.nx)) for v in _check_set(P, dim, "reg_run")]
     out = dict(cost=np.empty(B), x_viol=np.empty(B, np.int32), u_viol=np.empty(B, np.int32), tube_viol=np.empty(B, np.int32),
                not_optimal=np.empty(B, np.int32), fail_step=np.empty(B, np.int32), x_final=np.empty((B, h.nx)),
                iters_sum=np.empty(B, np.int32))
     cap = -1 if capture is None else int(capture)
     cx, cxn, cu = (np.empty((T + 1, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))) if cap >= 0 else (None, None, None)
-    ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
     args = [ptr(a) if isinstance(a, np.ndarray) or a is None else a for a in sets]
     rc = lib().tmpc_reg_run(h.ptr, B, T, ptr(x0), ptr(w), *args, ptr(out["cost"]), ptr(out["x_viol"]), ptr(out["u_viol"]),
                             ptr(out["tube_viol"]), ptr(out["not_optimal"]), ptr(out["fail_step"]), ptr(out["x_final"]),
@@ -900,7 +882,7 @@ def mc_replay(h: Handle, U, theta, gamma, w, xn0=None, x0=None, extended: bool =
     packets (no QP is solved).  U (B, T, N+1, nu): packets, terminal column last; theta, gamma (B, T): arrival flags;
     w (B, T, nx); xn0 (B, T, nx) for the extended controller.  Returns per step x (state after the step), x_hat (estimate
     after the step), x_nom (nominal state in the plant's packet), u (applied input), s, Theta, q."""
-    c = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    c, ptr = _contiguous, _ptr
     U, w = c(U), c(w)
     B, T = U.shape[:2]
     if U.shape != (B, T, h.N + 1, h.nu) or w.shape != (B, T, h.nx):
@@ -912,7 +894,6 @@ def mc_replay(h: Handle, U, theta, gamma, w, xn0=None, x0=None, extended: bool =
     tf = np.empty((B, T, 3 * h.nx + h.nu))
     ti = np.empty((B, T, 3), np.int32)
     mc_set_actuator(h, smart)
-    ptr = lambda a: None if a is None else a.ctypes.data
     try:
         rc = lib().tmpc_mc_replay(h.ptr, B, T, int(bool(extended)), ptr(U), ptr(xn0c), ptr(th), ptr(ga), ptr(w), ptr(x0c), ptr(tf), ptr(ti))
     finally:

@@ -1,4 +1,4 @@
-// Disturbance-set estimation (tmpc_west.hip): what tmpc_api.cpp and the host execution model of tests/wavesim see of it.
+// Disturbance-set estimation (tmpc_west.hip): what tmpc_offline.cpp and the host execution model of tests/wavesim see of it.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -160,7 +160,7 @@ def test_fused_closed_loop_source_under_sanitizers(binaries, cartpole, oracle_li
 
 def test_extended_closed_loop_source_under_sanitizers(binaries, oracle_lib):
     """closed_loop_step_kernel -- the extended controller's form: per time step one launch per problem (base / packet-received), each QP
-    followed by its trajectory's state machines, the arrival flags in two alternating buffers (csrc/tmpc_api.cpp: mc_run_impl; the harness
+    followed by its trajectory's state machines, the arrival flags in two alternating buffers (csrc/tmpc_loops.cpp: mc_run_impl; the harness
     steps the two launches the same way) -- on the host execution model under ASan + UBSan, warm-started: equal to the numpy state
     machines (RobustEstimator, ConsistentActuator with x_nom_0 adoption) driven by the ORACLE's solves of
     results_linear_system_with_extendedMPC.py:247-378."""

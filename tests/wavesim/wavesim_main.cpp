@@ -69,7 +69,7 @@ void read_layout(const char *path, Layout &L) {
 }
 }  // namespace
 
-// The arrays of tmpc::McState as the host side of tmpc_mc_run lays them out (tmpc_api.cpp: mc_run_impl), every one a heap block of its
+// The arrays of tmpc::McState as the host side of tmpc_mc_run lays them out (tmpc_loops.cpp: mc_run_impl), every one a heap block of its
 // exact size; what the kernel must initialise itself stays poisoned for MemorySanitizer.
 int run_loop(int argc, char **argv) {
     need(argc == 5 || argc == 6, "usage: wavesim --loop <layout> [<layout of the packet-received problem>] <loop file> <out>");
@@ -119,7 +119,7 @@ int run_loop(int argc, char **argv) {
         const hipError_t e = tmpc::launch_solve_mc(lay.d, lay.ks, B, u.get(), xo.get(), ss.get(), sst.get(), it.get(), hd[7] ? ws.data() : nullptr, &mf, &wc, 1, nullptr);
         need(e == hipSuccess, "launch failed (shape not compiled into this build?)");
     } else {
-        // the extended controller (tmpc_api.cpp: mc_run_impl): per time step one closed_loop_step_kernel launch per problem; the arrival
+        // the extended controller (tmpc_loops.cpp: mc_run_impl): per time step one closed_loop_step_kernel launch per problem; the arrival
         // flags a step writes select the problem of the NEXT step, so the selector read and the flags written alternate between two buffers
         std::vector<uint8_t> gam2(b, 1);
         uint8_t *gam_buf[2] = {gam.data(), gam2.data()};
