@@ -135,6 +135,28 @@ __device__ __forceinline__ void wave_sums_to_lds(const double (&acc)[CNT], doubl
     wv::swap_reduce_to_lds<CNT, SH::RR>(acc, red, out, lane);
 }
 
+// entries [OFF, OFF + CNT) of a longer array of accumulators
+template <class SH, int OFF, int CNT, int TOT>
+__device__ __forceinline__ void wave_sums_part(const double (&acc)[TOT], double *red, double *out, int lane) {
+    static_assert(OFF + CNT <= TOT, "part of the array");
+    double part[CNT];
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) part[i] = acc[OFF + i];
+    wave_sums_to_lds<SH, CNT>(part, red, out, lane);
+}
+// the same round for totals of two LDS arrays: entries below SPLIT go to out0, the others to out1
+template <class SH, int CNT, int SPLIT>
+__device__ __forceinline__ void wave_sums_to_lds2(const double (&acc)[CNT], double *red, double *out0, double *out1, int lane) {
+    wv::swap_reduce_to_lds_at<CNT, SH::RR>(acc, red, [out0, out1](int e) { return e < SPLIT ? out0 + e : out1 + (e - SPLIT); }, lane);
+}
+
+// Sweep B sums the dense products (2 NV) and the factored ones (2 KC + 2, the affine step's two statistics included) in ONE round of the
+// reduction in every shape that has both -- one fence and one read-back instead of two -- but one: with twelve variables at two waves per
+// SIMD, (12,1,0,5,4,0), the 36 live accumulators take the kernel to 254 ... 256 registers with 2 ... 4 of them spilled into a private
+// segment of 12 ... 20 bytes (241 registers and none with two rounds); that shape keeps the two rounds.
+template <class SH, int WPB>
+constexpr bool sweep_b_one_round() { return SH::FD > 0 && SH::KC > 0 && !(WPB == 8 && SH::NV == 12); }
+
 // packed lower triangle, column-major: (i,j), i >= j, at col_off(j) + i - j
 template <int NV>
 __host__ __device__ constexpr int col_off(int j) { return j * NV - j * (j - 1) / 2; }
@@ -246,9 +268,11 @@ __device__ __forceinline__ double fact_dot(const double *Hct, const double *c, i
     return t;
 }
 
-// ---- sweep A, dense functionals: 1/s and the weights of both sides, the gap, |r_p|_inf; then
+// ---- sweep A, dense functionals: 1/s and the weights of both sides, the gap; then
 //          [ G'DG      ]     [ (D.G)' ]
-//          [ (G't)'    ]  =  [  t'    ]  G          with D = sum of the sides' lambda / s, t = sum of +-(lambda / s) r_p
+//          [ (G't)'    ]  =  [  t'    ]  G          with D = sum of the sides' lambda / s, t = sum of +-(lambda / s) r_p0
+// (r_p0: the primal residual as it was written at the start of the phase.  The carried residual is kappa r_p0 with a
+// wave-uniform kappa, see solve_body; G't is linear in it, so kappa goes in once where the NV entries of G't are used.)
 // on the FP64 matrix cores (v_mfma_f64_16x16x4_f64): the sum over the functionals happens inside the instruction -- no
 // per-lane accumulators (NV (NV + 1) / 2 of them in a vector-ALU formulation) and no cross-lane reduction.  A operand
 // (16 x 4 per k-step): lane l holds column k = l / 16 of row i = l % 16, i.e. D_f g_f[16 I + i] of functional f = 4 ks + k
@@ -258,7 +282,7 @@ __device__ __forceinline__ double fact_dot(const double *Hct, const double *c, i
 typedef double v4d __attribute__((ext_vector_type(4)));
 template <class SH>
 __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const double (&s)[SH::RS], const double (&lam)[SH::RS],
-                                              const double *rpw, double (&rs)[SH::RS], double &gap_l, double &rpn_l,
+                                              const double *rpw, double (&rs)[SH::RS], double &gap_l,
                                               double *dtw, double *mt, double *gdr, int lane) {
     constexpr int NV = SH::NV, NB = SH::NB, LDG = SH::LDG, IT = NV / 16, CT = NV % 16;
     static_for<SH::FD>([&](auto kd_) {
@@ -273,7 +297,6 @@ __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const d
             const double d = lam[i] * rsi;
             const double rpi = rpw[i * WAVE + lane];
             gap_l = fma(s[i], lam[i], gap_l);
-            rpn_l = vmax_abs(rpn_l, rpi);
             D += d;
             t = sd ? fma(-d, rpi, t) : fma(d, rpi, t);
         }
@@ -349,7 +372,7 @@ __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const d
 // The FACTORED functionals: KC-wide left factor, so W = Hc' D Hc has only KT entries; one pass.
 template <class SH>
 __device__ __forceinline__ void sweep_a_factored(const double *Hct, const double (&s)[SH::RS], const double (&lam)[SH::RS],
-                                                 const double *rpw, double (&rs)[SH::RS], double &gap_l, double &rpn_l, double obj_l,
+                                                 const double *rpw, double (&rs)[SH::RS], double &gap_l, double obj_l,
                                                  double *red, double *csums, int lane) {
     constexpr int KC = SH::KC, KT = SH::KT, NCCP = SH::NCCP;
     double acc[KT + KC + 2];   // initialised by the first slot's products; the last two entries carry the wave's complementarity gap and objective
@@ -369,7 +392,6 @@ __device__ __forceinline__ void sweep_a_factored(const double *Hct, const double
             const double d = lam[i] * rsi;
             const double rpi = rpw[i * WAVE + lane];
             gap_l = fma(s[i], lam[i], gap_l);
-            rpn_l = vmax_abs(rpn_l, rpi);
             D += d;
             t = sd ? fma(-d, rpi, t) : fma(d, rpi, t);
         }
@@ -686,7 +708,11 @@ __device__ __forceinline__ void solve_body(
             } else {
                 // -------------------------------------------------------- interior point
                 double s[RS], lam[RS], rs[RS];
-                double *rpw = hw;       // carried primal residual, [side][lane], in the region of h
+                // The carried primal residual is kappa * r_p0: r_p0 [side][lane] is written once, below (in the region of h), and
+                // the Newton step gives r_p <- (1 - alpha) r_p exactly (ds = -r_p - G dz), so only the wave-uniform kappa moves
+                // from one iteration to the next.  |r_p|_inf = kappa * rpn0, the wave's largest |r_p0|, taken where r_p0 is written.
+                double *rpw = hw;
+                double kappa = 1.0, rpn0 = 0.0;
                 int it0 = 0;
                 double mu_hand = 0.0;       // mu of the iterate that is handed over
                 if (resume_it >= 0) {
@@ -719,7 +745,9 @@ __device__ __forceinline__ void solve_body(
                         }
                         s[i] = vl ? sv : 1.0;
                         lam[i] = vl ? lv : 0.0;
-                        rpw[i * WAVE + lane] = vl ? sv - raw : 0.0;
+                        const double rp0 = vl ? sv - raw : 0.0;
+                        rpw[i * WAVE + lane] = rp0;
+                        rpn0 = vmax_abs(rpn0, rp0);
                         rs[i] = 1.0;
                     }
                     wave_lds_fence();
@@ -752,11 +780,14 @@ __device__ __forceinline__ void solve_body(
                         const double raw = s[i];
                         s[i] = vl ? fmax(raw, fl) : 1.0;
                         lam[i] = vl ? lam0 : 0.0;
-                        rpw[i * WAVE + lane] = vl ? s[i] - raw : 0.0;   // r_p = G z + s - h with h - G z = raw; carried from here on:
-                        rs[i] = 1.0;                                    // the Newton step gives r_p <- (1 - alpha) r_p exactly (ds = -r_p - G dz)
+                        const double rp0 = vl ? s[i] - raw : 0.0;       // r_p = G z + s - h with h - G z = raw
+                        rpw[i * WAVE + lane] = rp0;
+                        rpn0 = vmax_abs(rpn0, rp0);
+                        rs[i] = 1.0;
                     }
                     wave_lds_fence();
                 }
+                rpn0 = readlane_d(wave_max(rpn0), 0);       // (wave-uniform, like kappa: scalar registers, none of the lanes')
                 for (int it = it0; it < qp.max_iter; ++it) {
                     it_done = it;
                     STAMP(9);
@@ -773,12 +804,12 @@ __device__ __forceinline__ void solve_body(
                         cgv[lane] = cgi;
                         obj_l = zv[lane] * (0.5 * (cgi - qi) + qi);
                     }
-                    // ---- sweep A: 1/s, weights, gap, |r_p|, G'DG (dense functionals by column blocks, factored ones as W), G'(d.r_p)
-                    double gap_l = 0.0, rpn_l = 0.0;
-                    if constexpr (FD > 0) sweep_a_dense<SH>(Gt, qp.nks, s, lam, rpw, rs, gap_l, rpn_l, dtw, Mf, sums, lane);
+                    // ---- sweep A: 1/s, weights, gap, G'DG (dense functionals by column blocks, factored ones as W), G'(d.r_p0)
+                    double gap_l = 0.0;
+                    if constexpr (FD > 0) sweep_a_dense<SH>(Gt, qp.nks, s, lam, rpw, rs, gap_l, dtw, Mf, sums, lane);
                     if constexpr (KC > 0) {
                         TMPC_REFRESH();
-                        sweep_a_factored<SH>(Hct, s, lam, rpw, rs, gap_l, rpn_l, obj_l, red, csums, lane);
+                        sweep_a_factored<SH>(Hct, s, lam, rpw, rs, gap_l, obj_l, red, csums, lane);
                         // fold the factored block into the dense totals: P = W Psi now, Psi' P when the rows of M are formed
                         for (int idx = lane; idx < KC * NV; idx += WAVE) {
                             const int a = idx / NV, j = idx - a * NV;
@@ -800,11 +831,11 @@ __device__ __forceinline__ void solve_body(
                         if (lane < NV) sums[lane] = v1;
                         wave_lds_fence();
                     }
-                    // |r_p| and max lambda are only ever compared with thresholds: a ballot each instead of a reduction
+                    // max lambda is only ever compared with a threshold: a ballot instead of a reduction
                     double lmax_l = 0.0;
 #pragma unroll
                     for (int i = 0; i < RS; ++i) lmax_l = vmax(lmax_l, lam[i]);
-                    const bool rp_small = !__any(rpn_l > try_tol * hn);
+                    const bool rp_small = !(kappa * rpn0 > try_tol * hn);
                     const bool lam_big = __any(lmax_l > 1e10);
                     double gap, obj;
                     if constexpr (KC > 0) {       // (summed with the factored block's totals: sweep_a_factored)
@@ -932,7 +963,7 @@ __device__ __forceinline__ void solve_body(
                                 mt[li] += shift;
                             }
                             wave_lds_fence();
-                            rhs_i = (lane < NV) ? -cgv[li] - sums[li] : 0.0;
+                            rhs_i = (lane < NV) ? fma(-kappa, sums[li], -cgv[li]) : 0.0;      // (sums: G'(d.r_p0))
                             if constexpr (NV > wv::DPP_ROW && wv::DPP_ROW > 0) {
                                 // two matrix rows per lane, DPP forms throughout (tmpc_wave.hpp: rows32_*); the right-hand side goes
                                 // through LDS, the factor stays in place of the matrix
@@ -980,8 +1011,7 @@ __device__ __forceinline__ void solve_body(
                         // -ds/s = -q and -dl/lam = 1 + q with q = dsa / s (dla = -lam (1 + q)): no reciprocal of lambda.
                         // Padding sides (s = 1, lam = 0, r_p = 0, g = 0) give q = 0: ratio 1, never binding.
                         auto side_stats = [&](int i, bool neg, double gdz, double &c1, double &c2) {
-                            const double rpi = rpw[i * WAVE + lane];
-                            const double dsa = neg ? gdz - rpi : -rpi - gdz;
+                            const double dsa = fma(-kappa, rpw[i * WAVE + lane], neg ? gdz : -gdz);
                             const double q = dsa * rs[i];
                             const double u = 1.0 + q;
                             const double dla = -lam[i] * u;
@@ -993,8 +1023,13 @@ __device__ __forceinline__ void solve_body(
                             c1 = neg ? fma(-w, rs[i], c1) : fma(w, rs[i], c1);      // (padding functionals have g = 0: their 1/s = 1
                             c2 = neg ? c2 - rs[i] : c2 + rs[i];                      //  never reaches G'(1/s); paired slots hold complete pairs only)
                         };
+                        // accumulators: the dense products, then the factored ones and the two sums of the affine step's statistics -- one
+                        // array, reduced in one round (sweep_b_one_round) or as its two parts
+                        constexpr bool ONE = sweep_b_one_round<SH, WPB>();
+                        constexpr int NBD = FD > 0 ? 2 * NV : 0, NBC = KC > 0 ? 2 * KC + 2 : 0;
+                        double acc[NBD + NBC];
+                        double *const accb = acc, *const accc = acc + NBD;
                         if constexpr (FD > 0) {
-                            double accb[2 * NV];
                             static_for<FD>([&](auto kd_) {
                                 constexpr int kd = decltype(kd_)::value;
                                 const int r = min(lane + kd * WAVE, grows);
@@ -1015,10 +1050,9 @@ __device__ __forceinline__ void solve_body(
                                 }
                                 if constexpr (WPB == 8 || TMPC_FENCE_ALL) row_fence();
                             });
-                            wave_sums_to_lds<SH, 2 * NV>(accb, red, sums, lane);   // overwrites G'(d.rp), G'lam (consumed)
+                            if constexpr (!ONE) wave_sums_part<SH, 0, NBD>(acc, red, sums, lane);   // overwrites G'(d.rp0), G'lam (consumed)
                         }
                         if constexpr (KC > 0) {
-                            double accc[2 * KC + 2];       // (+ the two sums of the affine step's statistics: see sweep_a_factored)
                             static_for<FC>([&](auto kc_) {
                                 constexpr int kc = decltype(kc_)::value;
                                 const int r = lane + kc * WAVE;
@@ -1035,9 +1069,10 @@ __device__ __forceinline__ void solve_body(
                                     accc[KC + a] = kc == 0 ? hc[a] * c2 : fma(hc[a], c2, accc[KC + a]);
                                 }
                             });
-                            accc[2 * KC] = sb1;
+                            accc[2 * KC] = sb1;         // (the two sums of the affine step's statistics: see sweep_a_factored)
                             accc[2 * KC + 1] = sb2;
-                            wave_sums_to_lds<SH, 2 * KC + 2>(accc, red, csums + KT, lane);
+                            if constexpr (ONE) wave_sums_to_lds2<SH, NBD + NBC, NBD>(acc, red, sums, csums + KT, lane);
+                            else wave_sums_part<SH, NBD, NBC>(acc, red, csums + KT, lane);
                             sb1 = readlane_d(csums[KT + 2 * KC], 0);
                             sb2 = readlane_d(csums[KT + 2 * KC + 1], 0);
                         } else {
@@ -1085,8 +1120,7 @@ __device__ __forceinline__ void solve_body(
                     {
                         // the reciprocal of lambda only ranks the step-length ratios (rcp1: one Newton step)
                         auto side_step = [&](int i, bool neg, double gdz) {
-                            const double rpi = rpw[i * WAVE + lane];
-                            const double dsk = neg ? gdz - rpi : -rpi - gdz;
+                            const double dsk = fma(-kappa, rpw[i * WAVE + lane], neg ? gdz : -gdz);
                             const double t1 = fma(lam[i], dsk, wv_[i] - smu);
                             const double dlk = valid(i) ? fma(-t1, rs[i], -lam[i]) : 0.0;
                             const double rl = valid(i) ? rcp1(lam[i]) : 0.0;
@@ -1110,13 +1144,12 @@ __device__ __forceinline__ void solve_body(
                     }
                     rho = wave_max(rho);
                     const double alpha = rho > tau ? tau / rho : 1.0;
-                    const double oma = 1.0 - alpha;
 #pragma unroll
                     for (int i = 0; i < RS; ++i) {
                         s[i] = fma(alpha, rs[i], s[i]);
                         lam[i] = fma(alpha, wv_[i], lam[i]);
-                        rpw[i * WAVE + lane] *= oma;
                     }
+                    kappa = readlane_d(kappa * (1.0 - alpha), 0);
                     if (lane < NV) zv[lane] += alpha * dzv[lane];
                     wave_lds_fence();
                     it_done = it + 1;

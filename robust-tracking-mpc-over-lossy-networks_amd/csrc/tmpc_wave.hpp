@@ -157,9 +157,10 @@ __device__ __forceinline__ void wave_sum2(double &a, double &b, int lane) {
 // d + (r & 1) H2 + (r >> 1) H1 as sixteen partial sums (a register without a partner pairs with zero).  Finish: the H2
 // registers go to rows of the [RR][RED_STRIDE] tile (lane l at column l + l / 16) -- H2 <= RR stores per lane where the
 // tile form needs CNT --, and lane l adds the sixteen partial sums of row (l >> 2), quarter (l & 3): a complete total, no
-// DPP step.  More than RR rows: rounds of RR.
-template <int CNT, int RR>
-__device__ __forceinline__ void swap_reduce_to_lds(const double (&acc)[CNT], double *red, double *out, int lane) {
+// DPP step.  More than RR rows: rounds of RR.  The general form takes the place of total e from `out_at(e)`, so that one
+// round can serve totals that live in different LDS arrays.
+template <int CNT, int RR, class OutAt>
+__device__ __forceinline__ void swap_reduce_to_lds_at(const double (&acc)[CNT], double *red, OutAt &&out_at, int lane) {
     constexpr int H1 = (CNT + 1) / 2, H2 = (H1 + 1) / 2;
     double r1[H1];
 #pragma unroll
@@ -187,9 +188,13 @@ __device__ __forceinline__ void swap_reduce_to_lds(const double (&acc)[CNT], dou
         for (int j = 0; j < 16; ++j) t4[j & 3] += red[kr * RED_STRIDE + qd * 17 + j];
         const double t = (t4[0] + t4[1]) + (t4[2] + t4[3]);
         const int e = (k < NR && d0 + k < H2) ? entry(d0 + k, qd) : -1;
-        if (e >= 0) out[e] = t;
+        if (e >= 0) *out_at(e) = t;
         lds_fence();
     }
+}
+template <int CNT, int RR>
+__device__ __forceinline__ void swap_reduce_to_lds(const double (&acc)[CNT], double *red, double *out, int lane) {
+    swap_reduce_to_lds_at<CNT, RR>(acc, red, [out](int e) { return out + e; }, lane);
 }
 
 // n x n symmetric positive definite solve with the rows on the lanes: lane i (< N) holds row i in registers; LDL' by
