@@ -8,9 +8,9 @@ pole length within +-spread of nominal, cart friction up to spread (montecarlo.s
   1. the disturbance box W is estimated on the device on the family (closed loops u = -K x, the nominal A, B, K: the one-step prediction error
      then contains the parametric mismatch) and printed beside the box estimated on the nominal plant and the box of the design;
   2. the controller is the design's (its tube is guaranteed for disturbances inside the design's box only);
-  3. the closed loop over the lossy network (numpy state machines and numpy plants around the device solver: the device loop
-     simulates one plant for the batch) runs on the nominal plant, on the same family and on one twice as wide: tracking error, steps outside the tube and
-     solves that were not optimal, by spread."""
+  3. the closed loop over the lossy network runs on the device -- state machines, solver and, for a family, a plant per trajectory
+     (tmpc_mc_run_plants) -- on the nominal plant, on the same family and on one twice as wide: tracking error, steps outside the tube
+     and solves that were not optimal, by spread."""
 import argparse
 import os
 import sys
@@ -54,9 +54,7 @@ def main():
     print(f"cart-pole, N = {N}: {n} trajectories per spread, {T} steps, loss rate {args.loss_rate:.2f}, no disturbance but the plant's own mismatch")
     worst = 0
     for s in (0.0, S, 2.0 * S):
-        plant = montecarlo.plant_callable("cartpole" if s == 0.0 else montecarlo.sample_cartpole(n, s, seed=7))
-        out = montecarlo.run_remote_tube_mpc(mpc.determine_packets, A, B, mpc.get_steady_state_controller_gain(), mpc.get_ancillary_controller_gain(),
-                                             N, mpc._Z, p_loss, ref, th, ga, w0, plant=plant)
+        out = mpc.run_closed_loop(p_loss, ref, th, ga, w0, plant="cartpole" if s == 0.0 else montecarlo.sample_cartpole(n, s, seed=7))
         if not np.all(np.isfinite(out["tracking_error"])):
             sys.exit("a trajectory diverged")
         print(f"   spread {s:4.2f}: tracking error {np.mean(out['tracking_error']):.5f} (worst {np.max(out['tracking_error']):.5f}), "

@@ -440,6 +440,46 @@ int tmpc_mc_set_plant(tmpc_handle *h, int kind, const double *par7, int substeps
  * stepped sessions simulate the handle's one plant (tmpc_mc_set_plant).  Added without an ABI bump: a new export.
  */
 int tmpc_mc_set_plant_models(tmpc_handle *h, int kind, int64_t B, const double *models, int substeps);
+/*
+ * A plant per trajectory in the TRACKING loop: the stepped session (tmpc_mc_open / tmpc_mc_step_device, below) driven for T steps around a
+ * family of plants that one more kernel advances (tmpc_plant.hip), with nothing returning to the host in between.  The resident kernels
+ * of tmpc_mc_run are not involved: they keep their one plant.
+ *
+ * tmpc_plant_step_device(device, kind, nx, nu, B, models, substeps, x, u, w, x_plus, stream): ONE launch, x_plus[b] = f_b(x[b], u[b]) + w[b].
+ *   kind    TMPC_PLANT_CARTPOLE (nx = 4, nu = 1): models is B x 7 rows {M, m, b, I, g, l, Th}; u held over the period, classical RK4 with
+ *           `substeps` >= 1 steps of Th_b / substeps -- the plant of tmpc_mc_set_plant with the row's numbers.
+ *           TMPC_PLANT_LINEAR (1 <= nx <= 16, 1 <= nu <= 16): models is B x nx x (nx + nu), the layout of tmpc_mc_set_plant_models;
+ *           x_plus_i = w_i + sum_k A_b[i, k] x_k + sum_j B_b[i, j] u_j, summed in this order.  substeps is ignored.
+ *   Every array is a DEVICE pointer: models, x (B*nx), u (B*nu), x_plus (B*nx), w (B*nx, or NULL: no disturbance).  stream: a hipStream_t
+ *   or NULL.  Enqueues the kernel and returns without synchronising.  x_plus must not overlap x (the lanes of one trajectory would
+ *   race): TMPC_E_INVALID, as for B < 1, another kind, a shape the kind does not take and a NULL pointer -- all found before anything
+ *   touches the device, the message through tmpc_last_error(NULL).  With tmpc_mc_step_device it makes a caller's own loop around the
+ *   library's plants.
+ *
+ * tmpc_mc_run_plants(h, B, T, extended, kind, models, substeps, p_loss, ref, th_u, ga_u, w, x0, HZ, hZ, rZ, HX, hX, rX, HU, hU, rU, err2,
+ *                    tube_viol, x_viol, u_viol, not_optimal, x_final, consistent, iters_sum, err2_phys): HOST pointers, the semantics of
+ *   tmpc_mc_run plus the session's check sets X and U (x_viol, u_viol) and the family: trajectory b runs on plant b of `models` (copied;
+ *   kind, layout and substeps as above, with the handle's nx and nu).  err2_phys (B, or NULL; cart-pole only, not written for a linear
+ *   family): the physics-rate error of tmpc_mc_get_physics_error, which works afterwards too.  Any output may be NULL.
+ *   Per step (number of problems + 2) launches on the handle's stream -- the solve(s), the state machines, the plants -- and between the
+ *   uploads and the copy-back no synchronisation and no copy.  Honoured as set on the handle: tmpc_mc_set_actuator, _set_warm_start,
+ *   _set_capture, tmpc_set_solve_timing, tmpc_set_kernel_path, the reference table, the loss channel and the device generator -- with it
+ *   th_u, ga_u and w may be NULL: the session draws the loss uniforms, the plant kernel the disturbance, exactly tmpc_mc_run's numbers.
+ *   Ignored: tmpc_mc_set_plant and tmpc_mc_set_fused (tmpc_mc_last_fused: 0).  An R-MPC trajectory that has stopped keeps its state.
+ *   Afterwards tmpc_mc_get_link_stats, _get_capture and _get_solve_ticks work as after tmpc_mc_close.
+ *   Refused before anything is launched, the handle left as it was: TMPC_E_INVALID for a regulator handle, an open session, B or T < 1,
+ *   a B that does not match a reference table or channel that is set, a cart-pole family on a handle with nx != 4 or nu != 1, a row that
+ *   is no plant (the rule of tmpc_estimate_w_models; a linear entry that is not finite) with the message naming trajectory and field or
+ *   entry, a NULL input; TMPC_E_DEVICE for a host-only handle, after these.  A device error in a step ends the loop: TMPC_E_DEVICE.
+ * Added without an ABI bump: new exports, nothing else changed.
+ */
+int tmpc_plant_step_device(int device, int kind, int32_t nx, int32_t nu, int64_t B, const double *models, int substeps, const double *x,
+                           const double *u, const double *w, double *x_plus, void *stream);
+int tmpc_mc_run_plants(tmpc_handle *h, int64_t B, int32_t T, int extended, int kind, const double *models, int substeps, const double *p_loss,
+                       const double *ref, const double *th_u, const double *ga_u, const double *w, const double *x0, const double *HZ,
+                       const double *hZ, int32_t rZ, const double *HX, const double *hX, int32_t rX, const double *HU, const double *hU,
+                       int32_t rU, double *err2, int32_t *tube_viol, int32_t *x_viol, int32_t *u_viol, int32_t *not_optimal, double *x_final,
+                       double *consistent, int32_t *iters_sum, double *err2_phys);
 
 /*
  * Stepped closed loop around a plant the CALLER owns: the per-trajectory state machines and the solve kernels of tmpc_mc_run,

@@ -273,7 +273,9 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         means are also appended to get_computational_times(), the list the scripts take their quantiles of (:305-315).
         device_rng = (seed, first_trajectory, w_bound): draw the realisations on the device instead of taking th_u, ga_u, w
         (tmpc_mc_set_device_rng; montecarlo.draw_realisations_philox is the host twin).
-        plant: None / "linear" / "cartpole" -- the plants the library simulates itself; or a callable (x, u) -> x_plus on
+        plant: None / "linear" / "cartpole" -- the plants the library simulates itself, one for the batch; a montecarlo.PlantFamily
+        (plant_family, sample_cartpole) of B plants -- a plant per trajectory, advanced on the device by a kernel of its own behind the
+        stepped loop (tmpc_mc_run_plants; `fused` does not apply, the result also has x_violations / u_violations); or a callable (x, u) -> x_plus on
         float64 CUDA tensors (B, nx), (B, nu): any other plant, stepped through open_closed_loop (one call per time step; w[:, t],
         if given, is added to x_plus; `fused` does not apply).
         ref: (T,) -- the scripts' position reference, shared by the batch: the solve gets [ref_t, 0, ..] and the tracking error is
@@ -287,6 +289,15 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         from . import _native
         if self._handle is None:
             raise RuntimeError("setup_optimization() has not been called")
+        from .montecarlo import PlantFamily
+        if isinstance(plant, PlantFamily):       # (before callable(): a family is callable, on numpy arrays -- the torch path cannot serve it)
+            _native.mc_set_actuator(self._handle, self._smart_actuator)
+            out = _native.mc_run_plants(self._handle, plant, p_loss, ref, th_u, ga_u, w, x0=x0, Z=None if self._smart_actuator else self._Z,
+                                        extended=extended, warm_start=warm_start, capture=capture, timing=timing, device_rng=device_rng,
+                                        ref_id=ref_id, T=T, channel=channel)
+            if timing:
+                self._computational_times.extend(out["solve_time_mean"].tolist())
+            return out
         if callable(plant):
             out = self._run_closed_loop_around(plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng,
                                                ref_id=ref_id, T=T, channel=channel)

@@ -149,6 +149,11 @@ def lib():
         L.tmpc_mc_set_plant.restype = C.c_int
         L.tmpc_mc_set_plant_models.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int]
         L.tmpc_mc_set_plant_models.restype = C.c_int
+        L.tmpc_plant_step_device.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.tmpc_plant_step_device.restype = C.c_int
+        L.tmpc_mc_run_plants.argtypes = ([C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+                                         + ([C.c_void_p] * 2 + [C.c_int32]) * 3 + [C.c_void_p] * 9)
+        L.tmpc_mc_run_plants.restype = C.c_int
         L.tmpc_lp_batch.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmpc_lp_batch.restype = C.c_int
@@ -747,6 +752,101 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
         if lib().tmpc_mc_get_physics_error(h.ptr, B, ptr(out["err2_physics"])) != 0:
             raise RuntimeError(h.error())
         out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * physics_substeps)
+    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing)
+
+
+def _family_models(who: str, plant, nx: int, nu: int, B=None):
+    """(kind id, models, substeps) of a montecarlo.PlantFamily as the C ABI takes it; the family must fit (nx, nu) and hold B plants."""
+    kind = getattr(plant, "kind", None)
+    if kind not in ("linear", "cartpole"):
+        raise ValueError(f"{who}: plant is a montecarlo.PlantFamily (plant_family, sample_cartpole)")
+    m = np.ascontiguousarray(np.asarray(plant.models, dtype=np.float64))
+    want = (7,) if kind == "cartpole" else (nx, nx + nu)
+    if m.ndim != len(want) + 1 or m.shape[1:] != want or (kind == "cartpole" and (nx, nu) != (4, 1)):
+        raise ValueError(f"{who}: {kind} models are (B,) + {want} for nx = {nx}, nu = {nu}; got {m.shape}")
+    if B is not None and m.shape[0] != B:
+        raise ValueError(f"{who}: the plant family holds {m.shape[0]} plants, the loop {B} trajectories")
+    return PLANT_KIND[kind], m, int(plant.substeps)
+
+
+def plant_step(plant, x, u, w=None, x_plus=None, stream=None):
+    """include/tmpc.h: tmpc_plant_step_device -- one launch that advances the plants of a montecarlo.PlantFamily by one period:
+    x_plus[b] = f_b(x[b], u[b]) + w[b].  x (B, nx), u (B, nu), w (B, nx) or None, x_plus (B, nx) or None (a new tensor): contiguous
+    float64 CUDA tensors; plant.models may be such a tensor too (a family kept on the device), else it is uploaded.  Enqueued on
+    `stream` (an integer hipStream_t; None: torch's current stream) without synchronising; returns x_plus, which must not overlap x."""
+    import torch
+    who = "plant_step"
+    for name, a in (("x", x), ("u", u), ("w", w), ("x_plus", x_plus)):
+        if a is not None and not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float64 and a.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous float64 CUDA tensor")
+    if x.dim() != 2 or u.dim() != 2 or u.shape[0] != x.shape[0]:
+        raise ValueError(f"{who}: x is (B, nx) and u is (B, nu)")
+    B, nx = x.shape
+    nu = u.shape[1]
+    models = plant.models
+    if isinstance(models, torch.Tensor):
+        kind, sub = PLANT_KIND[plant.kind], int(plant.substeps)
+        if not (models.is_cuda and models.dtype == torch.float64 and models.is_contiguous()) or models.shape[0] != B:
+            raise ValueError(f"{who}: models on the device are a contiguous float64 CUDA tensor of B = {B} plants")
+    else:
+        kind, m, sub = _family_models(who, plant, nx, nu, B)
+        models = torch.as_tensor(m, device=x.device)
+    if x_plus is None:
+        x_plus = torch.empty_like(x)
+    for name, a in (("w", w), ("x_plus", x_plus)):
+        if a is not None and tuple(a.shape) != (B, nx):
+            raise ValueError(f"{who}: {name} must be (B, nx) = {(B, nx)}")
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+    rc = lib().tmpc_plant_step_device(x.device.index, kind, nx, nu, B, models.data_ptr(), sub, x.data_ptr(), u.data_ptr(),
+                                      None if w is None else w.data_ptr(), x_plus.data_ptr(), int(stream) if stream else None)
+    if rc != 0:
+        raise RuntimeError(f"tmpc_plant_step_device failed ({rc}): {lib().tmpc_last_error(None).decode()}")
+    return x_plus
+
+
+def mc_run_plants(h: Handle, plant, p_loss, ref, th_u=None, ga_u=None, w=None, x0=None, Z=None, X=None, U=None, extended: bool = False,
+                  warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, T=None, channel=None) -> dict:
+    """include/tmpc.h: tmpc_mc_run_plants -- the closed loop of mc_run with a plant per trajectory: `plant` is a montecarlo.PlantFamily of
+    B plants, cart-poles or linear models; the stepped session and the plant kernel alternate on the device for T steps.  The arguments
+    are mc_run's (`fused` does not apply) plus the check sets X, U of mc_open; the result has mc_run's keys -- with
+    tracking_error_physics for a cart-pole family -- plus x_violations and u_violations."""
+    _set_loop_options(h, timing, warm_start, capture)
+    c, ptr = _contiguous, _ptr
+    p_loss, ch_par, n_traj = loop_batch("mc_run_plants", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
+    if T is None and device_rng is None and th_u is not None:
+        T = np.shape(th_u)[1]
+    ref, T_ref = _loop_reference(h, "mc_run_plants", ref, n_traj, T, ref_id)
+    _set_device_rng(h, device_rng)
+    if device_rng is not None:
+        th_u = ga_u = w = None
+        B, T = n_traj, T_ref
+    else:
+        th_u, ga_u, w = c(th_u), c(ga_u), c(w)
+        B, T = th_u.shape
+        if ch_par is not None and ch_par[0].shape[0] != B:
+            raise ValueError(f"mc_run_plants: the channel holds {ch_par[0].shape[0]} trajectories, the draws {B}")
+        if ga_u.shape != (B, T) or w.shape != (B, T, h.nx) or (p_loss is not None and p_loss.shape != (B,)) or (ref is not None and ref.shape != (T,)) or T_ref < T:
+            raise ValueError("mc_run_plants: inconsistent shapes")
+    kind, models, substeps = _family_models("mc_run_plants", plant, h.nx, h.nu, B)
+    x0c = None if x0 is None else c(x0).reshape(B, h.nx)
+    sets = [v for P, dim in ((Z, h.nx), (X, h.nx), (U, h.nu)) for v in _check_set(P, dim, "mc_run_plants")]
+    out = dict(err2=np.empty(B), tube_violations=np.empty(B, np.int32), x_violations=np.empty(B, np.int32), u_violations=np.empty(B, np.int32),
+               not_optimal=np.empty(B, np.int32), x_final=np.empty((B, h.nx)), consistent=np.empty(B), iters_sum=np.empty(B, np.int32))
+    cart = kind == PLANT_KIND["cartpole"]
+    if cart:
+        out["err2_physics"] = np.empty(B)
+    mc_set_channel(h, ch_par)            # (as in mc_run: last)
+    rc = lib().tmpc_mc_run_plants(h.ptr, B, T, int(bool(extended)), kind, models.ctypes.data, substeps, ptr(p_loss), ptr(ref), ptr(th_u), ptr(ga_u),
+                                  ptr(w), ptr(x0c), *[ptr(a) if isinstance(a, np.ndarray) or a is None else a for a in sets],
+                                  *[ptr(out[k]) for k in ("err2", "tube_violations", "x_violations", "u_violations", "not_optimal", "x_final",
+                                                          "consistent", "iters_sum")], ptr(out.get("err2_physics")))
+    if rc != 0:
+        msg = h.error()
+        mc_set_channel(h, None)          # a refused loop leaves no channel behind
+        raise RuntimeError(f"tmpc_mc_run_plants failed ({rc}): {msg}")
+    if cart:
+        out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * substeps)
     return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing)
 
 

@@ -355,11 +355,11 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     return out
 
 
-def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, x0=None, channel=None):
+def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, x0=None, channel=None, plant=None):
     """Closed loop of the non-robust comparator (R-MPC) over the lossy network: TrackingMPC + Estimator + plain
     SmartActuator (results_linear_system.py:198-205, 262-287).  A trajectory whose solve is infeasible stops there
     (track_feasible = False, :268-270) and reports a NaN tracking error (:297), and its link statistics stop at that step.  Same
-    conventions as run_remote_tube_mpc otherwise (`channel` included)."""
+    conventions as run_remote_tube_mpc otherwise (`channel` and `plant` included)."""
     from .Estimator import BatchedEstimator
     from .SmartActuator import BatchedConsistentActuator
     A = np.asarray(A, dtype=np.float64)
@@ -404,7 +404,7 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
             err2 += np.where(dead, 0.0, (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1))
         else:
             err2 += np.where(dead, 0.0, (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1))
-        x = np.where(dead[:, None], x, x @ A.T + u @ Bm.T + w[:, t])
+        x = np.where(dead[:, None], x, (x @ A.T + u @ Bm.T if plant is None else plant(x, u)) + w[:, t])
         gamma = gamma_all[:, t]
         est.update(pkt, gamma)
     te = np.sqrt(err2) / T
@@ -417,8 +417,8 @@ PLANT_STREAM = 0x706c616e74                          # second counter word of th
 
 
 class PlantFamily:
-    """A plant per trajectory for the host loops, the regulators' device loop (include/tmpc.h: tmpc_mc_set_plant_models) and the W
-    estimate (tmpc_estimate_w_models) -- what plant_family returns.
+    """A plant per trajectory for the host loops, the device loops (include/tmpc.h: tmpc_mc_run_plants for the tracking controllers,
+    tmpc_mc_set_plant_models for the regulators) and the W estimate (tmpc_estimate_w_models) -- what plant_family returns.
     kind "linear": A (B, nx, nx), B (B, nx, nu), the plant of trajectory b is x+ = A_b x + B_b u; kind "cartpole": par (B, 7) rows
     {M, m, b, I, g, l, Th}, the RK4 cart-pole of workloads.cartpole_trace with `substeps` steps per period.  The controller's model
     stays the nominal one.  models: the C layout; family(x, u) -> x+ for x (B, nx), u (B, nu) (the host loops add w); family[slice]:
@@ -541,8 +541,8 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     (tmpc_mc_set_device_rng) and by draw_realisations_philox, the same numbers, in the host loops.
     ref: a scalar or (T,) position reference; or (T, nx) one full-state schedule for every trajectory; or (K, T, nx) schedules
     with ref_id (n_total,) naming each trajectory's -- sliced with the shard, so the sweep stays shard-invariant.
-    plant: None / "cartpole"; in the host loop (on_device=False) also a PlantFamily of n_total plants (plant_family, sample_cartpole),
-    sliced with the shard.
+    plant: None / "cartpole"; or a PlantFamily of n_total plants (plant_family, sample_cartpole), sliced with the shard -- on the device
+    the loop of tmpc_mc_run_plants.
     mean_burst: None -- independent losses; else every loss rate p as the stationary rate of burst_channel(p, mean_burst), on the
     same uniforms (a rate above 1 - 1 / mean_burst keeps independent losses, whose bursts last 1 / (1 - p) on average; every rate must be below 1).  link_stats: four more columns at the end of the table: lost_up, lost_down, max_gap, overrun."""
     import torch
@@ -576,15 +576,13 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
         if len(plant) != n_total:
             raise ValueError(f"mc_sweep: the plant family holds {len(plant)} plants, the sweep {n_total} trajectories")
         plant = plant[lo:hi]
-        if on_device:
-            raise ValueError("mc_sweep: the device loop simulates one plant for the batch; a plant family goes with on_device=False")
     if on_device:        # state machines on the GPU as well (tmpc_mc_run); otherwise the host loop around determine_packets
         out = mpc.run_closed_loop(p_loss[pi[lo:hi]], ref, th, ga, w, extended=extended, plant=plant, warm_start=warm_start,
                                   timing=timing, device_rng=(seed, lo, model["w_bound"]) if device_rng else None, ref_id=ids,
                                   T=T if ids is not None else None, channel=channel)
     elif getattr(mpc, "_smart_actuator", False):       # TrackingMPC: the comparator's loop (results_linear_system.py:262-287)
         out = run_remote_tracking_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(), mpc._N,
-                                      p_loss[pi[lo:hi]], ref, th, ga, w, channel=channel)
+                                      p_loss[pi[lo:hi]], ref, th, ga, w, channel=channel, plant=None if plant is None else plant_callable(plant))
         out["tube_violations"] = np.zeros(hi - lo, dtype=np.int32)
     else:
         out = run_remote_tube_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(),

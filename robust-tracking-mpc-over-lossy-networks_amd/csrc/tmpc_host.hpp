@@ -251,4 +251,6 @@ int enqueue(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const 
 void release_session(tmpc_handle *h);
 int begin_loop(tmpc_handle *h, int64_t B);
 bool session_bars(tmpc_handle *h, const char *who);
+// (tmpc_offline.cpp) cart-pole rows {M, m, b, I, g, l, Th} of n trajectories: empty, or the message naming trajectory and field
+std::string cartpole_rows_error(const char *who, const double *rows, int64_t n);
 }  // namespace tmpc_host

@@ -1,5 +1,6 @@
 // The closed loops of libtmpc_hip.so (include/tmpc.h: tmpc_mc_*, tmpc_reg_run): settings, the resident loops and the stepped one.
 #include "tmpc_host.hpp"
+#include "tmpc_plant.hpp"
 
 using namespace tmpc_host;
 
@@ -379,6 +380,75 @@ int host_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t, c
     if (rc != TMPC_OK) s.failed = true;
     return finish_loop(h, rc);
 }
+
+// Opens the stepped loop `q` describes (checked by check_tracking_loop): carves the session's arrays -- and what `more` lists behind them,
+// pieces of a caller that drives the session itself -- and waits for the uploads, which read the caller's arrays.
+template <class More>
+int open_session(tmpc_handle *h, const TrackingLoop &q, More more) {
+    if (const int rc = begin_loop(h, q.B)) return rc;
+    const size_t nx = h->nx, nu = h->nu, b = static_cast<size_t>(q.B);
+    McSession &s = h->ses;
+    auto open = [&]() -> int {
+        s.m = tmpc::McModel{}; s.st = tmpc::McState{}; s.ext = tmpc::McExternal{};
+        s.warm = h->loop.warm != 0;
+        tracking_pieces(h, q, s.m, s.st, s.ws, &s);
+        more(h->arena, s);
+        HIP_TRY(h, h->arena.carve(h->stream));
+        link_block_carved(s.st, b);
+        HIP_TRY(h, tmpc::launch_mc_pre(s.m, s.st, q.B, q.full_ref ? 0.0 : q.ref[0], h->stream));
+        HIP_TRY(h, hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
+        // (the pinned block is a convenience: without it tmpc_mc_step copies from / to the caller's memory)
+        if (hipHostMalloc(reinterpret_cast<void **>(&s.pin), b * (nx + nu + (q.full_ref ? nx : 0)) * 8, hipHostMallocDefault) != hipSuccess) {
+            s.pin = nullptr;
+            (void)hipGetLastError();
+        }
+        HIP_TRY(h, sync_lanes(h));       // the uploads read the caller's arrays, which are theirs again from here on
+        return TMPC_OK;
+    };
+    if (const int rc = finish_loop(h, open())) {
+        release_session(h);
+        return rc;
+    }
+    if (q.full_ref) s.ref.assign(static_cast<size_t>(q.T), 0.0);       // (not read on the device in full-reference mode)
+    else s.ref.assign(q.ref, q.ref + q.T);
+    s.full_ref = q.full_ref;
+    s.B = q.B; s.T = q.T; s.t = 0; s.extended = q.extended ? 1 : 0;
+    s.open = true;
+    return TMPC_OK;
+}
+
+// The statistics of the open session over the steps taken, copied out behind what is enqueued; the session stays open.
+int fetch_session_results(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_viol, int32_t *u_viol, int32_t *not_optimal, double *consistent,
+                          int32_t *iters_sum) {
+    McSession &s = h->ses;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return fetch_tracking_results(h, s.st, s.B, s.T, err2, consistent, {{tube_viol, s.st.tube_viol}, {x_viol, s.ext.x_viol}, {u_viol, s.ext.u_viol},
+                                                                        {not_optimal, s.st.not_optimal}, {iters_sum, s.st.iters_sum}});
+}
+
+// Linear plants [B][nx][nx + nu], rows [A_b[i, :] | B_b[i, :]] (tmpc_mc_set_plant_models, tmpc_mc_run_plants): empty if every entry is finite,
+// otherwise the message, which names trajectory and entry.
+std::string linear_rows_error(const char *who, const double *models, int64_t B, int64_t nx, int64_t nu) {
+    const int64_t wid = nx + nu;
+    for (int64_t b = 0; b < B; ++b)
+        for (int64_t i = 0; i < nx; ++i)
+            for (int64_t j = 0; j < wid; ++j)
+                if (!std::isfinite(models[(b * nx + i) * wid + j]))
+                    return std::string(who) + ": " + (j < nx ? "A" : "B") + "[" + std::to_string(i) + ", " + std::to_string(j < nx ? j : j - nx) +
+                           "] of trajectory " + std::to_string(b) + " is not finite";
+    return std::string();
+}
+
+// A family of plants as tmpc_mc_run_plants and tmpc_plant_step_device take it: kind and shape against (nx, nu); empty, or the message
+std::string plant_family_error(const char *who, int kind, int nx, int nu, int substeps) {
+    const std::string w = std::string(who) + ": ";
+    if (kind != TMPC_PLANT_CARTPOLE && kind != TMPC_PLANT_LINEAR) return w + "kind is TMPC_PLANT_CARTPOLE or TMPC_PLANT_LINEAR";
+    if (kind == TMPC_PLANT_CARTPOLE && (nx != 4 || nu != 1)) return w + "the cart-pole plant needs nx = 4, nu = 1";
+    if (kind == TMPC_PLANT_CARTPOLE && substeps < 1) return w + "the cart-pole plant needs substeps >= 1";
+    if (nx < 1 || nx > 16 || nu < 1 || nu > 16) return w + "need 1 <= nx <= 16 and 1 <= nu <= 16";
+    return std::string();
+}
 }  // namespace
 
 extern "C" {
@@ -415,16 +485,8 @@ int tmpc_mc_set_plant_models(tmpc_handle *h, int kind, int64_t B, const double *
     if (kind == TMPC_PLANT_CARTPOLE) { h->err = std::string(who) + ": a regulator handle runs linear plants only"; return TMPC_E_INVALID; }
     if (kind != TMPC_PLANT_LINEAR) { h->err = std::string(who) + ": kind is TMPC_PLANT_LINEAR"; return TMPC_E_INVALID; }
     if (!models) { h->err = std::string(who) + ": models is NULL"; return TMPC_E_INVALID; }
-    const int64_t nx = h->nx, wid = h->nx + h->nu;
-    for (int64_t b = 0; b < B; ++b)
-        for (int64_t i = 0; i < nx; ++i)
-            for (int64_t j = 0; j < wid; ++j)
-                if (!std::isfinite(models[(b * nx + i) * wid + j])) {
-                    h->err = std::string(who) + ": " + (j < nx ? "A" : "B") + "[" + std::to_string(i) + ", " + std::to_string(j < nx ? j : j - nx) +
-                             "] of trajectory " + std::to_string(b) + " is not finite";
-                    return TMPC_E_INVALID;
-                }
-    h->loop.pm.assign(models, models + static_cast<size_t>(B) * static_cast<size_t>(nx * wid));
+    if (const std::string bad = linear_rows_error(who, models, B, h->nx, h->nu); !bad.empty()) { h->err = bad; return TMPC_E_INVALID; }
+    h->loop.pm.assign(models, models + static_cast<size_t>(B) * static_cast<size_t>(h->nx * (h->nx + h->nu)));
     h->loop.pm_B = B;
     return TMPC_OK;
 }
@@ -678,36 +740,7 @@ int tmpc_mc_open(tmpc_handle *h, int64_t B, int32_t T, int extended, const doubl
     if (!h) return TMPC_E_INVALID;
     TrackingLoop q{"tmpc_mc_open", true, B, T, extended, p_loss, ref, th_u, ga_u, nullptr, x0, {HZ, hZ, rZ}, {HX, hX, rX}, {HU, hU, rU}};
     if (const int rc = check_tracking_loop(h, q)) return rc;
-    if (const int rc = begin_loop(h, B)) return rc;
-    const size_t nx = h->nx, nu = h->nu, b = static_cast<size_t>(B);
-    McSession &s = h->ses;
-    auto open = [&]() -> int {
-        s.m = tmpc::McModel{}; s.st = tmpc::McState{}; s.ext = tmpc::McExternal{};
-        s.warm = h->loop.warm != 0;
-        tracking_pieces(h, q, s.m, s.st, s.ws, &s);
-        HIP_TRY(h, h->arena.carve(h->stream));
-        link_block_carved(s.st, b);
-        HIP_TRY(h, tmpc::launch_mc_pre(s.m, s.st, B, q.full_ref ? 0.0 : ref[0], h->stream));
-        HIP_TRY(h, hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
-        // (the pinned block is a convenience: without it tmpc_mc_step copies from / to the caller's memory)
-        if (hipHostMalloc(reinterpret_cast<void **>(&s.pin), b * (nx + nu + (q.full_ref ? nx : 0)) * 8, hipHostMallocDefault) != hipSuccess) {
-            s.pin = nullptr;
-            (void)hipGetLastError();
-        }
-        HIP_TRY(h, sync_lanes(h));       // the uploads read the caller's arrays, which are theirs again from here on
-        return TMPC_OK;
-    };
-    if (const int rc = finish_loop(h, open())) {
-        release_session(h);
-        return rc;
-    }
-    if (q.full_ref) s.ref.assign(static_cast<size_t>(T), 0.0);       // (not read on the device in full-reference mode)
-    else s.ref.assign(ref, ref + T);
-    s.full_ref = q.full_ref;
-    s.B = B; s.T = T; s.t = 0; s.extended = extended ? 1 : 0;
-    s.open = true;
-    return TMPC_OK;
+    return open_session(h, q, [](Arena &, McSession &) {});
 }
 
 int tmpc_mc_step_device(tmpc_handle *h, const double *x_t, double *u_t, void *caller_stream) {
@@ -737,13 +770,90 @@ int tmpc_mc_close(tmpc_handle *h, double *err2, int32_t *tube_viol, int32_t *x_v
     if (!h) return TMPC_E_INVALID;
     McSession &s = h->ses;
     if (!s.open) { h->err = "tmpc_mc_close: no stepped closed loop is open on this handle (tmpc_mc_open)"; return TMPC_E_INVALID; }
-    auto close = [&]() -> int {
-        HIP_TRY(h, hipSetDevice(h->device));
-        return fetch_tracking_results(h, s.st, s.B, s.T, err2, consistent, {{tube_viol, s.st.tube_viol}, {x_viol, s.ext.x_viol}, {u_viol, s.ext.u_viol},
-                                                                            {not_optimal, s.st.not_optimal}, {iters_sum, s.st.iters_sum}});
-    };
-    const int rc = finish_loop(h, close());
+    const int rc = finish_loop(h, fetch_session_results(h, err2, tube_viol, x_viol, u_viol, not_optimal, consistent, iters_sum));
     if (steps_done) *steps_done = s.t;
+    release_session(h);
+    return rc;
+}
+
+int tmpc_plant_step_device(int device, int kind, int32_t nx, int32_t nu, int64_t B, const double *models, int substeps, const double *x, const double *u,
+                           const double *w, double *x_plus, void *stream) {
+    const char *who = "tmpc_plant_step_device";
+    if (B < 1) { g_create_error = std::string(who) + ": B < 1"; return TMPC_E_INVALID; }
+    if (const std::string bad = plant_family_error(who, kind, nx, nu, substeps); !bad.empty()) { g_create_error = bad; return TMPC_E_INVALID; }
+    if (!models || !x || !u || !x_plus) { g_create_error = std::string(who) + ": NULL argument"; return TMPC_E_INVALID; }
+    // one lane per trajectory (or per state row) reads the whole x of its trajectory and writes x_plus: in place the lanes would race
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(x), pa = reinterpret_cast<uintptr_t>(x_plus), bytes = static_cast<uintptr_t>(B) * nx * sizeof(double);
+    if (xa < pa + bytes && pa < xa + bytes) { g_create_error = std::string(who) + ": x_plus overlaps x (the step is not in place)"; return TMPC_E_INVALID; }
+    tmpc::PlantStep a{};
+    a.kind = kind; a.nx = nx; a.nu = nu; a.substeps = substeps; a.B = B;
+    a.models = models; a.x = x; a.u = u; a.x_plus = x_plus; a.w = w; a.w_stride = nx;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = tmpc::launch_plant_step(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) { g_create_error = std::string(who) + ": " + hipGetErrorString(e); return TMPC_E_DEVICE; }
+    return TMPC_OK;
+}
+
+int tmpc_mc_run_plants(tmpc_handle *h, int64_t B, int32_t T, int extended, int kind, const double *models, int substeps, const double *p_loss,
+                       const double *ref, const double *th_u, const double *ga_u, const double *w, const double *x0, const double *HZ, const double *hZ,
+                       int32_t rZ, const double *HX, const double *hX, int32_t rX, const double *HU, const double *hU, int32_t rU, double *err2,
+                       int32_t *tube_viol, int32_t *x_viol, int32_t *u_viol, int32_t *not_optimal, double *x_final, double *consistent, int32_t *iters_sum,
+                       double *err2_phys) {
+    const char *who = "tmpc_mc_run_plants";
+    if (!h) return TMPC_E_INVALID;
+    auto refuse = [&](const std::string &msg) { h->err = std::string(who) + ": " + msg; return TMPC_E_INVALID; };
+    // the arguments of its own, then those of a session (check_tracking_loop, which also finds a host-only handle); nothing is launched
+    // and no setting changes before the last of them
+    if (h->ses.open) return refuse("a stepped closed loop is open on this handle (tmpc_mc_close first)");
+    if (h->regulator) return refuse("a regulator handle has no tracking loop (tmpc_reg_run with tmpc_mc_set_plant_models)");
+    if (B < 1 || T < 1) return refuse("need B >= 1 and T >= 1");
+    if (const std::string bad = plant_family_error(who, kind, h->nx, h->nu, substeps); !bad.empty()) { h->err = bad; return TMPC_E_INVALID; }
+    if (!models) return refuse("models is NULL");
+    const bool rng = h->loop.rng_on != 0, cart = kind == TMPC_PLANT_CARTPOLE;
+    if (!rng && !w) return refuse("NULL argument");
+    if (h->loop.ref_K > 0)
+        if (const int rc = reference_table_fits(h, who, B, T)) return rc;
+    const int64_t nx = h->nx, wid = h->nx + h->nu;
+    if (const std::string bad = cart ? cartpole_rows_error(who, models, B) : linear_rows_error(who, models, B, h->nx, h->nu); !bad.empty()) {
+        h->err = bad;
+        return TMPC_E_INVALID;
+    }
+    TrackingLoop q{who, true, B, T, extended, p_loss, ref, th_u, ga_u, nullptr, x0, {HZ, hZ, rZ}, {HX, hX, rX}, {HU, hU, rU}};
+    if (const int rc = check_tracking_loop(h, q)) return rc;
+    // the session's arena, and behind it the family, the two plant states (the linear step is not in place), the disturbance or its box,
+    // and the physics-rate error, which lives in the session's state: a trajectory that stops gets its NaN from the state machines too
+    const size_t b_ = static_cast<size_t>(B), t_ = static_cast<size_t>(T), nx_ = static_cast<size_t>(nx);
+    double *d_models = nullptr, *d_x[2] = {nullptr, nullptr}, *d_w = nullptr, *d_wb = nullptr;
+    const int rc_open = open_session(h, q, [&](Arena &a, McSession &s) {
+        a.piece(&d_models, (cart ? b_ * 7 : b_ * nx_ * static_cast<size_t>(wid)) * 8, models);
+        a.piece(&d_x[0], b_ * nx_ * 8, x0, 0);
+        a.piece(&d_x[1], b_ * nx_ * 8);
+        if (rng) a.piece(&d_wb, nx_ * 8, h->loop.w_bound.data());
+        else a.piece(&d_w, b_ * t_ * nx_ * 8, w);
+        if (cart) a.piece(&s.st.err2_phys, b_ * 8, nullptr, 0);
+    });
+    if (rc_open != TMPC_OK) return rc_open;
+    McSession &s = h->ses;
+    auto run = [&]() -> int {
+        tmpc::PlantStep p{};
+        p.kind = kind; p.nx = h->nx; p.nu = h->nu; p.substeps = substeps; p.B = B;
+        p.models = d_models; p.u = s.ext.u_t; p.w_stride = static_cast<int64_t>(t_ * nx_);
+        p.rng_on = rng ? 1 : 0; p.rng_seed = h->loop.rng_seed; p.rng_first = h->loop.rng_first; p.w_bound = d_wb;
+        p.hold = s.st.dead;
+        p.err2_phys = s.st.err2_phys; p.ref_tab = s.st.ref_tab; p.ref_id = s.st.ref_id; p.ref_T = s.st.ref_T;
+        // per step: the solve launch(es) and the state machines around x_t (session_step), then the plants -- all on the handle's stream
+        for (int t = 0; t < T; ++t) {
+            if (const int rc = session_step(h, who, d_x[t & 1], s.ext.u_t, nullptr)) return rc;
+            p.x = d_x[t & 1]; p.x_plus = d_x[(t + 1) & 1];
+            p.w = d_w ? d_w + static_cast<size_t>(t) * nx_ : nullptr;
+            p.t = t; p.ref_t = s.ref[static_cast<size_t>(t)];
+            HIP_TRY(h, tmpc::launch_plant_step(p, h->stream));
+        }
+        if (x_final) HIP_TRY(h, hipMemcpyAsync(x_final, d_x[T & 1], b_ * nx_ * 8, hipMemcpyDeviceToHost, h->stream));
+        if (err2_phys && cart) HIP_TRY(h, hipMemcpyAsync(err2_phys, s.st.err2_phys, b_ * 8, hipMemcpyDeviceToHost, h->stream));
+        return fetch_session_results(h, err2, tube_viol, x_viol, u_viol, not_optimal, consistent, iters_sum);
+    };
+    const int rc = finish_loop(h, run());
     release_session(h);
     return rc;
 }

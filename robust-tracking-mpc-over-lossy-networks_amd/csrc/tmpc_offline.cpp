@@ -24,7 +24,10 @@ struct WestEvents {
     ~WestEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
-// The cart-pole rows {M, m, b, I, g, l, Th} of n trajectories (tmpc_estimate_w_models): empty if every row
+}  // namespace
+
+namespace tmpc_host {
+// The cart-pole rows {M, m, b, I, g, l, Th} of n trajectories (tmpc_estimate_w_models, tmpc_mc_run_plants): empty if every row
 // describes a plant, otherwise the message, which names trajectory and field.
 std::string cartpole_rows_error(const char *who, const double *rows, int64_t n) {
     static const char *const field[7] = {"M", "m", "b", "I", "g", "l", "Th"};
@@ -39,8 +42,7 @@ std::string cartpole_rows_error(const char *who, const double *rows, int64_t n) 
         }
     return std::string();
 }
-
-}  // namespace
+}  // namespace tmpc_host
 
 extern "C" {
 

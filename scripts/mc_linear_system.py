@@ -35,7 +35,7 @@ def main():
                          "channel of montecarlo.burst_channel; a rate above 1 - 1 / L keeps independent losses); adds the "
                          "link statistics to the table")
     ap.add_argument("--plant-spread", type=float, default=None, metavar="S",
-                    help="with --host-loop: a cart-pole per trajectory instead of the controller's model: M, m, l within "
+                    help="a cart-pole per trajectory instead of the controller's model (tmpc_mc_run_plants; numpy plants with --host-loop): M, m, l within "
                          "+-S of nominal, cart friction up to S (montecarlo.sample_cartpole, keyed by the global trajectory index); "
                          "the controller keeps the nominal model")
     ap.add_argument("--host-loop", action="store_true", help="state machines in numpy on the host instead of on the device")
@@ -68,8 +68,6 @@ def main():
     if args.plant_spread is not None:
         if args.reference_streams:
             raise SystemExit("--plant-spread goes with the per-trajectory streams, not with --reference-streams")
-        if not args.host_loop:
-            raise SystemExit("--plant-spread needs --host-loop: the device loop simulates one plant for the whole batch")
         plant = montecarlo.sample_cartpole(len(p_loss) * args.n_mc, args.plant_spread, seed=20240301)
     for label, extended, rmpc in controllers:
         # controller set up in the package: offline sets through the batched LP kernel on this rank's device (0.2 s)
