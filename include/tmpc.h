@@ -601,6 +601,74 @@ int tmpc_mc_set_channel(tmpc_handle *h, int64_t B, const double *p_gb, const dou
 int tmpc_mc_get_channel(tmpc_handle *h, int64_t B, double *thr);
 int tmpc_mc_get_link_stats(tmpc_handle *h, int64_t B, int32_t *lost_up, int32_t *lost_down, int32_t *max_gap, int32_t *overrun);
 /*
+ * Time-resolved records of the tracking loops, and their statistics over the ensemble per time step.
+ *
+ * The record.  With tmpc_mc_set_series(h, 1) a loop keeps two values per step t and trajectory b, TIME-major ([T][B]: row t holds the
+ * B trajectories of step t):
+ *   e[t][b]     the step's tracking-error term -- exactly the value the step adds to err2[b], |x_t - [ref_t, 0, ..]|^2 or, under a reference
+ *               table, |x_t - r_t|^2 -- so that the sum of e[0..T)[b] in this order is err2[b], bit for bit
+ *   word[t][b]  bit 0  TMPC_SER_ALIVE        the trajectory took step t
+ *               bit 1  TMPC_SER_LOST_UP      the channel dropped the controller -> plant packet (as lost_up of tmpc_mc_get_link_stats: a
+ *                                            packet withheld after a failed solve is not counted)
+ *               bit 2  TMPC_SER_LOST_DOWN    the same for the plant -> controller packet
+ *               bit 3  TMPC_SER_ADOPTED      Theta_t = 1: the actuator adopted the packet of this step
+ *               bit 4  TMPC_SER_TUBE         x_t - x_nom_t is outside Z (what tube_viol counts; 0 when rZ = 0)
+ *               bit 5  TMPC_SER_NOT_OPTIMAL  status != 0 (what not_optimal counts)
+ *               bit 6  TMPC_SER_OVERRUN      t - s_t >= N: the terminal law (what overrun counts)
+ *               bit 7  zero
+ *               bits 8-19   iterations of the step's solve, saturating at TMPC_SER_SATURATE = 4095
+ *               bits 20-31  age t - s_t of the sequence played, saturating at 4095
+ * A trajectory that does not take the step writes nothing, and the buffers start as zeros: a stopped R-MPC trajectory has word 0 ("not
+ * alive") and e = 0 from the step of its infeasible solve on, and so has every trajectory in the steps a session did not take.
+ *
+ * tmpc_mc_set_series: on != 0 switches the record on for the following tmpc_mc_run, tmpc_mc_run_plants and tmpc_mc_open (a session honours
+ * it as set at open); works on a host-only handle; TMPC_E_INVALID on a regulator handle and while a session is open.  tmpc_mc_replay and
+ * tmpc_reg_run ignore it.  A recording tmpc_mc_run runs its state machines in the per-step kernels (tmpc_mc_last_fused: 0, whatever
+ * tmpc_mc_set_fused says): the fused kernels carry no recording code.  With the record off every loop is what it was.
+ *
+ * tmpc_mc_get_series: the record of the last such loop, or of the session tmpc_mc_close just ended, as e[T][B] and word[T][B] (either may
+ * be NULL).  TMPC_E_INVALID: no such loop, the record was off, or another B or T.
+ *
+ * tmpc_mc_series_stats: the statistics below of the record where it lies on the device; tmpc_series_stats: the same reduction of HOST
+ * arrays e[T][B], word[T][B] on `device`, without a handle (its errors through tmpc_last_error(NULL)).
+ *   group     [B] group of every trajectory in [0, G), or -1: in no group; NULL: everybody is in group 0.  Groups need not be contiguous.
+ *   q         [n_q] quantiles in [0, 1], 0 <= n_q <= 16
+ * Column (t, g) is the entries [t][b] of the members b of group g.  An entry takes part iff its ALIVE bit is set; an alive entry whose e
+ * is NaN (the loops produce none) is left out of the e statistics and counted in n_nan.  Outputs, [T][G] each, any may be NULL:
+ *   n_alive, n_nan                                          int32  entries that take part; those of them with e = NaN
+ *   lost_up, lost_down, adopted, tube, not_optimal, overrun int32  entries with the bit set
+ *   age_max, iters_max   int32    age_sum, iters_sum   int64      of the saturated fields of the word
+ *   e_sum     double  sum of the n = n_alive - n_nan values, in a fixed order that is not the host's: equal bytes from call to call, the
+ *                     last bits differ from a sequential sum (0 for n = 0)
+ *   e_max     double  their maximum (NaN for n = 0)
+ *   e_q       [T][G][n_q] double: quantile q is the element of rank floor(q (n - 1)) -- one multiplication and one floor in double -- of
+ *                     the sorted values: exact order statistics, no interpolation (NaN for n = 0).  Of -0.0 and 0.0 either may come back.
+ *   kernel_ms the reduction's device time (HIP events), or NULL
+ * TMPC_E_INVALID, before anything touches the device: B, T or G < 1, a NULL input, group[b] >= G or < -1, n_q outside [0, 16], q NULL with
+ * n_q > 0, a q[i] outside [0, 1] or NaN; tmpc_mc_series_stats also where tmpc_mc_get_series would refuse.  Added without an ABI bump.
+ */
+#define TMPC_SER_ALIVE       0x01u
+#define TMPC_SER_LOST_UP     0x02u
+#define TMPC_SER_LOST_DOWN   0x04u
+#define TMPC_SER_ADOPTED     0x08u
+#define TMPC_SER_TUBE        0x10u
+#define TMPC_SER_NOT_OPTIMAL 0x20u
+#define TMPC_SER_OVERRUN     0x40u
+#define TMPC_SER_ITERS_SHIFT 8
+#define TMPC_SER_AGE_SHIFT   20
+#define TMPC_SER_SATURATE    4095
+#define TMPC_SER_MAX_Q       16
+int tmpc_mc_set_series(tmpc_handle *h, int on);
+int tmpc_mc_get_series(tmpc_handle *h, int64_t B, int32_t T, double *e, uint32_t *word);
+int tmpc_mc_series_stats(tmpc_handle *h, int64_t B, int32_t T, int32_t G, const int32_t *group, int32_t n_q, const double *q,
+                         int32_t *n_alive, int32_t *n_nan, int32_t *lost_up, int32_t *lost_down, int32_t *adopted, int32_t *tube,
+                         int32_t *not_optimal, int32_t *overrun, int32_t *age_max, int64_t *age_sum, int32_t *iters_max, int64_t *iters_sum,
+                         double *e_sum, double *e_max, double *e_q, float *kernel_ms);
+int tmpc_series_stats(int device, int64_t B, int32_t T, const double *e, const uint32_t *word, int32_t G, const int32_t *group, int32_t n_q,
+                      const double *q, int32_t *n_alive, int32_t *n_nan, int32_t *lost_up, int32_t *lost_down, int32_t *adopted, int32_t *tube,
+                      int32_t *not_optimal, int32_t *overrun, int32_t *age_max, int64_t *age_sum, int32_t *iters_max, int64_t *iters_sum,
+                      double *e_sum, double *e_max, double *e_q, float *kernel_ms);
+/*
  * With a nonlinear plant tmpc_mc_run also sums |x - ref|^2 over the T * substeps physics steps (the state at the start of
  * every physics step, i.e. x_traj[:, 0:-1] of results_nonlinear_system.py:361, whose tracking error is taken at 500 Hz);
  * copied out per trajectory by tmpc_mc_get_physics_error (NaN for an R-MPC trajectory that stopped).

@@ -139,6 +139,14 @@ def lib():
         L.tmpc_mc_get_channel.restype = C.c_int
         L.tmpc_mc_get_link_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
         L.tmpc_mc_get_link_stats.restype = C.c_int
+        L.tmpc_mc_set_series.argtypes = [C.c_void_p, C.c_int]
+        L.tmpc_mc_set_series.restype = C.c_int
+        L.tmpc_mc_get_series.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.tmpc_mc_get_series.restype = C.c_int
+        L.tmpc_mc_series_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_void_p] * 16
+        L.tmpc_mc_series_stats.restype = C.c_int
+        L.tmpc_series_stats.argtypes = [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_void_p] * 16
+        L.tmpc_series_stats.restype = C.c_int
         L.tmpc_mc_close.argtypes = [C.c_void_p] * 9
         L.tmpc_mc_close.restype = C.c_int
         L.tmpc_mc_replay.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 8
@@ -279,6 +287,7 @@ class Handle:
     def __init__(self, ptr, nx, nu, N, nvariants, regulator: bool = False):
         self.ptr, self.nx, self.nu, self.N, self.nvariants = ptr, nx, nu, N, nvariants
         self.regulator = regulator
+        self.series_shape = None     # (B, T) of the per-step record the last loop left (series=True), for mc_series_stats
 
     def error(self) -> str:
         return lib().tmpc_last_error(self.ptr).decode()
@@ -626,6 +635,68 @@ def mc_link_stats(h: Handle, B: int) -> dict:
     return out
 
 
+def mc_get_series(h: Handle, B: int, T: int) -> dict:
+    """include/tmpc.h: tmpc_mc_get_series -- the per-step record of the last loop run with series=True: e (T, B) float64, word (T, B)
+    uint32, and the word's fields decoded (montecarlo.unpack_series_word): alive, lost_up, lost_down, adopted, tube, not_optimal,
+    overrun (bool), iters, age (int32)."""
+    from .montecarlo import decode_series
+    e, word = np.empty((int(T), int(B))), np.empty((int(T), int(B)), np.uint32)
+    if lib().tmpc_mc_get_series(h.ptr, int(B), int(T), e.ctypes.data, word.ctypes.data) != 0:
+        raise RuntimeError(h.error())
+    return decode_series(e, word)
+
+
+def _series_tables(who: str, B: int, T: int, group, q, G):
+    """The arguments of a reduction as the C ABI takes them and its output tables -> (group or None, G, q, tables, pointers in ABI order)."""
+    from .montecarlo import SERIES_INT_TABLES
+    if group is not None:
+        group = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
+        if group.size != B:
+            raise ValueError(f"{who}: group holds {group.size} entries, the record {B} trajectories")
+    G = (int(group.max()) + 1 if group is not None and group.size else 1) if G is None else int(G)
+    q = np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1))
+    shape = (max(int(T), 0), max(G, 0))
+    out = {k: np.empty(shape, np.int64 if k.endswith("_sum") else np.int32) for k in SERIES_INT_TABLES}
+    out["e_sum"], out["e_max"], out["e_q"] = np.empty(shape), np.empty(shape), np.empty(shape + (q.size,))
+    return group, G, q, out, [v.ctypes.data for v in out.values()]
+
+
+def mc_series_stats(h: Handle, group=None, q=(0.5, 0.95), G=None, B=None, T=None) -> dict:
+    """include/tmpc.h: tmpc_mc_series_stats -- the ensemble statistics of the record the last series=True loop left on the device, per
+    time step and group: (T, G) tables n_alive, n_nan, lost_up, lost_down, adopted, tube, not_optimal, overrun, age_max, age_sum,
+    iters_max, iters_sum, e_sum, e_max and e_q (T, G, len(q)); kernel_ms, the reduction's device time.  group (B,): ids in [0, G) or -1
+    (None: everybody in one group); q: quantiles -- the element of rank floor(q (n - 1)) of the sorted values, no interpolation
+    (montecarlo.series_stats is the numpy twin).  B, T: the record's shape (default: that of the handle's last loop)."""
+    if B is None or T is None:
+        if getattr(h, "series_shape", None) is None:
+            raise RuntimeError("mc_series_stats: the handle's last loop kept no per-step record (series=True)")
+        B, T = h.series_shape
+    B, T = int(B), int(T)
+    group, G, q, out, ptrs = _series_tables("mc_series_stats", B, T, group, q, G)
+    ms = C.c_float(0.0)
+    rc = lib().tmpc_mc_series_stats(h.ptr, B, T, G, _ptr(group), q.size, q.ctypes.data, *ptrs, C.addressof(ms))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_mc_series_stats failed ({rc}): {h.error()}")
+    out["kernel_ms"] = float(ms.value)
+    return out
+
+
+def series_stats(e, word, group=None, q=(0.5, 0.95), G=None, device: int = 0) -> dict:
+    """include/tmpc.h: tmpc_series_stats -- the reduction of mc_series_stats on host arrays e, word (T, B), without a handle."""
+    e = np.ascontiguousarray(np.asarray(e, dtype=np.float64))
+    word = np.ascontiguousarray(np.asarray(word, dtype=np.uint32))
+    if e.ndim != 2 or word.shape != e.shape:
+        raise ValueError("series_stats: e and word are (T, B)")
+    T, B = e.shape
+    group, G, q, out, ptrs = _series_tables("series_stats", B, T, group, q, G)
+    ms = C.c_float(0.0)
+    rc = lib().tmpc_series_stats(int(device), B, T, e.ctypes.data, word.ctypes.data, G, _ptr(group), q.size, q.ctypes.data, *ptrs, C.addressof(ms))
+    if rc != 0:
+        raise RuntimeError(f"tmpc_series_stats failed ({rc}): {lib().tmpc_last_error(None).decode()}")
+    out["kernel_ms"] = float(ms.value)
+    return out
+
+
 MC_FUSED = {"off": 0, "on": 1, "auto": 2, False: 0, True: 1, None: 2}      # include/tmpc.h: TMPC_MC_FUSED_*
 
 
@@ -637,12 +708,12 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
-def _set_loop_options(h: Handle, timing, warm_start, capture, fused="keep"):
-    """The per-call settings of a tracking loop (mc_run, mc_open): tmpc_set_solve_timing, tmpc_mc_set_warm_start, tmpc_mc_set_capture
-    and -- mc_run; a session has one launch form and leaves the setting alone -- tmpc_mc_set_fused.  THE place where a new per-call
-    loop option is set."""
+def _set_loop_options(h: Handle, timing, warm_start, capture, fused="keep", series: bool = False):
+    """The per-call settings of a tracking loop (mc_run, mc_open): tmpc_set_solve_timing, tmpc_mc_set_warm_start, tmpc_mc_set_capture,
+    tmpc_mc_set_series and -- mc_run; a session has one launch form and leaves the setting alone -- tmpc_mc_set_fused.  THE place where
+    a new per-call loop option is set."""
     calls = [(lib().tmpc_set_solve_timing, int(bool(timing))), (lib().tmpc_mc_set_warm_start, int(bool(warm_start))),
-             (lib().tmpc_mc_set_capture, -1 if capture is None else int(capture))]
+             (lib().tmpc_mc_set_capture, -1 if capture is None else int(capture)), (lib().tmpc_mc_set_series, int(bool(series)))]
     if fused != "keep":
         calls.insert(1, (lib().tmpc_mc_set_fused, MC_FUSED[fused]))
     for call, arg in calls:
@@ -672,7 +743,7 @@ def _check_set(P, dim: int, who: str):
     return HA, hb, HA.shape[0]
 
 
-def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode: int, capture, timing) -> dict:
+def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode: int, capture, timing, series: bool = False) -> dict:
     """Completes the result of a tracking loop (mc_run, mc_close) over the `steps` steps taken of T: the recorded trajectory, the
     solve times, the link statistics and the derived statistics.  THE place where a new loop output is fetched."""
     n = steps
@@ -688,6 +759,9 @@ def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode
         out["solve_time_mean"], out["solve_time_max"] = tsum * (TICK_SECONDS / max(n, 1)), tmax * TICK_SECONDS
     out["link_stats"] = mc_link_stats(h, B)
     out.update(out["link_stats"])
+    h.series_shape = (B, T) if series else None
+    if series:
+        out["series"] = mc_get_series(h, B, T)       # (T, B) arrays; rows of steps a session did not take are zero
     out["loop_mode"] = loop_mode      # 1: one launch per sweep; 2: one launch per problem and step; 0: solve launches + a state-machine launch per step
     out["fused"] = loop_mode == 1
     out["tracking_error"] = np.sqrt(out["err2"]) / max(n, 1)
@@ -698,7 +772,7 @@ def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode
 
 def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: bool = False, warm_start: bool = False,
            capture=None, timing: bool = False, physics_substeps: int = 0, device_rng=None, fused=None, ref_id=None, T=None,
-           channel=None) -> dict:
+           channel=None, series: bool = False) -> dict:
     """include/tmpc.h: tmpc_mc_run -- the closed loop over the lossy network, resident on the device.
     warm_start: tmpc_mc_set_warm_start for this call; capture: index of a trajectory to record (tmpc_mc_set_capture) ->
     x_traj (T, nx), x_nom_traj (T, nx), u_traj (T, nu) in the result; timing: per trajectory the mean and the maximum
@@ -716,8 +790,11 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     all states.  A (T,) call clears an earlier table.  T: the steps (default: the draws' or the reference's).
     channel: the Gilbert-Elliott loss channel of this call (mc_set_channel; None: independent losses with probability p_loss, and
     an earlier channel is cleared); p_loss is then not read and may be None.  The result carries the link statistics lost_up,
-    lost_down, max_gap, overrun (also as the dict link_stats) with either loss model."""
-    _set_loop_options(h, timing, warm_start, capture, fused)
+    lost_down, max_gap, overrun (also as the dict link_stats) with either loss model.
+    series: keep the per-step record (tmpc_mc_set_series) -> result["series"], a dict of (T, B) arrays: e, the error term of every
+    step, word, and the word's fields alive, lost_up, lost_down, adopted, tube, not_optimal, overrun, iters, age; mc_series_stats then
+    reduces it on the device.  Such a loop runs per time step (loop_mode 0, whatever `fused` says)."""
+    _set_loop_options(h, timing, warm_start, capture, fused, series)
     c, ptr = _contiguous, _ptr
     p_loss, ch_par, n_traj = loop_batch("mc_run", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if T is None and device_rng is None and th_u is not None:
@@ -752,7 +829,7 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
         if lib().tmpc_mc_get_physics_error(h.ptr, B, ptr(out["err2_physics"])) != 0:
             raise RuntimeError(h.error())
         out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * physics_substeps)
-    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing)
+    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing, series)
 
 
 def _family_models(who: str, plant, nx: int, nu: int, B=None):
@@ -806,12 +883,13 @@ def plant_step(plant, x, u, w=None, x_plus=None, stream=None):
 
 
 def mc_run_plants(h: Handle, plant, p_loss, ref, th_u=None, ga_u=None, w=None, x0=None, Z=None, X=None, U=None, extended: bool = False,
-                  warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, T=None, channel=None) -> dict:
+                  warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, T=None, channel=None,
+                  series: bool = False) -> dict:
     """include/tmpc.h: tmpc_mc_run_plants -- the closed loop of mc_run with a plant per trajectory: `plant` is a montecarlo.PlantFamily of
     B plants, cart-poles or linear models; the stepped session and the plant kernel alternate on the device for T steps.  The arguments
     are mc_run's (`fused` does not apply) plus the check sets X, U of mc_open; the result has mc_run's keys -- with
-    tracking_error_physics for a cart-pole family -- plus x_violations and u_violations."""
-    _set_loop_options(h, timing, warm_start, capture)
+    tracking_error_physics for a cart-pole family -- plus x_violations and u_violations.  series: as in mc_run."""
+    _set_loop_options(h, timing, warm_start, capture, series=series)
     c, ptr = _contiguous, _ptr
     p_loss, ch_par, n_traj = loop_batch("mc_run_plants", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if T is None and device_rng is None and th_u is not None:
@@ -847,17 +925,19 @@ def mc_run_plants(h: Handle, plant, p_loss, ref, th_u=None, ga_u=None, w=None, x
         raise RuntimeError(f"tmpc_mc_run_plants failed ({rc}): {msg}")
     if cart:
         out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * substeps)
-    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing)
+    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing, series)
 
 
 def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=None, X=None, U=None, extended: bool = False,
-            warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, channel=None) -> dict:
+            warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, channel=None,
+            series: bool = False) -> dict:
     """include/tmpc.h: tmpc_mc_open -- opens the stepped closed loop around a plant of the caller's.  p_loss (B,), ref (T,)
     or a full-state form (mc_run; (nx,) together with T: a constant full state -- the table of a session steered by ref_next),
     th_u / ga_u (B, T) loss uniforms (None with device_rng = (seed, first_trajectory[, ignored]): Philox block 0, the draws of
     mc_run), x0 (B, nx) or None; T: steps the session may take (default: len(ref)); Z / X / U: tube cross-section and the check
     sets for x_t / u_t (polytopes or None).  No disturbance is drawn: w is the plant's.  channel: the Gilbert-Elliott loss channel of
-    the session (mc_run; p_loss may then be None).  Returns what mc_close needs."""
+    the session (mc_run; p_loss may then be None).  series: the session keeps its per-step record (mc_run), which mc_close returns.
+    Returns what mc_close needs."""
     c, ptr = _contiguous, _ptr
     p_loss, ch_par, B = loop_batch("mc_open", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if p_loss is not None:
@@ -867,7 +947,7 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
     T = T_ref if T is None else int(T)
     if (ref.shape[0] if ref is not None else T_ref) < T:
         raise ValueError("mc_open: ref must cover the T steps of the session")
-    _set_loop_options(h, timing, warm_start, capture)
+    _set_loop_options(h, timing, warm_start, capture, series=series)
     _set_device_rng(h, device_rng, draws_w=False)
     if device_rng is not None:
         th_u = ga_u = None
@@ -886,7 +966,7 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
         msg = h.error()
         mc_set_channel(h, None)          # (no session was opened: the setter is free)
         raise RuntimeError(f"tmpc_mc_open failed ({rc}): {msg}")
-    return dict(B=B, T=T, capture=capture, timing=bool(timing), full_ref=ref is None)
+    return dict(B=B, T=T, capture=capture, timing=bool(timing), full_ref=ref is None, series=bool(series))
 
 
 def mc_step(h: Handle, info: dict, x, u=None, stream=None, ref_next=None):
@@ -940,7 +1020,7 @@ def mc_close(h: Handle, info: dict) -> dict:
     if rc != 0:
         raise RuntimeError(f"tmpc_mc_close failed ({rc}): {h.error()}")
     out["steps"] = int(steps.value)
-    return _tracking_result(h, out, B, T, out["steps"], 0, info.get("capture"), info.get("timing"))
+    return _tracking_result(h, out, B, T, out["steps"], 0, info.get("capture"), info.get("timing"), info.get("series", False))
 
 
 def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=None, capture=None, plant=None) -> dict:

@@ -224,6 +224,101 @@ def _loss_flags(channel, p_loss, th_u, ga_u):
     return theta, gamma
 
 
+# --------------------------------------------------------------------------- the per-step record and its ensemble statistics
+# the word of the per-step record (include/tmpc.h: TMPC_SER_*)
+SER_ALIVE, SER_LOST_UP, SER_LOST_DOWN, SER_ADOPTED, SER_TUBE, SER_NOT_OPTIMAL, SER_OVERRUN = (1 << i for i in range(7))
+SER_ITERS_SHIFT, SER_AGE_SHIFT, SER_SATURATE, SER_MAX_Q = 8, 20, 4095, 16
+SERIES_FLAGS = ("alive", "lost_up", "lost_down", "adopted", "tube", "not_optimal", "overrun")
+SERIES_INT_TABLES = ("n_alive", "n_nan", "lost_up", "lost_down", "adopted", "tube", "not_optimal", "overrun", "age_max", "age_sum",
+                     "iters_max", "iters_sum")
+
+
+def pack_series_word(alive, lost_up=0, lost_down=0, adopted=0, tube=0, not_optimal=0, overrun=0, iters=0, age=0):
+    """The packed word of the loops' per-step record (include/tmpc.h: TMPC_SER_*): bits 0-6 the flags in the order of the arguments,
+    bits 8-19 the iterations and bits 20-31 the age t - s_t, each saturating at 4095.  Arrays broadcast; returns uint32."""
+    flags = (alive, lost_up, lost_down, adopted, tube, not_optimal, overrun)
+    word = np.zeros(np.broadcast(*flags, iters, age).shape, dtype=np.uint32)
+    for i, f in enumerate(flags):
+        word |= (np.asarray(f).astype(bool).astype(np.uint32) << np.uint32(i))
+    word |= np.clip(np.asarray(iters, dtype=np.int64), 0, SER_SATURATE).astype(np.uint32) << np.uint32(SER_ITERS_SHIFT)
+    word |= np.clip(np.asarray(age, dtype=np.int64), 0, SER_SATURATE).astype(np.uint32) << np.uint32(SER_AGE_SHIFT)
+    return word
+
+
+def unpack_series_word(word) -> dict:
+    """The fields of pack_series_word: the seven flags as bool arrays, iters and age as int32."""
+    word = np.asarray(word, dtype=np.uint32)
+    out = {name: ((word >> np.uint32(i)) & np.uint32(1)).astype(bool) for i, name in enumerate(SERIES_FLAGS)}
+    out["iters"] = ((word >> np.uint32(SER_ITERS_SHIFT)) & np.uint32(SER_SATURATE)).astype(np.int32)
+    out["age"] = (word >> np.uint32(SER_AGE_SHIFT)).astype(np.int32)
+    return out
+
+
+def decode_series(e, word) -> dict:
+    """The `series` entry of a loop's result: e and word (T, B) and the word's fields (unpack_series_word)."""
+    return dict(e=e, word=word, **unpack_series_word(word))
+
+
+def series_stats(e, word, group=None, q=(0.5, 0.95), G=None) -> dict:
+    """The numpy twin of the device reduction (include/tmpc.h: tmpc_series_stats): per time step t and group g the statistics of the
+    entries [t][b] of the members b of g.  e, word (T, B); group (B,) ids in [0, G) or -1 (in no group), None: one group of everybody;
+    G: the number of groups (default: the largest id + 1).  An entry takes part iff its ALIVE bit is set; an alive entry with e = NaN
+    is counted in n_nan and left out of the e statistics.  Quantile q of the n values that take part is the element of rank
+    floor(q (n - 1)) of np.sort (NaN for n = 0, like e_max; e_sum is then 0).  Returns (T, G) tables, e_q (T, G, len(q))."""
+    e = np.asarray(e, dtype=np.float64)
+    word = np.asarray(word, dtype=np.uint32)
+    T, B = word.shape
+    group = np.zeros(B, dtype=np.int64) if group is None else np.asarray(group, dtype=np.int64).reshape(B)
+    G = int(group.max()) + 1 if G is None else int(G)
+    q = np.asarray(q, dtype=np.float64).reshape(-1)
+    f = unpack_series_word(word)
+    out = {k: np.zeros((T, G), dtype=np.int64 if k.endswith("_sum") else np.int32) for k in SERIES_INT_TABLES}
+    out["e_sum"], out["e_max"] = np.zeros((T, G)), np.full((T, G), np.nan)
+    out["e_q"] = np.full((T, G, q.size), np.nan)
+    for g in range(G):
+        members = np.flatnonzero(group == g)
+        for t in range(T):
+            m = members[f["alive"][t, members]]
+            out["n_alive"][t, g] = m.size
+            for k in ("lost_up", "lost_down", "adopted", "tube", "not_optimal", "overrun"):
+                out[k][t, g] = np.count_nonzero(f[k][t, m])
+            for k in ("age", "iters"):
+                out[k + "_max"][t, g] = f[k][t, m].max(initial=0)
+                out[k + "_sum"][t, g] = f[k][t, m].sum(dtype=np.int64)
+            v = e[t, m]
+            nan = np.isnan(v)
+            out["n_nan"][t, g] = np.count_nonzero(nan)
+            v = np.sort(v[~nan])
+            if v.size:
+                out["e_sum"][t, g], out["e_max"][t, g] = v.sum(), v[-1]
+                out["e_q"][t, g] = v[np.floor(q * (v.size - 1)).astype(np.int64)]
+    return out
+
+
+class _SeriesRecord:
+    """The per-step record of the closed loops (include/tmpc.h: tmpc_mc_set_series), kept by the host twins: e (T, B) the error term
+    of the step, word (T, B) the packed flags, iterations and age; entries of trajectories that did not take the step stay 0."""
+
+    def __init__(self, T: int, nb: int, N: int):
+        self.N = int(N)
+        self.e, self.word = np.zeros((T, nb)), np.zeros((T, nb), dtype=np.uint32)
+
+    def step(self, t: int, alive, a, theta_drawn, gamma_drawn, Theta, tube, status, iters, s):
+        age = t - np.asarray(s, dtype=np.int64)
+        w = pack_series_word(True, theta_drawn == 0, gamma_drawn == 0, np.asarray(Theta) == 1, tube, np.asarray(status) != 0, age >= self.N,
+                             iters, age)
+        self.e[t] = np.where(alive, a, 0.0)
+        self.word[t] = np.where(alive, w, np.uint32(0))
+
+    def result(self):
+        return decode_series(self.e, self.word)
+
+
+def _packets(res):
+    """(U_t, x_nom_0, status, iters) of a packets_fn result: the fourth entry, the iterations of the solves, is optional (0)."""
+    return res[0], res[1], res[2], (res[3] if len(res) > 3 else 0)
+
+
 class _LinkStats:
     """The four link statistics of the closed loops (include/tmpc.h: tmpc_mc_get_link_stats), kept by the host twins."""
 
@@ -243,7 +338,7 @@ class _LinkStats:
 
 
 def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, ga_u, w, x0=None, extended: bool = False,
-                        plant=None, capture=None, observer=None, channel=None):
+                        plant=None, capture=None, observer=None, channel=None, series: bool = False):
     """Closed loop of the remote tube-based MPC over a lossy network for a batch of trajectories:
     the body of the reference's Monte-Carlo loop (results_linear_system.py:209-259, 291) with the
     per-trajectory objects replaced by the batched state machines and the QP solves of one time
@@ -263,6 +358,9 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     observer: optional callable (t, {'s', 'Theta', 'u'}) called after the actuator of step t (copies of its s_t, Theta_t and u_t).
     channel: None = independent losses with probability p_loss; or the Gilbert-Elliott channel (channel_parameters, e.g.
     burst_channel(..)) driven by the same uniforms -- p_loss is then not read and may be None.
+    series: also keep the per-step record of the device loops (include/tmpc.h: tmpc_mc_set_series) -> 'series', a dict of (T, B)
+    arrays: e, the error term of every step -- summed over t in order it is 'err2' --, word, and the word's fields (unpack_series_word);
+    the iterations are those packets_fn returns as an optional fourth entry (0 without one).
     Returns a dict of per-trajectory statistics, the link statistics lost_up, lost_down, max_gap, overrun among them."""
     from .Estimator import BatchedEstimator
     from .SmartActuator import BatchedConsistentActuator
@@ -273,6 +371,7 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     p_loss = None if channel is not None else np.asarray(p_loss, dtype=np.float64).reshape(nb)
     theta_all, gamma_all = _loss_flags(channel, p_loss, th_u, ga_u)
     link = _LinkStats(nb, N)
+    rec = _SeriesRecord(T, nb, N) if series else None
     every = np.ones(nb, dtype=bool)
     ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, (B, T) per trajectory, or (B, T, nx) full states
     full_ref = ref.ndim == 3                         # the solve gets ref[:, t, :], the error is sum_i (x_i - r_i)^2
@@ -299,9 +398,9 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
             r_t[:, 0] = ref_at(t)
         q_t = est.get_qt()
         if extended:
-            U_t, x_nom_0, status = packets_fn(est.get_estimate(), r_t, gamma.astype(np.uint8))     # RLX:276, gamma of step t-1
+            U_t, x_nom_0, status, iters = _packets(packets_fn(est.get_estimate(), r_t, gamma.astype(np.uint8)))     # RLX:276, gamma of step t-1
         else:
-            U_t, x_nom_0, status = packets_fn(est.get_estimate(), r_t)                             # :240
+            U_t, x_nom_0, status, iters = _packets(packets_fn(est.get_estimate(), r_t))            # :240
         bad = status >= 2
         not_optimal += (status != 0)
         if bad.any():
@@ -320,13 +419,17 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
         if observer is not None:
             observer(t, dict(s=np.array(act.s).copy(), Theta=np.array(act.Theta).copy(), u=np.array(u).copy()))
         if full_ref:
-            err2 += (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1)        # (the order of the sum below)
+            a_t = (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1)          # (the order of the sum below)
         else:
-            err2 += (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1)                        # :291 (x_t, t = 0..T-1)
+            a_t = (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1)                          # :291 (x_t, t = 0..T-1)
+        err2 += a_t
         # :258 / results_linear_system_with_extendedMPC.py:310-318,331-333 -- x_traj[:, t] - x_nom_traj[:, t]: the nominal state
         # appended after the PREVIOUS step's process_packet, so for the extended controller the state before this step's
         # adoption of x_nom_0 (SmartActuator.py:219-222); for the plain tube MPC the two coincide
-        tube_viol += ~np.asarray(Z.contains((x - x_nom_now).T)).reshape(nb)
+        outside = ~np.asarray(Z.contains((x - x_nom_now).T)).reshape(nb)
+        tube_viol += outside
+        if rec is not None:
+            rec.step(t, every, a_t, theta_all[:, t], gamma_all[:, t], act.Theta, outside, status, iters, act.s)
         if cap is not None:
             cap["x_traj"][t], cap["x_nom_traj"][t], cap["u_traj"][t] = x[capture], x_nom_now[capture], u[capture]
         if plant is not None and hasattr(plant, "trace"):
@@ -346,8 +449,10 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
         ok = (act.Theta == 1) & (gamma == 1)
         if ok.any():
             consistent_err = max(consistent_err, float(np.max(np.abs(est.x_hat[ok] - act.x_nom[ok]))))
-    out = dict(tracking_error=np.sqrt(err2) / T, tube_violations=tube_viol, not_optimal=not_optimal,
+    out = dict(tracking_error=np.sqrt(err2) / T, err2=err2, tube_violations=tube_viol, not_optimal=not_optimal,
                consistent_estimate_error=consistent_err, x_final=x, **link.result())
+    if rec is not None:
+        out["series"] = rec.result()
     if n_phys:
         out["tracking_error_physics"] = np.sqrt(err2_phys) / n_phys
     if cap is not None:
@@ -355,11 +460,12 @@ def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, g
     return out
 
 
-def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, x0=None, channel=None, plant=None):
+def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, x0=None, channel=None, plant=None, series: bool = False):
     """Closed loop of the non-robust comparator (R-MPC) over the lossy network: TrackingMPC + Estimator + plain
     SmartActuator (results_linear_system.py:198-205, 262-287).  A trajectory whose solve is infeasible stops there
     (track_feasible = False, :268-270) and reports a NaN tracking error (:297), and its link statistics stop at that step.  Same
-    conventions as run_remote_tube_mpc otherwise (`channel` and `plant` included)."""
+    conventions as run_remote_tube_mpc otherwise (`channel`, `plant` and `series` included: a stopped trajectory's record is not alive
+    from the step of its infeasible solve on; 'err2' keeps the sum up to there, the tracking error is NaN)."""
     from .Estimator import BatchedEstimator
     from .SmartActuator import BatchedConsistentActuator
     A = np.asarray(A, dtype=np.float64)
@@ -369,6 +475,7 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
     p_loss = None if channel is not None else np.asarray(p_loss, dtype=np.float64).reshape(nb)
     theta_all, gamma_all = _loss_flags(channel, p_loss, th_u, ga_u)
     link = _LinkStats(nb, N)
+    rec = _SeriesRecord(T, nb, N) if series else None
     ref = np.asarray(ref, dtype=np.float64)          # (T,) shared by the batch, (B, T) per trajectory, or (B, T, nx) full states
     full_ref = ref.ndim == 3                         # the solve gets ref[:, t, :], the error is sum_i (x_i - r_i)^2
 
@@ -389,7 +496,7 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
             r_t = np.zeros((nb, nx))
             r_t[:, 0] = ref_at(t)
         q_t = est.get_qt()
-        U_t, _, status = packets_fn(est.get_estimate(), r_t)
+        U_t, _, status, iters = _packets(packets_fn(est.get_estimate(), r_t))
         newly = ~dead & (status >= 2)
         not_optimal += (~dead & (status != 0))
         dead |= newly
@@ -401,15 +508,21 @@ def run_remote_tracking_mpc(packets_fn, A, B, K, N, p_loss, ref, th_u, ga_u, w, 
         pkt = {"x_t": x.copy(), "s_t": pkt["s_t"]}
         link.step(t, ~dead, theta_all[:, t], gamma_all[:, t], act.s)
         if full_ref:
-            err2 += np.where(dead, 0.0, (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1))
+            a_t = np.where(dead, 0.0, (x[:, 0] - r_t[:, 0]) ** 2 + np.sum((x[:, 1:] - r_t[:, 1:]) ** 2, axis=1))
         else:
-            err2 += np.where(dead, 0.0, (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1))
+            a_t = np.where(dead, 0.0, (x[:, 0] - ref_at(t)) ** 2 + np.sum(x[:, 1:] ** 2, axis=1))
+        err2 += a_t
+        if rec is not None:      # (no tube: the comparator has no nominal model)
+            rec.step(t, ~dead, a_t, theta_all[:, t], gamma_all[:, t], act.Theta, False, status, iters, act.s)
         x = np.where(dead[:, None], x, (x @ A.T + u @ Bm.T if plant is None else plant(x, u)) + w[:, t])
         gamma = gamma_all[:, t]
         est.update(pkt, gamma)
     te = np.sqrt(err2) / T
     te[dead] = np.nan
-    return dict(tracking_error=te, not_optimal=not_optimal, infeasible=dead, x_final=x, **link.result())
+    out = dict(tracking_error=te, err2=err2, not_optimal=not_optimal, infeasible=dead, x_final=x, **link.result())
+    if rec is not None:
+        out["series"] = rec.result()
+    return out
 
 
 CARTPOLE_KEYS = ("M", "m", "b", "I", "g", "l")      # the order of a cart-pole row {M, m, b, I, g, l, Th} (include/tmpc.h)
@@ -530,7 +643,7 @@ def plant_callable(plant):
 def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240301, rank: int = 0, world: int = 1,
              extended: bool = False, device=None, on_device: bool = False, plant=None, warm_start: bool = False,
              timing: bool = False, device_rng: bool = False, force_collective: bool = False, ref_id=None, mean_burst=None,
-             link_stats: bool = False):
+             link_stats: bool = False, series=None):
     """The Monte-Carlo sweep of results_linear_system.py:147-301 (BASELINE config 4): len(p_loss) x n_mc
     trajectories of T steps, sharded over `world` ranks (one process per GPU, contiguous p_loss-balanced
     shards), every time step of a shard solved by one kernel launch, statistics all-gathered at the end.
@@ -544,7 +657,14 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     plant: None / "cartpole"; or a PlantFamily of n_total plants (plant_family, sample_cartpole), sliced with the shard -- on the device
     the loop of tmpc_mc_run_plants.
     mean_burst: None -- independent losses; else every loss rate p as the stationary rate of burst_channel(p, mean_burst), on the
-    same uniforms (a rate above 1 - 1 / mean_burst keeps independent losses, whose bursts last 1 / (1 - p) on average; every rate must be below 1).  link_stats: four more columns at the end of the table: lost_up, lost_down, max_gap, overrun."""
+    same uniforms (a rate above 1 - 1 / mean_burst keeps independent losses, whose bursts last 1 / (1 - p) on average; every rate must be below 1).  link_stats: four more columns at the end of the table: lost_up, lost_down, max_gap, overrun.
+    series: None -- nothing more; True or a sequence of quantiles (True: 0.5, 0.95) -- the loops keep their per-step record and a third
+    value is returned, the record's ensemble statistics per time step and loss rate (series_stats, (T, len(p_loss)) tables; on the device
+    tmpc_mc_series_stats).  One rank only: quantiles of shards do not merge (ValueError with world > 1)."""
+    if series is not None and series is not False and world > 1:
+        raise ValueError("mc_sweep: series needs world == 1 (order statistics of shards do not merge)")
+    want_series = series is not None and series is not False
+    series_q = (0.5, 0.95) if series is True else (tuple(series) if want_series else ())
     import torch
     p_loss = np.asarray(p_loss, dtype=np.float64)
     pi, _ = trajectory_table(p_loss, n_mc)
@@ -579,15 +699,16 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     if on_device:        # state machines on the GPU as well (tmpc_mc_run); otherwise the host loop around determine_packets
         out = mpc.run_closed_loop(p_loss[pi[lo:hi]], ref, th, ga, w, extended=extended, plant=plant, warm_start=warm_start,
                                   timing=timing, device_rng=(seed, lo, model["w_bound"]) if device_rng else None, ref_id=ids,
-                                  T=T if ids is not None else None, channel=channel)
+                                  T=T if ids is not None else None, channel=channel, **(dict(series=True) if want_series else {}))
     elif getattr(mpc, "_smart_actuator", False):       # TrackingMPC: the comparator's loop (results_linear_system.py:262-287)
         out = run_remote_tracking_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(), mpc._N,
-                                      p_loss[pi[lo:hi]], ref, th, ga, w, channel=channel, plant=None if plant is None else plant_callable(plant))
+                                      p_loss[pi[lo:hi]], ref, th, ga, w, channel=channel, plant=None if plant is None else plant_callable(plant),
+                                      series=want_series)
         out["tube_violations"] = np.zeros(hi - lo, dtype=np.int32)
     else:
         out = run_remote_tube_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(),
                                   mpc.get_ancillary_controller_gain(), mpc._N, mpc._Z, p_loss[pi[lo:hi]], ref, th, ga, w,
-                                  extended=extended, plant=None if plant is None else plant_callable(plant), channel=channel)
+                                  extended=extended, plant=None if plant is None else plant_callable(plant), channel=channel, series=want_series)
     cols = [out["tracking_error"], out["tube_violations"], out["not_optimal"]]
     if timing and on_device:
         cols += [out["solve_time_mean"], out["solve_time_max"]]
@@ -597,6 +718,13 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     if device is not None:
         local = local.to(device)
     table = gather_statistics(local, n_total, rank, world, force_collective=force_collective)
+    if want_series:
+        if on_device:
+            from . import _native
+            stats = _native.mc_series_stats(mpc._handle, group=pi, q=series_q, G=len(p_loss))
+        else:
+            stats = series_stats(out["series"]["e"], out["series"]["word"], pi, series_q, G=len(p_loss))
+        return table.cpu().numpy(), pi, stats
     return table.cpu().numpy(), pi
 
 

@@ -187,6 +187,11 @@ struct McState {                         // all [trajectory]-major device arrays
     // block [4][B] in this order and fetches it with the loop's other outputs                                           [B]
     int32_t *lost_up, *lost_down;             // steps t > 0 whose controller->plant / plant->controller packet the channel dropped
     int32_t *max_gap, *overrun;               // max_t (t - s_t); steps with t - s_t >= N (the buffer exhausted: the terminal law)
+    // per-step record (tmpc_mc_set_series), both or none (ser_w == nullptr: not recorded), TIME-major: row t is contiguous over the
+    // trajectories, which is what the ensemble reduction reads (tmpc_series.hip).  Zeroed by the host: word 0 = "took no step here"
+    double *ser_e;                            // [T][ser_B] the step's tracking-error term, the very value added to err2
+    uint32_t *ser_w;                          // [T][ser_B] TMPC_SER_* bits | iterations << 8 | age << 20 (include/tmpc.h)
+    int64_t ser_B;                            // row stride = B
 };
 // The caller's side of the stepped closed loop (tmpc_mc_open / tmpc_mc_step_device, m.plant = TMPC_PLANT_EXTERNAL): the plant
 // state of this step comes from the caller and the applied input goes back; X and U are the caller's check sets for the two.

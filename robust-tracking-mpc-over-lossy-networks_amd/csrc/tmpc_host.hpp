@@ -100,6 +100,10 @@ struct LoopRecords {
     int fused = 0;               // tmpc_mc_last_fused
     std::vector<int32_t> link;   // link statistics [4][link_B]: lost_up, lost_down, max_gap, overrun -- a HOST copy, fetched with the loop's
     int64_t link_B = 0;          // other outputs (tmpc_mc_get_link_stats then costs no device call); 0: no loop has finished
+    double *ser_e = nullptr;     // the per-step record (tmpc_mc_set_series): [ser_T][ser_B] each, where the loop left them in the arena
+    uint32_t *ser_w = nullptr;
+    int64_t ser_B = 0;
+    int ser_T = 0;
 };
 
 // One launch lane of a device handle: a non-blocking stream and everything a solve launch on it mutates, so that launches on
@@ -178,6 +182,7 @@ struct LoopSettings {
     // tmpc_mc_set_plant_models (regulator handles): a linear plant per trajectory, [B][nx][nx + nu] (pm_B = 0: none)
     int64_t pm_B = 0;
     std::vector<double> pm;
+    int series = 0;              // tmpc_mc_set_series: the tracking loops keep their per-step record
 };
 }  // namespace tmpc_host
 

@@ -1,6 +1,7 @@
 // The closed loops of libtmpc_hip.so (include/tmpc.h: tmpc_mc_*, tmpc_reg_run): settings, the resident loops and the stepped one.
 #include "tmpc_host.hpp"
 #include "tmpc_plant.hpp"
+#include "tmpc_series.hpp"
 
 using namespace tmpc_host;
 
@@ -84,7 +85,7 @@ struct TrackingLoop {
     const double *p_loss, *ref, *th_u, *ga_u, *w, *x0;
     SetRows Z, X, U;
     const McReplay *rp;         // (tmpc_mc_replay solves nothing and is given its arrival flags: it ignores the reference table and the channel)
-    bool host_draws, full_ref, channel;
+    bool host_draws, full_ref, channel, series;       // (series: tmpc_mc_set_series -- ignored by tmpc_mc_replay like the other two)
 };
 
 // The argument checks of the tracking loops, in the order each entry point has always reported them (it differs between the resident
@@ -97,6 +98,7 @@ int check_tracking_loop(tmpc_handle *h, TrackingLoop &q) {
     q.host_draws = q.rp != nullptr || !h->loop.rng_on;
     q.full_ref = !q.rp && h->loop.ref_K > 0;
     q.channel = !q.rp && h->loop.ch_B > 0;
+    q.series = !q.rp && h->loop.series != 0;
     if (q.session && h->regulator) return refuse("a regulator handle has no stepped loop");
     if (q.session && (q.B <= 0 || q.T <= 0 || q.Z.rows < 0 || q.X.rows < 0 || q.U.rows < 0)) return refuse("need B > 0, T > 0 and row counts >= 0");
     if (q.B < 0 || q.T < 0 || (!q.p_loss && !q.channel) || (!q.ref && !q.full_ref) || (q.host_draws && (!q.th_u || !q.ga_u || (!q.session && !q.w))) ||
@@ -179,6 +181,11 @@ void tracking_pieces(tmpc_handle *h, const TrackingLoop &q, tmpc::McModel &m, tm
         st.ref_T = L.ref_T;
         if (s) a.piece(&s->ref_stage, b * nx * 8, nullptr, 0);
     }
+    if (q.series) {         // the per-step record, time-major; zeros: "took no step here"
+        a.piece(&st.ser_e, t_ * b * 8, nullptr, 0);
+        a.piece(&st.ser_w, t_ * b * 4, nullptr, 0);
+        st.ser_B = q.B;
+    }
     if (q.rp) {
         // (plain controller: the packets carry no x_nom_0; the state machines then never read it -- zeros)
         a.piece(&st.rp_U, b * t_ * (N + 1) * nu * 8, q.rp->U);
@@ -204,6 +211,7 @@ int fetch_tracking_results(tmpc_handle *h, const tmpc::McState &st, int64_t B, i
     if (st.err2_phys) { h->rec.err2_phys = st.err2_phys; h->rec.phys_B = B; }
     if (st.tick_sum) { h->rec.tick_sum = st.tick_sum; h->rec.tick_max = st.tick_max; h->rec.tick_B = B; }
     h->rec.link_B = B;
+    if (st.ser_w) { h->rec.ser_e = st.ser_e; h->rec.ser_w = st.ser_w; h->rec.ser_B = B; h->rec.ser_T = T; }
     return TMPC_OK;
 }
 
@@ -225,7 +233,8 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
     // that launch is a trajectory, T solves long: with B a little above a multiple of the resident waves the last round
     // of trajectories would run on a nearly empty card, so TMPC_MC_FUSED_AUTO fuses when the rounds are at least 85 % full
     // (or there is a single round) and otherwise keeps the launch per time step, whose work item is one solve.
-    bool fuse = !rp && !extended && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]);
+    // (a loop that keeps its per-step record runs per time step: the fused kernels are compiled without the recording)
+    bool fuse = !rp && !extended && !q.series && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]);
     if (fuse && h->loop.fused == TMPC_MC_FUSED_AUTO) {
         const int64_t slots = tmpc::resident_waves(h->v[0].shape, h->n_cu);
         const int64_t rounds = slots > 0 ? (B + slots - 1) / slots : 0;
@@ -235,7 +244,7 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
     // its trajectories inside (closed_loop_step_kernel) -- two launches per step where the plain per-step loop has three
     // (TMPC_MC_FUSED_AUTO: from one round of resident waves on -- below that a step is the latency of its launches, and the state
     // machines inside BOTH of them lengthen it: 200 trajectories at N = 20 0.0345 s with three launches per step, 0.0367 s with two)
-    bool step_fuse = !rp && extended && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]) && !use_block(h, h->v[1]);
+    bool step_fuse = !rp && extended && !q.series && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]) && !use_block(h, h->v[1]);
     if (step_fuse && h->loop.fused == TMPC_MC_FUSED_AUTO) step_fuse = B >= tmpc::resident_waves(h->v[1].shape, h->n_cu);
     // the fused kernels' record {model, state, T, reference}: uploaded once the state is carved; lives until the final synchronise
     tmpc::McFused mf{};
@@ -449,6 +458,101 @@ std::string plant_family_error(const char *who, int kind, int nx, int nu, int su
     if (nx < 1 || nx > 16 || nu < 1 || nu > 16) return w + "need 1 <= nx <= 16 and 1 <= nu <= 16";
     return std::string();
 }
+// ---- ensemble statistics of the per-step record (tmpc_series.hip; include/tmpc.h: tmpc_mc_series_stats, tmpc_series_stats)
+// the output tables in the order of the C entry points; any may be NULL
+struct SeriesOut {
+    int32_t *i[tmpc::SERIES_INT_TABLES];         // n_alive, n_nan, lost_up, lost_down, adopted, tube, not_optimal, overrun, age_max, iters_max
+    int64_t *l[tmpc::SERIES_LONG_TABLES];        // age_sum, iters_sum
+    double *d[tmpc::SERIES_REAL_TABLES];         // e_sum, e_max
+    double *q;                                   // [T][G][n_q]
+    float *kernel_ms;
+};
+// The argument errors of a reduction, found on the host before anything touches the device: empty, or the message, which names the argument
+std::string series_args_error(const char *who, int64_t B, int32_t T, int32_t G, const int32_t *group, int32_t n_q, const double *q) {
+    const std::string w = std::string(who) + ": ";
+    if (B < 1) return w + "B < 1";
+    if (T < 1) return w + "T < 1";
+    if (G < 1) return w + "G < 1";
+    if (B > 0x7fffffffll) return w + "B is beyond 2^31 - 1 trajectories";
+    if (static_cast<int64_t>(T) * G > 0x7fffffffll) return w + "T * G is beyond 2^31 - 1 columns";
+    if (n_q < 0 || n_q > TMPC_SER_MAX_Q) return w + "n_q = " + std::to_string(n_q) + " is not in [0, " + std::to_string(TMPC_SER_MAX_Q) + "]";
+    if (n_q > 0 && !q) return w + "q is NULL";
+    for (int32_t i = 0; i < n_q; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return w + "q[" + std::to_string(i) + "] = " + std::to_string(q[i]) + " is not in [0, 1]";      // (NaN fails both)
+    for (int64_t b = 0; group && b < B; ++b)
+        if (group[b] < -1 || group[b] >= G) return w + "group[" + std::to_string(b) + "] = " + std::to_string(group[b]) + " is neither -1 nor in [0, " + std::to_string(G) + ")";
+    return std::string();
+}
+// The reduction of a record that lies on the current device (arguments checked): the member list sorted by group, one launch on `stream`,
+// the tables that are wanted copied out.  Its device memory is its own, one block: a handle's arena keeps the record.
+int series_reduce(const char *who, std::string &err, const double *d_e, const uint32_t *d_w, int64_t B, int32_t T, int32_t G, const int32_t *group,
+                  int32_t n_q, const double *q, const SeriesOut &out, hipStream_t stream) {
+    const size_t b_ = static_cast<size_t>(B), g_ = static_cast<size_t>(G), ncol = static_cast<size_t>(T) * g_, nq = static_cast<size_t>(n_q);
+    // counting sort of the trajectories by group (stable: ascending b inside a group); -1: in no group
+    std::vector<int32_t> start(g_ + 1, 0), member(b_);
+    for (size_t b = 0; b < b_; ++b) {
+        const int32_t g = group ? group[b] : 0;
+        if (g >= 0) ++start[static_cast<size_t>(g) + 1];
+    }
+    for (size_t g = 0; g < g_; ++g) start[g + 1] += start[g];
+    {
+        std::vector<int32_t> next(start.begin(), start.end() - 1);
+        for (size_t b = 0; b < b_; ++b) {
+            const int32_t g = group ? group[b] : 0;
+            if (g >= 0) member[static_cast<size_t>(next[static_cast<size_t>(g)]++)] = static_cast<int32_t>(b);
+        }
+    }
+    struct Block {
+        char *p = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        ~Block() {
+            if (p) (void)hipFree(p);
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        }
+    } blk;
+    // 8-byte tables first: q | age_sum, iters_sum | e_sum, e_max | e_q | the ten int32 tables | members | group starts
+    const size_t off_l = TMPC_SER_MAX_Q * 8, off_d = off_l + tmpc::SERIES_LONG_TABLES * ncol * 8, off_q = off_d + tmpc::SERIES_REAL_TABLES * ncol * 8,
+                 off_i = off_q + ncol * nq * 8, off_m = off_i + tmpc::SERIES_INT_TABLES * ncol * 4, off_s = off_m + b_ * 4, total = off_s + (g_ + 1) * 4;
+    auto fail = [&](const char *what, hipError_t e) { err = std::string(who) + ": " + what + ": " + hipGetErrorString(e); return TMPC_E_DEVICE; };
+    if (hipMalloc(reinterpret_cast<void **>(&blk.p), total) != hipSuccess) {
+        (void)hipGetLastError();
+        blk.p = nullptr;
+        err = std::string(who) + ": out of device memory";
+        return TMPC_E_NOMEM;
+    }
+    hipError_t e = hipSuccess;
+    if (n_q > 0 && (e = hipMemcpyAsync(blk.p, q, nq * 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail("upload", e);
+    if ((e = hipMemcpyAsync(blk.p + off_m, member.data(), b_ * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail("upload", e);
+    if ((e = hipMemcpyAsync(blk.p + off_s, start.data(), (g_ + 1) * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail("upload", e);
+    tmpc::SeriesStats a{};
+    a.B = B; a.T = T; a.G = G; a.n_q = n_q;
+    a.e = d_e; a.word = d_w;
+    a.member = reinterpret_cast<const int32_t *>(blk.p + off_m); a.start = reinterpret_cast<const int32_t *>(blk.p + off_s);
+    a.q = reinterpret_cast<const double *>(blk.p);
+    a.out_l = reinterpret_cast<int64_t *>(blk.p + off_l); a.out_d = reinterpret_cast<double *>(blk.p + off_d);
+    a.out_q = reinterpret_cast<double *>(blk.p + off_q); a.out_i = reinterpret_cast<int32_t *>(blk.p + off_i);
+    for (hipEvent_t &ev : blk.ev)
+        if ((e = hipEventCreate(&ev)) != hipSuccess) return fail("hipEventCreate", e);
+    if ((e = hipEventRecord(blk.ev[0], stream)) != hipSuccess) return fail("hipEventRecord", e);
+    if ((e = tmpc::launch_series_stats(a, stream)) != hipSuccess) return fail("launch", e);
+    if ((e = hipEventRecord(blk.ev[1], stream)) != hipSuccess) return fail("hipEventRecord", e);
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
+    if (out.kernel_ms && (e = hipEventElapsedTime(out.kernel_ms, blk.ev[0], blk.ev[1])) != hipSuccess) return fail("hipEventElapsedTime", e);
+    for (int k = 0; k < tmpc::SERIES_INT_TABLES; ++k)
+        if (out.i[k] && (e = hipMemcpy(out.i[k], a.out_i + k * ncol, ncol * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail("copy-out", e);
+    for (int k = 0; k < tmpc::SERIES_LONG_TABLES; ++k)
+        if (out.l[k] && (e = hipMemcpy(out.l[k], a.out_l + k * ncol, ncol * 8, hipMemcpyDeviceToHost)) != hipSuccess) return fail("copy-out", e);
+    for (int k = 0; k < tmpc::SERIES_REAL_TABLES; ++k)
+        if (out.d[k] && (e = hipMemcpy(out.d[k], a.out_d + k * ncol, ncol * 8, hipMemcpyDeviceToHost)) != hipSuccess) return fail("copy-out", e);
+    if (out.q && n_q > 0 && (e = hipMemcpy(out.q, a.out_q, ncol * nq * 8, hipMemcpyDeviceToHost)) != hipSuccess) return fail("copy-out", e);
+    return TMPC_OK;
+}
+// the record the getters read: is there one of this shape?
+bool series_missing(tmpc_handle *h, const char *who, int64_t B, int32_t T) {
+    if (h->rec.ser_w && B == h->rec.ser_B && T == h->rec.ser_T) return false;
+    h->err = std::string(who) + ": no tracking loop of this B and T has kept its per-step record (tmpc_mc_set_series before tmpc_mc_run, tmpc_mc_run_plants or tmpc_mc_open)";
+    return true;
+}
 }  // namespace
 
 extern "C" {
@@ -628,6 +732,68 @@ int tmpc_mc_get_link_stats(tmpc_handle *h, int64_t B, int32_t *lost_up, int32_t 
     for (size_t k = 0; k < 4; ++k)
         if (out[k]) std::memcpy(out[k], h->rec.link.data() + k * b, b * sizeof(int32_t));
     return TMPC_OK;
+}
+
+int tmpc_mc_set_series(tmpc_handle *h, int on) {
+    if (!h || session_bars(h, "tmpc_mc_set_series")) return TMPC_E_INVALID;
+    if (h->regulator) { h->err = "tmpc_mc_set_series: a regulator handle keeps no per-step record"; return TMPC_E_INVALID; }
+    h->loop.series = on ? 1 : 0;
+    return TMPC_OK;
+}
+
+int tmpc_mc_get_series(tmpc_handle *h, int64_t B, int32_t T, double *e, uint32_t *word) {
+    if (!h) return TMPC_E_INVALID;
+    if (series_missing(h, "tmpc_mc_get_series", B, T)) return TMPC_E_INVALID;
+    const size_t n = static_cast<size_t>(B) * static_cast<size_t>(T);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, sync_lanes(h));
+    if (e) HIP_TRY(h, hipMemcpy(e, h->rec.ser_e, n * 8, hipMemcpyDeviceToHost));
+    if (word) HIP_TRY(h, hipMemcpy(word, h->rec.ser_w, n * 4, hipMemcpyDeviceToHost));
+    return TMPC_OK;
+}
+
+int tmpc_mc_series_stats(tmpc_handle *h, int64_t B, int32_t T, int32_t G, const int32_t *group, int32_t n_q, const double *q, int32_t *n_alive,
+                         int32_t *n_nan, int32_t *lost_up, int32_t *lost_down, int32_t *adopted, int32_t *tube, int32_t *not_optimal, int32_t *overrun,
+                         int32_t *age_max, int64_t *age_sum, int32_t *iters_max, int64_t *iters_sum, double *e_sum, double *e_max, double *e_q,
+                         float *kernel_ms) {
+    const char *who = "tmpc_mc_series_stats";
+    if (!h) return TMPC_E_INVALID;
+    if (const std::string bad = series_args_error(who, B, T, G, group, n_q, q); !bad.empty()) { h->err = bad; return TMPC_E_INVALID; }
+    if (series_missing(h, who, B, T)) return TMPC_E_INVALID;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, sync_lanes(h));
+    const SeriesOut out{{n_alive, n_nan, lost_up, lost_down, adopted, tube, not_optimal, overrun, age_max, iters_max}, {age_sum, iters_sum}, {e_sum, e_max}, e_q, kernel_ms};
+    return series_reduce(who, h->err, h->rec.ser_e, h->rec.ser_w, B, T, G, group, n_q, q, out, h->stream);
+}
+
+int tmpc_series_stats(int device, int64_t B, int32_t T, const double *e, const uint32_t *word, int32_t G, const int32_t *group, int32_t n_q,
+                      const double *q, int32_t *n_alive, int32_t *n_nan, int32_t *lost_up, int32_t *lost_down, int32_t *adopted, int32_t *tube,
+                      int32_t *not_optimal, int32_t *overrun, int32_t *age_max, int64_t *age_sum, int32_t *iters_max, int64_t *iters_sum,
+                      double *e_sum, double *e_max, double *e_q, float *kernel_ms) {
+    const char *who = "tmpc_series_stats";
+    if (std::string bad = series_args_error(who, B, T, G, group, n_q, q); !bad.empty() || !e || !word) {
+        if (bad.empty()) bad = std::string(who) + (!e ? ": e is NULL" : ": word is NULL");
+        g_create_error = bad;
+        return TMPC_E_INVALID;
+    }
+    if (device < 0) { g_create_error = std::string(who) + ": device < 0: the reduction runs on the GPU"; return TMPC_E_DEVICE; }
+    struct Record {
+        char *p = nullptr;
+        ~Record() { if (p) (void)hipFree(p); }
+    } rec;
+    const size_t n = static_cast<size_t>(B) * static_cast<size_t>(T);
+    auto fail = [&](const char *what, hipError_t err) { g_create_error = std::string(who) + ": " + what + ": " + hipGetErrorString(err); return TMPC_E_DEVICE; };
+    if (const hipError_t err = hipSetDevice(device); err != hipSuccess) return fail("hipSetDevice", err);
+    if (hipMalloc(reinterpret_cast<void **>(&rec.p), n * 12) != hipSuccess) {
+        (void)hipGetLastError();
+        rec.p = nullptr;
+        g_create_error = std::string(who) + ": out of device memory";
+        return TMPC_E_NOMEM;
+    }
+    if (const hipError_t err = hipMemcpy(rec.p, e, n * 8, hipMemcpyHostToDevice); err != hipSuccess) return fail("upload", err);
+    if (const hipError_t err = hipMemcpy(rec.p + n * 8, word, n * 4, hipMemcpyHostToDevice); err != hipSuccess) return fail("upload", err);
+    const SeriesOut out{{n_alive, n_nan, lost_up, lost_down, adopted, tube, not_optimal, overrun, age_max, iters_max}, {age_sum, iters_sum}, {e_sum, e_max}, e_q, kernel_ms};
+    return series_reduce(who, g_create_error, reinterpret_cast<const double *>(rec.p), reinterpret_cast<const uint32_t *>(rec.p + n * 8), B, T, G, group, n_q, q, out, nullptr);
 }
 
 int tmpc_mc_set_warm_start(tmpc_handle *h, int on) {

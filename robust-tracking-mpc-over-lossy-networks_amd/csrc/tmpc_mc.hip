@@ -53,7 +53,7 @@ __global__ __launch_bounds__(WAVE_MC * MC_WPB) void mc_step_kernel(const McModel
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t b = static_cast<int64_t>(blockIdx.x) * MC_WPB + wave;
     if (b >= B) return;
-    (void)mc_step_wave(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, sh[wave], lane);
+    (void)mc_step_wave<true>(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, sh[wave], lane);
 }
 
 // The same launch for the stepped loop (tmpc_mc_step_device): the plant state is the caller's array, the applied input goes to
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(WAVE_MC * MC_WPB) void mc_session_kernel(const McMo
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t b = static_cast<int64_t>(blockIdx.x) * MC_WPB + wave;
     if (b >= B) return;
-    (void)mc_step_impl<true>(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, sh[wave], lane, nullptr, ext);
+    (void)mc_step_impl<true, true>(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, sh[wave], lane, nullptr, ext);
 }
 
 }  // namespace

@@ -119,7 +119,12 @@ enum { V_X = 0, V_XN, V_E, V_ET, V_U, V_UN, V_BASE, V_TMP, V_COUNT };
 // st.ch_thr != nullptr (tmpc_mc_set_channel): the two loss tests are those of the Gilbert-Elliott channel, whose link states live in
 // st.ch_state; p_loss is then not read.  One wave-uniform branch per link.  A failed solve forces theta = 0 as ever and leaves the
 // channel's state to the draw.  st.lost_up != nullptr: lane 0 keeps the link statistics, with either loss model.
-template <bool EXT, class ModelRec, class StateRec>
+//
+// SER = true and st.ser_w != nullptr (tmpc_mc_set_series): lane 0 of a trajectory that took the step stores the step's error term and its
+// packed word (include/tmpc.h: TMPC_SER_*) at [t][b] -- one store each at the very end, from values the step has computed anyway; one
+// wave-uniform branch.  A template parameter like EXT: the fused solve kernels are compiled without it and keep their code and their
+// registers (a loop that records runs its state machines in the per-step kernels).
+template <bool EXT, bool SER = false, class ModelRec, class StateRec>
 __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &st, const int t, const int T, const int64_t b,
                                              const double ref_t, const double ref_next,
                                              const double *u_nom, const double *x_nom0, const double *xu_ss, const int32_t *status,
@@ -237,6 +242,8 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
     mc_fence();
     const int d = t - s_t;
     const bool inside = d < N;
+    [[maybe_unused]] double ser_a = 0.0;              // SER: the error term and the tube verdict of this step, as lane 0 has them
+    [[maybe_unused]] int ser_tube = 0;
     double un_l = 0.0, u_l = 0.0;
     if (lu) {
         // (Theta = 1 means s_t = t: the input is column 0 of the packet just adopted -- read from the packet, not back from the buffer)
@@ -281,6 +288,7 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
             double a = (S[V_X][0] - S[V_TMP][0]) * (S[V_X][0] - S[V_TMP][0]);
             for (int i = 1; i < nx; ++i) a += (S[V_X][i] - S[V_TMP][i]) * (S[V_X][i] - S[V_TMP][i]);
             st.err2[b] += a;
+            if constexpr (SER) ser_a = a;
         }
         if (!EXT && m.plant == TMPC_PLANT_CARTPOLE)
             for (int i = 0; i < 4; ++i) rp[i] = S[V_TMP][i];
@@ -289,6 +297,7 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
         double a = (S[V_X][0] - ref_t) * (S[V_X][0] - ref_t);
         for (int i = 1; i < nx; ++i) a += S[V_X][i] * S[V_X][i];
         st.err2[b] += a;
+        if constexpr (SER) ser_a = a;
     }
     if (m.rZ > 0) {
         // x_t - x_nom_t in Z (:258): the rZ rows of Z over the lanes
@@ -298,7 +307,9 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
             for (int i = 0; i < nx; ++i) v += m.HZ[r * nx + i] * S[V_ET][i];
             out |= (v > 1e-7);                                  // polytope's abs_tol
         }
-        if (__any(out) && lane == 0) st.tube_viol[b] += 1;
+        const int left = __any(out);
+        if (left && lane == 0) st.tube_viol[b] += 1;
+        if constexpr (SER) ser_tube = left ? 1 : 0;
     }
     if constexpr (EXT) {
         // the caller's plant in X, the applied input in U (rows over the lanes, abs_tol as above; tmpc_reg.hip: set_violated)
@@ -423,17 +434,29 @@ __device__ __forceinline__ bool mc_step_impl(const ModelRec &m, const StateRec &
         if (lu) tf[3 * nx + lane] = u_l;
         if (lane == 0) { int32_t *ti = st.trace_i + (b * T + t) * 3; ti[0] = s_t; ti[1] = Theta; ti[2] = q_before; }
     }
+    if constexpr (SER) {
+        if (st.ser_w != nullptr && lane == 0) {
+            const int it = replay ? 0 : iters[b];
+            const uint32_t word = TMPC_SER_ALIVE | (lost_u ? TMPC_SER_LOST_UP : 0u) | (lost_d ? TMPC_SER_LOST_DOWN : 0u) | (Theta ? TMPC_SER_ADOPTED : 0u) |
+                                  (ser_tube ? TMPC_SER_TUBE : 0u) | (stat != 0 ? TMPC_SER_NOT_OPTIMAL : 0u) | (d >= N ? TMPC_SER_OVERRUN : 0u) |
+                                  (static_cast<uint32_t>(it < 0 ? 0 : (it > TMPC_SER_SATURATE ? TMPC_SER_SATURATE : it)) << TMPC_SER_ITERS_SHIFT) |
+                                  (static_cast<uint32_t>(d > TMPC_SER_SATURATE ? TMPC_SER_SATURATE : d) << TMPC_SER_AGE_SHIFT);
+            const int64_t at = static_cast<int64_t>(t) * st.ser_B + b;
+            st.ser_e[at] = ser_a;
+            st.ser_w[at] = word;
+        }
+    }
     return true;
 }
 
-// the loops that own their plant (tmpc_mc_run, tmpc_mc_replay: mc_step_kernel and the fused solve kernels)
-template <class ModelRec, class StateRec>
+// the loops that own their plant (tmpc_mc_run, tmpc_mc_replay: mc_step_kernel, SER = true, and the fused solve kernels, SER = false)
+template <bool SER = false, class ModelRec, class StateRec>
 __device__ __forceinline__ bool mc_step_wave(const ModelRec &m, const StateRec &st, const int t, const int T, const int64_t b,
                                              const double ref_t, const double ref_next,
                                              const double *u_nom, const double *x_nom0, const double *xu_ss, const int32_t *status,
                                              const int32_t *iters, double (&S)[V_COUNT][MAXN], const int lane,
                                              uint8_t *gamma_out = nullptr) {
-    return mc_step_impl<false>(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, S, lane, gamma_out, McExternal{});
+    return mc_step_impl<false, SER>(m, st, t, T, b, ref_t, ref_next, u_nom, x_nom0, xu_ss, status, iters, S, lane, gamma_out, McExternal{});
 }
 
 }  // namespace mcstep

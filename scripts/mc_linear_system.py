@@ -38,6 +38,10 @@ def main():
                     help="a cart-pole per trajectory instead of the controller's model (tmpc_mc_run_plants; numpy plants with --host-loop): M, m, l within "
                          "+-S of nominal, cart friction up to S (montecarlo.sample_cartpole, keyed by the global trajectory index); "
                          "the controller keeps the nominal model")
+    ap.add_argument("--series", default=None, metavar="OUT.npz",
+                    help="keep the loops' per-step record (tmpc_mc_set_series) and save its ensemble statistics per time step and loss rate "
+                         "(tmpc_mc_series_stats: counts, sums, maxima, the median and the 95 %% quantile of the error term) as (T, 10) tables; "
+                         "one rank, not with --reference-streams; with --all-controllers the file name gets the controller's index")
     ap.add_argument("--host-loop", action="store_true", help="state machines in numpy on the host instead of on the device")
     ap.add_argument("--all-controllers", action="store_true",
                     help="tube MPC, extended tube MPC and the tracking MPC one after the other on the SAME realisations "
@@ -69,7 +73,9 @@ def main():
         if args.reference_streams:
             raise SystemExit("--plant-spread goes with the per-trajectory streams, not with --reference-streams")
         plant = montecarlo.sample_cartpole(len(p_loss) * args.n_mc, args.plant_spread, seed=20240301)
-    for label, extended, rmpc in controllers:
+    if args.series and (world != 1 or args.reference_streams):
+        raise SystemExit("--series needs one rank (order statistics of shards do not merge) and the per-trajectory streams")
+    for index, (label, extended, rmpc) in enumerate(controllers):
         # controller set up in the package: offline sets through the batched LP kernel on this rank's device (0.2 s)
         mpc, model = workloads.make_controller("cartpole", args.N, True, extended=extended, device=local, tracking=rmpc)
         t0 = time.time()
@@ -86,10 +92,16 @@ def main():
             pi = np.repeat(np.arange(len(p_loss)), args.n_mc)
         else:
             # one seed for every controller: the same loss patterns and disturbances (per-trajectory streams)
-            table, pi = montecarlo.mc_sweep(mpc, model, p_loss, args.n_mc, args.T, args.ref, rank=rank, world=world,
-                                            extended=extended, device=device, on_device=not args.host_loop, warm_start=args.warm_start,
-                                            timing=args.timing and not args.host_loop, device_rng=args.device_rng, force_collective=use_pg,
-                                            mean_burst=args.mean_burst, link_stats=args.mean_burst is not None, plant=plant)
+            res = montecarlo.mc_sweep(mpc, model, p_loss, args.n_mc, args.T, args.ref, rank=rank, world=world,
+                                      extended=extended, device=device, on_device=not args.host_loop, warm_start=args.warm_start,
+                                      timing=args.timing and not args.host_loop, device_rng=args.device_rng, force_collective=use_pg,
+                                      mean_burst=args.mean_burst, link_stats=args.mean_burst is not None, plant=plant,
+                                      series=(0.5, 0.95) if args.series else None)
+            table, pi = res[0], res[1]
+            if args.series:
+                name = args.series if len(controllers) == 1 else "{0}.{2}{1}".format(*os.path.splitext(args.series), index)
+                np.savez(name, p_loss=p_loss, q=np.array([0.5, 0.95]), **{k: v for k, v in res[2].items() if isinstance(v, np.ndarray)})
+                print(f"   per-step ensemble statistics ({args.T} steps x {len(p_loss)} loss rates) -> {name}")
         dt = time.time() - t0
         if rank == 0:
             report(label, table, pi, p_loss, dt, world, args)
