@@ -848,6 +848,89 @@ int tmpc_estimate_w_models(int device, int32_t nx, int32_t nu, const double *A, 
                            double *order_stats, double *w_min, double *w_max, int64_t *n_samples, int64_t *n_nonfinite,
                            int64_t *not_settled, double *x_final_norm_max, double *x0_used, double *samples, float *kernel_ms);
 
+/*
+ * Sensitivity of the solution to its inputs: the Jacobian of y = [u_nom (N nu) | x_nom0 (nx) | xu_ss (nx + nu)] with respect to
+ * p = [x_k | ref], and its transpose applied to a vector (the backward pass of a differentiable layer around tmpc_solve_batch_device).
+ *
+ * The minimiser of the condensed QP (tmpc_get_condensed; F = [F1 F2], Ebar = [E 0]) is piecewise affine in p.  On the critical region
+ * of a given solution the law follows from one KKT solve on its working set A -- the rows with slack g0_i + E_i x_k - G_i z <= act_tol,
+ * taken in ascending row order (act_tol <= 0 selects 1e-7, on unscaled rows):  M = G_A H^-1 G_A',
+ *   lambda_A = -M^-1 (G_A H^-1 F p + g0_A + Ebar_A p),   dlambda/dp = -M^-1 (G_A H^-1 F + Ebar_A),   dz/dp = -H^-1 (F + G_A' dlambda/dp),
+ * and J = Y dz/dp + Yp with the affine output map y = Y z + Yp p of the condensing (ny x 2 nx, ny = N nu + 2 nx + nu).
+ * NOTHING IS SOLVED HERE: u_nom, x_nom0, xu_ss and status are the outputs of a preceding solve (or of any other solver of the same
+ * problem), from which z is rebuilt.  One kernel launch per problem variant (csrc/tmpc_sens.hip).
+ *
+ * tmpc_sens_jacobian(h, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, J, flag, n_active, active): HOST pointers.
+ *   in   x_k, ref, variant (or NULL), u_nom, x_nom0, xu_ss, status (or NULL: every instance counts as solved): as tmpc_solve_batch
+ *   out  J         B*ny*2nx   [B][ny][2 nx], row-major
+ *        flag      B int32    TMPC_SENS_* bits, below
+ *        n_active  B int32    rows of the working set after the rank test
+ *        active    B*ceil(nc_max/32) uint32 or NULL: bit i (word i / 32, bit i % 32) is set when row i, in tmpc_get_condensed order of
+ *                  the instance's variant, is in the working set after the rank test; nc_max = the largest nc of the handle's variants.
+ *                  The words are the identity of the critical region.
+ * tmpc_sens_vjp(h, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, ybar, pbar, flag, n_active): pbar[b] = J_b' ybar[b],
+ *   ybar [B][ny], pbar [B][2 nx], one right-hand side through the same system; J is not formed.
+ * tmpc_sens_jacobian_device / tmpc_sens_vjp_device: the same with DEVICE pointers, under the ordering contract of tmpc_solve_batch_device:
+ *   calls on a handle take effect as if executed in call order, and a call goes to the other launch lane than the call before it when none
+ *   of its arrays -- read: x_k, ref, variant, u_nom, x_nom0, xu_ss, status, ybar; written: J / pbar, flag, n_active, active; by byte range --
+ *   overlaps an array of the unfinished calls of that call's lane (solve calls and sensitivity calls alike).  Independent calls run side by
+ *   side; a call that overlaps stays behind the call it depends on.  Returns without synchronising (tmpc_synchronize); as there, the
+ *   handle's streams are not ordered against the caller's.  The calls count in tmpc_debug_lane_counters.
+ * tmpc_last_kernel_ms after any of the four: the device time of the call's launches (they count as calls in tmpc_kernel_ms_total).
+ *
+ * Flags:
+ *   TMPC_SENS_SKIPPED    status >= TMPC_STATUS_INFEASIBLE, a variant id out of range, or a non-finite input: the outputs are NaN,
+ *                        n_active 0, no other bit
+ *   TMPC_SENS_DEPENDENT  rows were dropped by the rank test: a row whose pivot in the row-by-row Cholesky factorisation of M falls to
+ *                        rank_tol = 1e-10 times its own diagonal entry of M (and every candidate after nv rows are kept) is left out; the
+ *                        derivative is that on the reduced set
+ *   TMPC_SENS_WEAK       a working row's multiplier is <= mult_tol max(1, |lambda|_inf), mult_tol = 1e-9: the point lies on the boundary of
+ *                        its region; the derivative written is the one-sided one with the row held active
+ *   TMPC_SENS_NOT_KKT    the given point is not a KKT point of its working set: |H z + F p + G_A' lambda_A|_inf > kkt_tol (1 + |F p|_inf),
+ *                        kkt_tol = 1e-6, or a multiplier below minus that; values are still written
+ * The three tolerances are compile-time constants (csrc/tmpc_sens.hpp); LinearMPCOverNetworks/sensitivity.py is the numpy twin.
+ *
+ * Refused before anything touches the device: NULL arguments or B < 0 (TMPC_E_INVALID); an open stepped session (TMPC_E_INVALID); a
+ * regulator handle (TMPC_E_UNSUPPORTED); a variant that keeps unpriced auxiliaries (extended, literal_terminal_row without HTP: the
+ * outputs do not determine z; TMPC_E_UNSUPPORTED); a host-only handle (TMPC_E_DEVICE).  The model part (H^-1, G H^-1, H^-1 F, Y, Yp)
+ * is computed and uploaded by the first sensitivity call of a handle; a handle that never asks allocates nothing.
+ *
+ * tmpc_qp_sensitivity(device, nv, nc, np, ny, H, F, G, g0, Ebar, Y, Yp, B, P, Z, status, act_tol, mode, ybar, out, flag, n_active,
+ *   active): the same launcher on raw condensed data, without a handle (errors through tmpc_last_error(NULL)); HOST pointers.
+ *   H nv*nv (symmetric positive definite), F nv*np, G nc*nv, g0 nc, Ebar nc*np, Y ny*nv, Yp ny*np; P [B][np], Z [B][nv] the minimisers,
+ *   status [B] or NULL; mode TMPC_SENS_JACOBIAN (out [B][ny][np]) or TMPC_SENS_VJP (ybar [B][ny], out [B][np]); active
+ *   [B][ceil(nc/32)] or NULL.  Limits: 1 <= nv <= 128, 0 <= nc <= 2^20, 1 <= np <= 32, 1 <= ny <= 4096 (TMPC_E_INVALID beyond them, as
+ *   for NULL arguments, B < 0 and an H that is not positive definite; device < 0: TMPC_E_DEVICE).
+ * tmpc_sens_get_model(h, variant, F, Ebar, Y, Yp, Rec): what the handle entries hand the kernel beyond tmpc_get_condensed, for a caller
+ *   who drives tmpc_qp_sensitivity or a host implementation with a handle's problem (any pointer may be NULL; works on a host-only handle):
+ *   F nv*2nx = [F1 F2], Ebar nc*2nx = [E 0], Y ny*nv and Yp ny*2nx (y = Y z + Yp [x_k | ref]), Rec nv*(ny + 2nx): z = Rec [y | x_k | ref],
+ *   the map back from a solve's outputs (theta by least squares from xu_ss).  Refusals as above.
+ * Added without an ABI bump: new exports, nothing else changed.
+ */
+#define TMPC_SENS_SKIPPED   0x1
+#define TMPC_SENS_DEPENDENT 0x2
+#define TMPC_SENS_WEAK      0x4
+#define TMPC_SENS_NOT_KKT   0x8
+#define TMPC_SENS_JACOBIAN  0
+#define TMPC_SENS_VJP       1
+int tmpc_sens_jacobian(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                       const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, double *J, int32_t *flag,
+                       int32_t *n_active, uint32_t *active);
+int tmpc_sens_jacobian_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                              const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, double *J, int32_t *flag,
+                              int32_t *n_active, uint32_t *active);
+int tmpc_sens_vjp(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                  const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, const double *ybar, double *pbar,
+                  int32_t *flag, int32_t *n_active);
+int tmpc_sens_vjp_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                         const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, const double *ybar, double *pbar,
+                         int32_t *flag, int32_t *n_active);
+int tmpc_sens_get_model(tmpc_handle *h, int variant, double *F, double *Ebar, double *Y, double *Yp, double *Rec);
+int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
+                        const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t B, const double *P, const double *Z,
+                        const int32_t *status, double act_tol, int mode, const double *ybar, double *out, int32_t *flag, int32_t *n_active,
+                        uint32_t *active);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,16 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         reference itself has no method of this name."""
         return self.solve_optimization_problem(x_k, ref)
 
+    def solve_with_sensitivity(self, x, ref, variant=None, act_tol: float = 0.0) -> dict:
+        """Solves on the device and differentiates the solutions there (include/tmpc.h: tmpc_sens_jacobian): the outputs of `_solve`
+        plus J (B, ny, 2 nx) = d [u_nom | x_nom0 | xu_ss] / d [x | ref], flag (TMPC_SENS_* bits), n_active and active, the bit words
+        of the working set -- the identity of the critical region (sensitivity.decode_active)."""
+        from . import _native
+        out = self._solve(x, ref, variant=variant, want_traj=False)
+        xs = np.asarray(x, dtype=np.float64).reshape(-1, self._nx)
+        out.update(_native.sens_jacobian(self._handle, xs, ref, out, variant=variant, act_tol=act_tol))
+        return out
+
     def _is_batched(self, x) -> bool:
         """(nx,) and the reference's column vector (nx,1) are single instances; (B,nx) is a batch."""
         return np.ndim(x) == 2 and np.shape(x) != (self._nx, 1)

@@ -197,6 +197,16 @@ def lib():
                                    + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 8 + [C.c_int64]
                                    + [C.c_void_p] * 3)
         L.tmpc_reg_run.restype = C.c_int
+        jac = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_double] + [C.c_void_p] * 4
+        vjp = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_double] + [C.c_void_p] * 4
+        for name, sig in (("tmpc_sens_jacobian", jac), ("tmpc_sens_jacobian_device", jac), ("tmpc_sens_vjp", vjp), ("tmpc_sens_vjp_device", vjp)):
+            getattr(L, name).argtypes = sig
+            getattr(L, name).restype = C.c_int
+        L.tmpc_sens_get_model.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.tmpc_sens_get_model.restype = C.c_int
+        L.tmpc_qp_sensitivity.argtypes = ([C.c_int] + [C.c_int32] * 4 + [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_double, C.c_int]
+                                          + [C.c_void_p] * 5)
+        L.tmpc_qp_sensitivity.restype = C.c_int
         _lib = L
     return _lib
 
@@ -1193,4 +1203,105 @@ def estimate_w(A, B, K, T: int, x0=None, x0_box=None, n_traj=None, seed: int = 0
            "x_final_norm_max": worst.value, "x0_used": x0u, "rollout_ms": float(ms[0]), "selection_ms": float(ms[1])}
     if want_samples:
         out["samples"] = smp
+    return out
+
+
+# ---- sensitivity of the solution (include/tmpc.h: tmpc_sens_*, tmpc_qp_sensitivity; csrc/tmpc_sens.hip)
+SENS_SKIPPED, SENS_DEPENDENT, SENS_WEAK, SENS_NOT_KKT = 1, 2, 4, 8
+_SENS_RC = {-1: ValueError, -2: NotImplementedError}
+
+
+def _sens_fail(name: str, rc: int, msg: str):
+    raise _SENS_RC.get(rc, RuntimeError)(f"{name} failed ({rc}): {msg}")
+
+
+def sens_active_words(h: Handle) -> int:
+    """Words per instance of the `active` output: ceil(nc_max / 32) over the handle's variants."""
+    return (max(get_dims(h, k)[1] for k in range(h.nvariants)) + 31) // 32
+
+
+def sens_get_model(h: Handle, variant: int = 0) -> dict:
+    """include/tmpc.h: tmpc_sens_get_model -> F (nv, 2nx), Ebar (nc, 2nx), Y (ny, nv), Yp (ny, 2nx), Rec (nv, ny + 2nx)."""
+    nv, nc, _ = get_dims(h, variant)
+    ny, npar = h.N * h.nu + 2 * h.nx + h.nu, 2 * h.nx
+    out = dict(F=np.zeros((nv, npar)), Ebar=np.zeros((nc, npar)), Y=np.zeros((ny, nv)), Yp=np.zeros((ny, npar)), Rec=np.zeros((nv, ny + npar)))
+    rc = lib().tmpc_sens_get_model(h.ptr, int(variant), *[out[k].ctypes.data for k in ("F", "Ebar", "Y", "Yp", "Rec")])
+    if rc != 0:
+        _sens_fail("tmpc_sens_get_model", rc, h.error())
+    return out
+
+
+def _sens_inputs(h: Handle, x, ref, variant, sol: dict):
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, h.nx))
+    B = x.shape[0]
+    ref = np.ascontiguousarray(np.broadcast_to(np.asarray(ref, dtype=np.float64).reshape(-1, h.nx), (B, h.nx)))
+    var = None if variant is None else np.ascontiguousarray(np.broadcast_to(np.asarray(variant, dtype=np.uint8).reshape(-1), (B,)))
+    u = np.ascontiguousarray(np.asarray(sol["u_nom"], dtype=np.float64).reshape(B, h.N * h.nu))
+    x0 = np.ascontiguousarray(np.asarray(sol["x_nom0"], dtype=np.float64).reshape(B, h.nx))
+    ss = np.ascontiguousarray(np.asarray(sol["xu_ss"], dtype=np.float64).reshape(B, h.nx + h.nu))
+    st = None if sol.get("status") is None else np.ascontiguousarray(np.asarray(sol["status"], dtype=np.int32).reshape(B))
+    return B, x, ref, var, u, x0, ss, st
+
+
+def sens_jacobian(h: Handle, x, ref, sol: dict, variant=None, act_tol: float = 0.0) -> dict:
+    """Host-pointer entry (tmpc_sens_jacobian): the Jacobians of y = [u_nom | x_nom0 | xu_ss] with respect to [x_k | ref] at the
+    solutions `sol` (u_nom, x_nom0, xu_ss, status of a preceding solve) -> J (B, ny, 2nx), flag, n_active, active (B, words)."""
+    B, x, ref, var, u, x0, ss, st = _sens_inputs(h, x, ref, variant, sol)
+    ny = h.N * h.nu + 2 * h.nx + h.nu
+    out = dict(J=np.empty((B, ny, 2 * h.nx)), flag=np.empty(B, np.int32), n_active=np.empty(B, np.int32),
+               active=np.zeros((B, sens_active_words(h)), np.uint32))
+    rc = lib().tmpc_sens_jacobian(h.ptr, B, x.ctypes.data, ref.ctypes.data, _ptr(var), u.ctypes.data, x0.ctypes.data, ss.ctypes.data, _ptr(st),
+                                  float(act_tol), out["J"].ctypes.data, out["flag"].ctypes.data, out["n_active"].ctypes.data, out["active"].ctypes.data)
+    if rc != 0:
+        _sens_fail("tmpc_sens_jacobian", rc, h.error())
+    return out
+
+
+def sens_vjp(h: Handle, x, ref, sol: dict, ybar, variant=None, act_tol: float = 0.0) -> dict:
+    """Host-pointer entry (tmpc_sens_vjp): pbar[b] = J_b' ybar[b] -> pbar (B, 2nx), flag, n_active."""
+    B, x, ref, var, u, x0, ss, st = _sens_inputs(h, x, ref, variant, sol)
+    ny = h.N * h.nu + 2 * h.nx + h.nu
+    ybar = np.ascontiguousarray(np.asarray(ybar, dtype=np.float64).reshape(B, ny))
+    out = dict(pbar=np.empty((B, 2 * h.nx)), flag=np.empty(B, np.int32), n_active=np.empty(B, np.int32))
+    rc = lib().tmpc_sens_vjp(h.ptr, B, x.ctypes.data, ref.ctypes.data, _ptr(var), u.ctypes.data, x0.ctypes.data, ss.ctypes.data, _ptr(st),
+                             float(act_tol), ybar.ctypes.data, out["pbar"].ctypes.data, out["flag"].ctypes.data, out["n_active"].ctypes.data)
+    if rc != 0:
+        _sens_fail("tmpc_sens_vjp", rc, h.error())
+    return out
+
+
+def sens_jacobian_device(h: Handle, B: int, x_ptr, r_ptr, var_ptr, u_ptr, x0_ptr, ss_ptr, st_ptr, act_tol, J_ptr, flag_ptr, nact_ptr, act_ptr):
+    """Device-pointer entry (tmpc_sens_jacobian_device): raw addresses; returns without synchronising."""
+    rc = lib().tmpc_sens_jacobian_device(h.ptr, int(B), x_ptr, r_ptr, var_ptr, u_ptr, x0_ptr, ss_ptr, st_ptr, float(act_tol), J_ptr, flag_ptr, nact_ptr, act_ptr)
+    if rc != 0:
+        _sens_fail("tmpc_sens_jacobian_device", rc, h.error())
+
+
+def sens_vjp_device(h: Handle, B: int, x_ptr, r_ptr, var_ptr, u_ptr, x0_ptr, ss_ptr, st_ptr, act_tol, ybar_ptr, pbar_ptr, flag_ptr, nact_ptr):
+    """Device-pointer entry (tmpc_sens_vjp_device): raw addresses; returns without synchronising."""
+    rc = lib().tmpc_sens_vjp_device(h.ptr, int(B), x_ptr, r_ptr, var_ptr, u_ptr, x0_ptr, ss_ptr, st_ptr, float(act_tol), ybar_ptr, pbar_ptr, flag_ptr, nact_ptr)
+    if rc != 0:
+        _sens_fail("tmpc_sens_vjp_device", rc, h.error())
+
+
+def qp_sensitivity(H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol: float = 0.0, mode: str = "jacobian", ybar=None, device: int = 0) -> dict:
+    """include/tmpc.h: tmpc_qp_sensitivity -- the sensitivity kernel on raw condensed data, without a handle; arguments and result as
+    LinearMPCOverNetworks.sensitivity.qp_sensitivity, its numpy twin (without `lam`)."""
+    H, F, G, g0, Ebar, Y, Yp = (_contiguous(a) for a in (H, F, G, g0, Ebar, Y, Yp))
+    nv, npar = F.shape
+    nc, ny = g0.shape[0], Y.shape[0]
+    P = _contiguous(P).reshape(-1, npar)
+    Z = _contiguous(Z).reshape(-1, nv)
+    B = P.shape[0]
+    vjp = mode == "vjp"
+    st = None if status is None else np.ascontiguousarray(np.asarray(status, dtype=np.int32).reshape(B))
+    yb = _contiguous(ybar).reshape(B, ny) if vjp else None
+    out = dict(out=np.empty((B, npar) if vjp else (B, ny, npar)), flag=np.empty(B, np.int32), n_active=np.empty(B, np.int32),
+               active=np.zeros((B, (nc + 31) // 32), np.uint32))
+    rc = lib().tmpc_qp_sensitivity(int(device), nv, nc, npar, ny, H.ctypes.data, F.ctypes.data, G.ctypes.data if nc else None,
+                                   g0.ctypes.data if nc else None, Ebar.ctypes.data if nc else None, Y.ctypes.data, Yp.ctypes.data, B,
+                                   P.ctypes.data, Z.ctypes.data, _ptr(st), float(act_tol), 1 if vjp else 0, _ptr(yb), out["out"].ctypes.data,
+                                   out["flag"].ctypes.data, out["n_active"].ctypes.data, out["active"].ctypes.data if nc else None)
+    if rc != 0:
+        _sens_fail("tmpc_qp_sensitivity", rc, lib().tmpc_last_error(None).decode())
     return out

@@ -588,6 +588,11 @@ hipError_t sync_lanes(tmpc_handle *h) {
     return e;
 }
 
+// The lane choice and the in-flight record of tmpc_solve_batch_device, for the other entry points that follow its ordering contract
+// (tmpc_sens.cpp)
+int pick_call_lane(tmpc_handle *h, const tmpc::CallRanges &call, Lane **out) { return pick_lane(h, call, out); }
+int note_call(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call) { return h->overlap ? note_in_flight(h, lane, call) : (++lane.calls, TMPC_OK); }
+
 bool use_block(const tmpc_handle *h, const Variant &v) { return h->kernel_path == TMPC_PATH_BLOCK ? v.tiles != 0 : !v.wave_ok; }
 
 // Regulator handles: B x nx zeros in device memory, handed to the solve kernels as their reference (the condensed QP has F2 = 0, but
@@ -758,6 +763,7 @@ void tmpc_destroy(tmpc_handle *h) {
     for (Lane &l : h->lane)
         if (l.stream) (void)hipStreamSynchronize(l.stream);
     release_session(h);                  // (an open stepped loop ends here: its arrays go with the arena below)
+    release_sens(h);
     for (Lane &l : h->lane) {
         for (DeviceBuffer *b : {&l.blk_ws, &l.save, &l.ticks}) b->release();
         if (l.wc.ring) (void)hipFree(l.wc.ring);

@@ -16,9 +16,10 @@ inline bool ranges_overlap(const ByteRange &a, const ByteRange &b) {
     return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi;
 }
 
-// What one solve call touches.  Reads: x_k, ref, variant.  Writes: u_nom, x_nom0, xu_ss, x_nom, status, iters.
+// What one call touches.  A solve call reads x_k, ref, variant and writes u_nom, x_nom0, xu_ss, x_nom, status, iters; a sensitivity call
+// (tmpc_sens.cpp) reads eight arrays and writes four.  Unused slots are empty ranges.
 struct CallRanges {
-    static constexpr int NR = 3, NW = 6;
+    static constexpr int NR = 8, NW = 6;
     ByteRange reads[NR], writes[NW];
     ByteRange hull;                      // covers every range above (empty: the call touches nothing)
 };

@@ -184,6 +184,7 @@ struct LoopSettings {
     std::vector<double> pm;
     int series = 0;              // tmpc_mc_set_series: the tracking loops keep their per-step record
 };
+struct SensState;                // what the sensitivity entry points keep on the device (tmpc_sens.cpp), created by the first such call
 }  // namespace tmpc_host
 
 struct tmpc_handle {
@@ -231,6 +232,7 @@ struct tmpc_handle {
     tmpc_host::Arena arena;
     tmpc_host::LoopRecords rec;
     tmpc_host::McSession ses;
+    tmpc_host::SensState *sens = nullptr;   // tmpc_sens_*: nullptr until the first call (a handle that never asks allocates nothing)
 };
 
 namespace tmpc_host __attribute__((visibility("hidden"))) {
@@ -256,6 +258,10 @@ int enqueue(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const 
 void release_session(tmpc_handle *h);
 int begin_loop(tmpc_handle *h, int64_t B);
 bool session_bars(tmpc_handle *h, const char *who);
+int pick_call_lane(tmpc_handle *h, const tmpc::CallRanges &call, Lane **out);
+int note_call(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call);
+// (tmpc_sens.cpp) frees what the sensitivity calls allocated; the caller has synchronised
+void release_sens(tmpc_handle *h);
 // (tmpc_offline.cpp) cart-pole rows {M, m, b, I, g, l, Th} of n trajectories: empty, or the message naming trajectory and field
 std::string cartpole_rows_error(const char *who, const double *rows, int64_t n);
 }  // namespace tmpc_host
