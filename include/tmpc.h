@@ -931,6 +931,87 @@ int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t 
                         const int32_t *status, double act_tol, int mode, const double *ybar, double *out, int32_t *flag, int32_t *n_active,
                         uint32_t *active);
 
+/*
+ * The explicit control law: a table of critical regions per problem variant, evaluated on the device (csrc/tmpc_law.hip), with the
+ * handle's ordinary solve as the fallback for the instances no stored region holds.
+ *
+ * On the critical region of a working set A (rows of tmpc_get_condensed; the bit words `active` of tmpc_sens_jacobian) the minimiser
+ * is affine in p = [x_k | ref]: with M = G_A H^-1 G_A' and W = G H^-1,
+ *   lambda_A(p) = Kl p + kl,  Kl = -M^-1 (W_A F + Ebar_A),  kl = -M^-1 g0_A;   z(p) = Kz p + kz,  Kz = -H^-1 (F + G_A' Kl),  kz = -H^-1 G_A' kl;
+ *   y(p) = Ky p + ky,  Ky = Y Kz + Yp,  ky = Y kz          (y = [u_nom | x_nom0 | xu_ss], the output map of tmpc_sens_get_model).
+ * The region's polyhedron S p + s >= 0 has nrow = nc + npar rows, in this order: row i < nc outside A is the primal slack
+ * g0_i + Ebar_i p - G_i z(p) + TMPC_LAW_FEAS_TOL; row i < nc inside A is its multiplier lambda_i(p) + TMPC_LAW_MULT_TOL; row nc + j is the
+ * parameter-only row gp0_j + Ep_j x_k + TMPC_LAW_FEAS_TOL (tmpc_get_param_rows).  Acceptance of p by a region is the KKT test of the
+ * strictly convex QP, so an accepted instance gets THE minimiser: a table that is incomplete, badly ordered or built from doubtful
+ * working sets costs speed, never correctness.  The two thresholds are compile-time constants (csrc/tmpc_law.hpp), absolute, on the
+ * unscaled rows; LinearMPCOverNetworks/explicit_law.py is the numpy twin.  A region is built in double on the host with a Cholesky
+ * factorisation of M; a set whose M is not positive definite is refused (id -1).  The empty set is a valid region.
+ *
+ * Per handle and variant the table keeps stable region ids 0 .. R-1 (insertion order; a set already stored keeps its id), a hit
+ * counter per region in device memory, and a search order (a permutation of the ids, insertion order until tmpc_law_reorder).  The
+ * first tmpc_law_* call allocates; a handle that never asks allocates nothing.  Growth beyond the device's memory: TMPC_E_NOMEM, the
+ * table as it was.
+ *
+ * tmpc_law_add(h, variant, n_sets, words, ids): HOST pointers; words [n_sets][ceil(nc/32)] of that variant, ids [n_sets] or NULL.  Waits
+ *   for the handle's launch lanes first.  Works on a host-only handle (for tmpc_law_get_region).
+ * tmpc_law_learn(h, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, ids, n_new): HOST pointers, the inputs and outputs of a
+ *   preceding solve.  Runs the sensitivity kernel for the signatures and adds every one whose flag has neither TMPC_SENS_SKIPPED nor
+ *   TMPC_SENS_NOT_KKT (WEAK and DEPENDENT sets are admissible: acceptance certifies).  ids [B] or NULL: the region of each instance, -1
+ *   where none was added; n_new or NULL: regions that were new.
+ * tmpc_law_eval(h, B, x_k, ref, variant, hint, max_tries, u_nom, x_nom0, xu_ss, x_nom, status, iters, region, tries): HOST pointers, the law
+ *   kernel alone.  Inputs and outputs as tmpc_solve_batch, and
+ *     hint      B int32 or NULL   the region tried first where it is a valid id (last step's region of a closed loop)
+ *     max_tries                   candidates tested per instance at most, the hint included; <= 0: all
+ *     region    B int32           the id of the region that holds the instance, -1: none (a miss)
+ *     tries     B int32 or NULL   candidates tested
+ *   A hit has status TMPC_STATUS_OPTIMAL and iters 0; x_nom is the rollout x_{i+1} = A x_i + B u_i from x_nom0.  A miss has NaN outputs and
+ *   status TMPC_STATUS_NUMERICAL; so has an instance with a non-finite input or a variant id out of range (tries 0).  x_nom, iters,
+ *   hint and tries may be NULL.  An empty table is no error: everything misses.
+ * tmpc_law_solve: the same arguments (iters is required); the misses, and only they, go through the handle's solve kernels in the same
+ *   call -- the law kernel writes a selector byte per instance, and the solve launches that follow on the same launch lane skip every
+ *   instance it has answered.  No host synchronisation, no gather or scatter, no copy.  Every instance is answered as by
+ *   tmpc_solve_batch; region tells which came from the table.
+ * tmpc_law_eval_device / tmpc_law_solve_device: the same with DEVICE pointers, under the ordering contract of tmpc_solve_batch_device (read:
+ *   x_k, ref, variant, hint; written: u_nom, x_nom0, xu_ss, x_nom, status, iters, region, tries).  They return without synchronising and
+ *   count in tmpc_debug_lane_counters, tmpc_last_kernel_ms and tmpc_kernel_ms_total.
+ * tmpc_law_get_stats(h, variant, R, hits): the number of regions and (hits [R] or NULL) the hit counters; waits for the lanes.
+ * tmpc_law_reorder(h, variant): sorts the search order by descending hits, ties by id; the ids stay.  Waits for the lanes.
+ * tmpc_law_clear(h, variant): empties the table and its counters.
+ * tmpc_law_get_region(h, variant, id, words, Ky, ky, S, s): the region as uploaded -- words [ceil(nc/32)], Ky [ny][2 nx], ky [ny],
+ *   S [nrow][2 nx], s [nrow] (tolerances folded in); any pointer may be NULL.  tmpc_get_param_rows(h, variant, gp0, Ep): the npar rows
+ *   0 <= gp0 + Ep x_k (npar from tmpc_get_dims; Ep [npar][nx]).  Both work on a host-only handle.
+ * tmpc_qp_law_eval(device, nv, nc, np, ny, H, F, G, g0, Ebar, Y, Yp, n_sets, words, n_order, order, B, P, hint, max_tries, out_y, region,
+ *   tries): the same kernel on raw condensed data without a handle (errors through tmpc_last_error(NULL)); HOST pointers.  The model as
+ *   for tmpc_qp_sensitivity, no parameter-only rows; words [n_sets][ceil(nc/32)], set i is region i (a refused set stays in the table as
+ *   a region that holds no p); order [n_order] ids; P [B][np]; out_y [B][ny] (NaN for a miss); hint and tries may be NULL.  Limits:
+ *   1 <= nv <= 128, 0 <= nc <= 2^20, 1 <= np <= 32, 1 <= ny <= 4096, n_sets and n_order <= 2^20.
+ *
+ * Refused before anything touches the device: NULL arguments or B < 0 (TMPC_E_INVALID); an open stepped session (TMPC_E_INVALID); a
+ * regulator handle (TMPC_E_UNSUPPORTED); a variant that keeps unpriced auxiliaries (TMPC_E_UNSUPPORTED); for the evaluating entries and
+ * tmpc_law_learn a host-only handle (TMPC_E_DEVICE).  Added without an ABI bump: new exports, nothing else changed.
+ */
+#define TMPC_LAW_FEAS_TOL 1e-10
+#define TMPC_LAW_MULT_TOL 1e-10
+int tmpc_law_add(tmpc_handle *h, int variant, int64_t n_sets, const uint32_t *words, int32_t *ids);
+int tmpc_law_learn(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom, const double *x_nom0,
+                   const double *xu_ss, const int32_t *status, double act_tol, int32_t *ids, int64_t *n_new);
+int tmpc_law_eval(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const int32_t *hint, int max_tries, double *u_nom,
+                  double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, int32_t *region, int32_t *tries);
+int tmpc_law_eval_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const int32_t *hint, int max_tries,
+                         double *u_nom, double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, int32_t *region, int32_t *tries);
+int tmpc_law_solve(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const int32_t *hint, int max_tries, double *u_nom,
+                   double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, int32_t *region, int32_t *tries);
+int tmpc_law_solve_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const int32_t *hint, int max_tries,
+                          double *u_nom, double *x_nom0, double *xu_ss, double *x_nom, int32_t *status, int32_t *iters, int32_t *region, int32_t *tries);
+int tmpc_law_get_stats(tmpc_handle *h, int variant, int32_t *R, int64_t *hits);
+int tmpc_law_reorder(tmpc_handle *h, int variant);
+int tmpc_law_clear(tmpc_handle *h, int variant);
+int tmpc_law_get_region(tmpc_handle *h, int variant, int32_t id, uint32_t *words, double *Ky, double *ky, double *S, double *s);
+int tmpc_get_param_rows(tmpc_handle *h, int variant, double *gp0, double *Ep);
+int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G, const double *g0,
+                     const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order, const int32_t *order,
+                     int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,12 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         out.update(_native.sens_jacobian(self._handle, xs, ref, out, variant=variant, act_tol=act_tol))
         return out
 
+    def explicit_law(self):
+        """The explicit law of this controller (explicit_law.ExplicitLaw): a table of critical regions on the handle, learnt from solved
+        instances and evaluated on the device in front of the solver (include/tmpc.h: tmpc_law_*)."""
+        from .explicit_law import ExplicitLaw
+        return ExplicitLaw(self)
+
     def _is_batched(self, x) -> bool:
         """(nx,) and the reference's column vector (nx,1) are single instances; (B,nx) is a batch."""
         return np.ndim(x) == 2 and np.shape(x) != (self._nx, 1)

@@ -207,6 +207,22 @@ def lib():
         L.tmpc_qp_sensitivity.argtypes = ([C.c_int] + [C.c_int32] * 4 + [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_double, C.c_int]
                                           + [C.c_void_p] * 5)
         L.tmpc_qp_sensitivity.restype = C.c_int
+        law = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8
+        for name in ("tmpc_law_eval", "tmpc_law_eval_device", "tmpc_law_solve", "tmpc_law_solve_device"):
+            getattr(L, name).argtypes = law
+            getattr(L, name).restype = C.c_int
+        L.tmpc_law_add.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+        L.tmpc_law_learn.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_double] + [C.c_void_p] * 2
+        L.tmpc_law_get_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tmpc_law_reorder.argtypes = [C.c_void_p, C.c_int]
+        L.tmpc_law_clear.argtypes = [C.c_void_p, C.c_int]
+        L.tmpc_law_get_region.argtypes = [C.c_void_p, C.c_int, C.c_int32] + [C.c_void_p] * 5
+        L.tmpc_get_param_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tmpc_qp_law_eval.argtypes = ([C.c_int] + [C.c_int32] * 4 + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                                                            C.c_void_p, C.c_int] + [C.c_void_p] * 3)
+        for name in ("tmpc_law_add", "tmpc_law_learn", "tmpc_law_get_stats", "tmpc_law_reorder", "tmpc_law_clear", "tmpc_law_get_region", "tmpc_get_param_rows",
+                     "tmpc_qp_law_eval"):
+            getattr(L, name).restype = C.c_int
         _lib = L
     return _lib
 
@@ -1304,4 +1320,129 @@ def qp_sensitivity(H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol: float =
                                    out["flag"].ctypes.data, out["n_active"].ctypes.data, out["active"].ctypes.data if nc else None)
     if rc != 0:
         _sens_fail("tmpc_qp_sensitivity", rc, lib().tmpc_last_error(None).decode())
+    return out
+
+
+# ---- the explicit control law (include/tmpc.h: tmpc_law_*, tmpc_qp_law_eval; csrc/tmpc_law.hip)
+LAW_FEAS_TOL, LAW_MULT_TOL = 1e-10, 1e-10      # include/tmpc.h: TMPC_LAW_*_TOL; csrc/tmpc_law.hpp
+
+
+def _law_check(name: str, rc: int, h: Handle = None):
+    if rc != 0:
+        _sens_fail(name, rc, h.error() if h is not None else lib().tmpc_last_error(None).decode())
+
+
+def get_param_rows(h: Handle, variant: int = 0) -> dict:
+    """include/tmpc.h: tmpc_get_param_rows -> gp0 (npar,), Ep (npar, nx): the rows 0 <= gp0 + Ep x_k."""
+    npar = get_dims(h, variant)[2]
+    out = dict(gp0=np.zeros(npar), Ep=np.zeros((npar, h.nx)))
+    _law_check("tmpc_get_param_rows", lib().tmpc_get_param_rows(h.ptr, int(variant), out["gp0"].ctypes.data, out["Ep"].ctypes.data), h)
+    return out
+
+
+def law_add(h: Handle, words, variant: int = 0):
+    """include/tmpc.h: tmpc_law_add -- words (n, ceil(nc / 32)) uint32 -> the region ids (n,), -1 for a refused set."""
+    nw = (get_dims(h, variant)[1] + 31) // 32
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32).reshape(-1, nw) if nw else np.zeros((len(words), 0), np.uint32))
+    ids = np.full(w.shape[0], -1, np.int32)
+    _law_check("tmpc_law_add", lib().tmpc_law_add(h.ptr, int(variant), w.shape[0], w.ctypes.data if w.size else ids.ctypes.data, ids.ctypes.data), h)
+    return ids
+
+
+def law_learn(h: Handle, x, ref, sol: dict, variant=None, act_tol: float = 0.0):
+    """include/tmpc.h: tmpc_law_learn -- the working sets of the solutions `sol` of a preceding solve -> (ids (B,), number of new regions)."""
+    B, x, ref, var, u, x0, ss, st = _sens_inputs(h, x, ref, variant, sol)
+    ids, n_new = np.full(B, -1, np.int32), C.c_int64(0)
+    rc = lib().tmpc_law_learn(h.ptr, B, x.ctypes.data, ref.ctypes.data, _ptr(var), u.ctypes.data, x0.ctypes.data, ss.ctypes.data, _ptr(st), float(act_tol),
+                              ids.ctypes.data, C.addressof(n_new))
+    _law_check("tmpc_law_learn", rc, h)
+    return ids, int(n_new.value)
+
+
+def _law_call(name: str, h: Handle, x, ref, variant, hint, max_tries: int, want_traj: bool) -> dict:
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, h.nx))
+    B, nx, nu, N = x.shape[0], h.nx, h.nu, h.N
+    ref = np.ascontiguousarray(np.broadcast_to(np.asarray(ref, dtype=np.float64).reshape(-1, nx), (B, nx)))
+    var = None if variant is None else np.ascontiguousarray(np.broadcast_to(np.asarray(variant, dtype=np.uint8).reshape(-1), (B,)))
+    hint = None if hint is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hint, dtype=np.int32).reshape(-1), (B,)))
+    out = dict(u_nom=np.empty((B, N, nu)), x_nom0=np.empty((B, nx)), xu_ss=np.empty((B, nx + nu)), x_nom=np.empty((B, N + 1, nx)) if want_traj else None,
+               status=np.empty(B, np.int32), iters=np.empty(B, np.int32), region=np.empty(B, np.int32), tries=np.empty(B, np.int32))
+    rc = getattr(lib(), name)(h.ptr, B, x.ctypes.data, ref.ctypes.data, _ptr(var), _ptr(hint), int(max_tries),
+                              *[_ptr(out[k]) for k in ("u_nom", "x_nom0", "xu_ss", "x_nom", "status", "iters", "region", "tries")])
+    _law_check(name, rc, h)
+    out["x_ss"], out["u_ss"] = out["xu_ss"][:, :nx], out["xu_ss"][:, nx:]
+    return out
+
+
+def law_eval(h: Handle, x, ref, variant=None, hint=None, max_tries: int = 0, want_traj: bool = True) -> dict:
+    """Host-pointer entry (tmpc_law_eval): the law kernel alone -> the outputs of solve_batch plus region, tries; a miss is NaN, status 3."""
+    return _law_call("tmpc_law_eval", h, x, ref, variant, hint, max_tries, want_traj)
+
+
+def law_solve(h: Handle, x, ref, variant=None, hint=None, max_tries: int = 0, want_traj: bool = True) -> dict:
+    """Host-pointer entry (tmpc_law_solve): the law, and the handle's solve for the misses, in one call."""
+    return _law_call("tmpc_law_solve", h, x, ref, variant, hint, max_tries, want_traj)
+
+
+def _law_device(name: str, h: Handle, B: int, ptrs):
+    x, r, var, hint, max_tries = ptrs[:5]
+    _law_check(name, getattr(lib(), name)(h.ptr, int(B), x, r, var, hint, int(max_tries), *ptrs[5:]), h)
+
+
+def law_eval_device(h: Handle, B: int, x_ptr, r_ptr, var_ptr, hint_ptr, max_tries, u_ptr, x0_ptr, ss_ptr, xn_ptr, st_ptr, it_ptr, region_ptr, tries_ptr):
+    """Device-pointer entry (tmpc_law_eval_device): raw addresses; returns without synchronising."""
+    _law_device("tmpc_law_eval_device", h, B, (x_ptr, r_ptr, var_ptr, hint_ptr, max_tries, u_ptr, x0_ptr, ss_ptr, xn_ptr, st_ptr, it_ptr, region_ptr, tries_ptr))
+
+
+def law_solve_device(h: Handle, B: int, x_ptr, r_ptr, var_ptr, hint_ptr, max_tries, u_ptr, x0_ptr, ss_ptr, xn_ptr, st_ptr, it_ptr, region_ptr, tries_ptr):
+    """Device-pointer entry (tmpc_law_solve_device): raw addresses; returns without synchronising."""
+    _law_device("tmpc_law_solve_device", h, B, (x_ptr, r_ptr, var_ptr, hint_ptr, max_tries, u_ptr, x0_ptr, ss_ptr, xn_ptr, st_ptr, it_ptr, region_ptr, tries_ptr))
+
+
+def law_stats(h: Handle, variant: int = 0):
+    """include/tmpc.h: tmpc_law_get_stats -> the hit counters (R,) int64."""
+    R = C.c_int32(0)
+    _law_check("tmpc_law_get_stats", lib().tmpc_law_get_stats(h.ptr, int(variant), C.addressof(R), None), h)
+    hits = np.zeros(R.value, np.int64)
+    if R.value:
+        _law_check("tmpc_law_get_stats", lib().tmpc_law_get_stats(h.ptr, int(variant), None, hits.ctypes.data), h)
+    return hits
+
+
+def law_reorder(h: Handle, variant: int = 0):
+    _law_check("tmpc_law_reorder", lib().tmpc_law_reorder(h.ptr, int(variant)), h)
+
+
+def law_clear(h: Handle, variant: int = 0):
+    _law_check("tmpc_law_clear", lib().tmpc_law_clear(h.ptr, int(variant)), h)
+
+
+def law_get_region(h: Handle, i: int, variant: int = 0) -> dict:
+    """include/tmpc.h: tmpc_law_get_region -> words, Ky (ny, 2nx), ky (ny,), S (nrow, 2nx), s (nrow,) as uploaded."""
+    _, nc, npar = get_dims(h, variant)
+    ny, npp, nrow = h.N * h.nu + 2 * h.nx + h.nu, 2 * h.nx, nc + npar
+    out = dict(words=np.zeros((nc + 31) // 32, np.uint32), Ky=np.zeros((ny, npp)), ky=np.zeros(ny), S=np.zeros((nrow, npp)), s=np.zeros(nrow))
+    rc = lib().tmpc_law_get_region(h.ptr, int(variant), int(i), *[_ptr(out[k]) for k in ("words", "Ky", "ky", "S", "s")])
+    _law_check("tmpc_law_get_region", rc, h)
+    return out
+
+
+def qp_law_eval(H, F, G, g0, Ebar, Y, Yp, words, order, P, hint=None, max_tries: int = 0, device: int = 0) -> dict:
+    """include/tmpc.h: tmpc_qp_law_eval -- the law kernel on raw condensed data, without a handle -> y (B, ny), region, tries; arguments as
+    LinearMPCOverNetworks.explicit_law.locate on a table of region_law(model, decode(words[i]))."""
+    H, F, G, g0, Ebar, Y, Yp = (_contiguous(a) for a in (H, F, G, g0, Ebar, Y, Yp))
+    nv, npar = F.shape
+    nc, ny = g0.shape[0], Y.shape[0]
+    nw = (nc + 31) // 32
+    words = np.ascontiguousarray(np.asarray(words, dtype=np.uint32).reshape(-1, nw) if nw else np.zeros((len(words), 0), np.uint32))
+    order = np.ascontiguousarray(np.asarray(order, dtype=np.int32).reshape(-1))
+    P = _contiguous(P).reshape(-1, npar)
+    B = P.shape[0]
+    hint = None if hint is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hint, dtype=np.int32).reshape(-1), (B,)))
+    out = dict(y=np.empty((B, ny)), region=np.empty(B, np.int32), tries=np.empty(B, np.int32))
+    rc = lib().tmpc_qp_law_eval(int(device), nv, nc, npar, ny, H.ctypes.data, F.ctypes.data, G.ctypes.data if nc else None, g0.ctypes.data if nc else None,
+                                Ebar.ctypes.data if nc else None, Y.ctypes.data, Yp.ctypes.data, words.shape[0], words.ctypes.data if words.size else None,
+                                order.shape[0], order.ctypes.data if order.size else None, B, P.ctypes.data, _ptr(hint), int(max_tries),
+                                out["y"].ctypes.data, out["region"].ctypes.data, out["tries"].ctypes.data)
+    _law_check("tmpc_qp_law_eval", rc)
     return out

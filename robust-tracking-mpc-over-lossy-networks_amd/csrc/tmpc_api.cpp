@@ -663,6 +663,13 @@ int enqueue(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const 
     { const int rce = begin_timed_launch(h, lane); if (rce) return rce; }
     if (io.variant != nullptr && !variants_valid)      // (the closed loop's selector is its own gamma flags: always 0 or 1)
         HIP_TRY(h, tmpc::launch_mark_invalid_variants(io, h->nvariants, h->nx, h->nu, h->N, lane.stream));
+    if (const int rc = enqueue_solves(h, lane, io, ws)) return rc;
+    HIP_TRY(h, hipEventRecord(h->ev1, lane.stream));
+    h->timed = true;
+    return TMPC_OK;
+}
+
+int enqueue_solves(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const *ws) {
     const int nvar = io.variant != nullptr ? h->nvariants : 1;        // (no per-instance selector: everything is variant 0)
     { const int rcs = prepare_wave_scratch(h, lane, io.B, nvar); if (rcs) return rcs; }
     for (int k = 0; k < nvar; ++k) {
@@ -675,8 +682,6 @@ int enqueue(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const 
         }
         HIP_TRY(h, tmpc::launch_solve(v.d, v.shape, k, io, ws ? ws[k] : nullptr, ws ? ws[k] : nullptr, &lane.wc, h->n_cu, lane.stream));
     }
-    HIP_TRY(h, hipEventRecord(h->ev1, lane.stream));
-    h->timed = true;
     return TMPC_OK;
 }
 
@@ -764,6 +769,7 @@ void tmpc_destroy(tmpc_handle *h) {
         if (l.stream) (void)hipStreamSynchronize(l.stream);
     release_session(h);                  // (an open stepped loop ends here: its arrays go with the arena below)
     release_sens(h);
+    release_law(h);
     for (Lane &l : h->lane) {
         for (DeviceBuffer *b : {&l.blk_ws, &l.save, &l.ticks}) b->release();
         if (l.wc.ring) (void)hipFree(l.wc.ring);

@@ -17,9 +17,10 @@ inline bool ranges_overlap(const ByteRange &a, const ByteRange &b) {
 }
 
 // What one call touches.  A solve call reads x_k, ref, variant and writes u_nom, x_nom0, xu_ss, x_nom, status, iters; a sensitivity call
-// (tmpc_sens.cpp) reads eight arrays and writes four.  Unused slots are empty ranges.
+// (tmpc_sens.cpp) reads eight arrays and writes four; an explicit-law call (tmpc_law.cpp) reads four and writes eight.  Unused slots are
+// empty ranges.
 struct CallRanges {
-    static constexpr int NR = 8, NW = 6;
+    static constexpr int NR = 8, NW = 8;
     ByteRange reads[NR], writes[NW];
     ByteRange hull;                      // covers every range above (empty: the call touches nothing)
 };

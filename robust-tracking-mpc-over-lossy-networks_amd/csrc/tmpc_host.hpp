@@ -184,6 +184,7 @@ struct LoopSettings {
     std::vector<double> pm;
     int series = 0;              // tmpc_mc_set_series: the tracking loops keep their per-step record
 };
+struct LawState;                 // the explicit law's tables (tmpc_law.cpp), created by the first tmpc_law_* call
 struct SensState;                // what the sensitivity entry points keep on the device (tmpc_sens.cpp), created by the first such call
 }  // namespace tmpc_host
 
@@ -232,6 +233,7 @@ struct tmpc_handle {
     tmpc_host::Arena arena;
     tmpc_host::LoopRecords rec;
     tmpc_host::McSession ses;
+    tmpc_host::LawState *law = nullptr;     // tmpc_law_*: nullptr until the first call
     tmpc_host::SensState *sens = nullptr;   // tmpc_sens_*: nullptr until the first call (a handle that never asks allocates nothing)
 };
 
@@ -262,6 +264,22 @@ int pick_call_lane(tmpc_handle *h, const tmpc::CallRanges &call, Lane **out);
 int note_call(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call);
 // (tmpc_sens.cpp) frees what the sensitivity calls allocated; the caller has synchronised
 void release_sens(tmpc_handle *h);
+// (tmpc_sens.cpp) what the sensitivity entries and the explicit law (tmpc_law.cpp) both build on: the Cholesky factor of a symmetric
+// matrix in place (false: not positive definite) and a solve with it, H^-1, and the model of a handle's variant beyond its condensed
+// form -- F = [F1 F2], Ebar = [E 0], y = Y z + Yp p, z = Rec [y | p]
+bool chol(std::vector<double> &a, int n);
+void chol_solve(const std::vector<double> &L, int n, double *x);
+std::string spd_inverse(const double *H, int n, std::vector<double> &Hinv);
+struct HostModel {
+    tmpc::Mat F, Eb, Y, Yp, Rec;
+};
+std::string host_model(const tmpc_handle *h, int k, HostModel &hm, int &rc);
+int sens_signatures(tmpc_handle *h, const char *who, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                    const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, int32_t *flag, int32_t *n_active, uint32_t *active);
+// (tmpc_law.cpp) frees what the explicit-law entries allocated; the caller has synchronised
+void release_law(tmpc_handle *h);
+// the solve launches of one call without its timing events: one per variant, `io.variant` the selector (tmpc_law.cpp runs them behind its own kernel)
+int enqueue_solves(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const *ws);
 // (tmpc_offline.cpp) cart-pole rows {M, m, b, I, g, l, Th} of n trajectories: empty, or the message naming trajectory and field
 std::string cartpole_rows_error(const char *who, const double *rows, int64_t n);
 }  // namespace tmpc_host

@@ -1,0 +1,64 @@
+// The explicit control law (tmpc_law.hip): what tmpc_law.cpp and the kernel share.  include/tmpc.h has the entry points (tmpc_law_*,
+// tmpc_qp_law_eval) and the meaning of a region.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace tmpc {
+
+// The limits of the sensitivity entries (tmpc_sens.hpp): a region is built from what they return
+constexpr int LAW_MAX_NV = 128, LAW_MAX_NP = 32, LAW_MAX_NY = 4096, LAW_MAX_NC = 1 << 20;
+constexpr int LAW_MAX_NX = LAW_MAX_NP / 2;       // a handle's p = [x_k | ref]
+
+// The acceptance thresholds (include/tmpc.h: TMPC_LAW_FEAS_TOL, TMPC_LAW_MULT_TOL), compile-time constants shared with the numpy twin
+// (LinearMPCOverNetworks/explicit_law.py).  A row of a region is accepted when its value is >= -tol; the host folds the tolerance
+// into the row's constant, so the kernel compares with zero.  Both are absolute, on the unscaled rows of tmpc_get_condensed, and a
+// tenth of the 1e-9 that the certificates of the solve's outputs allow on a primal residual and on a negative multiplier.
+constexpr double LAW_FEAS_TOL = 1e-10;   // primal slack of a row outside the working set, and the parameter-only rows
+constexpr double LAW_MULT_TOL = 1e-10;   // multiplier of a row of the working set
+
+constexpr double LAW_RANK_TOL = 1e-13;   // a working set is refused when a diagonal entry of M's Cholesky factor is <= LAW_RANK_TOL times the largest
+
+constexpr int LAW_WAVES = 4;             // instances per workgroup, one per wavefront
+constexpr int LAW_TODO_DONE = 0xFF;      // selector byte of an instance that needs no solve
+
+// The regions of one problem variant on the device.  Row i of region r is  sum_q S[r][q][i] p_q + S[r][np][i] >= 0.
+struct LawTable {
+    int nrow = 0;            // nc + npar
+    int nrowp = 0;           // nrow rounded up to 64; the padding rows are 0 p + 1
+    int R = 0;               // regions stored
+    int n_order = 0;         // length of the search order
+    const double *S = nullptr;        // [R][np + 1][nrowp]
+    const double *K = nullptr;        // [R][np + 1][ny]: y_j = sum_q K[r][q][j] p_q + K[r][np][j]
+    const int32_t *order = nullptr;   // [n_order] region ids
+    unsigned long long *hits = nullptr;       // [R] or NULL
+};
+
+// One launch over B instances.  All pointers are device pointers.
+struct LawArgs {
+    int np, ny, nvariants;
+    const LawTable *t;       // [nvariants], in device memory: the tables change between launches only, and the kernel reads the one of its instance
+    int64_t B;
+    int np0;                 // p = [P0[b][0..np0) | P1[b][0..np - np0)]
+    const double *P0, *P1;
+    const uint8_t *variant;  // or NULL
+    const int32_t *hint;     // or NULL
+    int max_tries;           // <= 0: all
+    int ny0, ny1;            // y = [Y0[b][0..ny0) | Y1[b][0..ny1) | Y2[b][0..ny - ny0 - ny1)]
+    double *Y0, *Y1, *Y2;
+    // the nominal trajectory x_{i+1} = A x_i + Bm u_i from x_0 = Y1[b] with u = Y0[b] (ny0 = N nu, ny1 = nx), or x_nom == NULL
+    double *x_nom;           // [B][N + 1][nx]
+    const double *A, *Bm;    // [nx][nx], [nx][nu]
+    int nx, nu, N;
+    int32_t *status;         // [B] or NULL
+    int32_t *iters;          // [B] or NULL
+    int32_t *region;         // [B]
+    int32_t *tries;          // [B] or NULL
+    uint8_t *todo;           // [B] or NULL: the variant id of a miss, LAW_TODO_DONE otherwise
+    int fallback;            // 1: a miss leaves y, x_nom, status and iters to the solve launches that follow
+};
+
+unsigned law_blocks(int64_t B, int n_cu);
+hipError_t launch_law(const LawArgs &a, unsigned blocks, hipStream_t stream);
+
+}  // namespace tmpc

@@ -33,12 +33,7 @@ void release_sens(tmpc_handle *h) {
     h->sens = nullptr;
 }
 
-}  // namespace tmpc_host
-
-namespace {
-
-using tmpc::Mat;
-
+// What the explicit law (tmpc_law.cpp) builds its regions with as well
 // In-place Cholesky factor (lower triangle) of the symmetric n x n matrix a; false when a pivot is not positive.
 bool chol(std::vector<double> &a, int n) {
     for (int j = 0; j < n; ++j) {
@@ -68,6 +63,34 @@ void chol_solve(const std::vector<double> &L, int n, double *x) {
         x[i] = s / L[static_cast<size_t>(i) * n + i];
     }
 }
+// H^-1 of the symmetric part of the n x n matrix H, symmetrised; "" or what is wrong with H
+std::string spd_inverse(const double *H, int n, std::vector<double> &Hinv) {
+    const size_t nv = n;
+    std::vector<double> L(H, H + nv * nv);
+    for (size_t i = 0; i < nv; ++i)
+        for (size_t j = 0; j < i; ++j) L[i * nv + j] = L[j * nv + i] = 0.5 * (H[i * nv + j] + H[j * nv + i]);
+    for (size_t i = 0; i < nv * nv; ++i)
+        if (!std::isfinite(H[i])) return "H has a non-finite entry";
+    if (!chol(L, n)) return "H is not positive definite";
+    Hinv.assign(nv * nv, 0.0);
+    std::vector<double> col(nv);
+    for (size_t j = 0; j < nv; ++j) {
+        std::fill(col.begin(), col.end(), 0.0);
+        col[j] = 1.0;
+        chol_solve(L, n, col.data());
+        for (size_t i = 0; i < nv; ++i) Hinv[i * nv + j] = col[i];
+    }
+    for (size_t i = 0; i < nv; ++i)
+        for (size_t j = 0; j < i; ++j) Hinv[i * nv + j] = Hinv[j * nv + i] = 0.5 * (Hinv[i * nv + j] + Hinv[j * nv + i]);
+    return std::string();
+}
+
+}  // namespace tmpc_host
+
+namespace {
+
+using tmpc::Mat;
+
 // (A'A)^-1 A' of a matrix with independent columns; false when they are not
 bool left_inverse(const Mat &A, Mat &out) {
     const int r = A.r, c = A.c;
@@ -98,22 +121,9 @@ struct RawModel {
 // Computes H^-1, W, H^-1 F and uploads everything as one block ("" on success, else the message; rc says which error)
 std::string upload_model(const RawModel &r, SensModel &m, int &rc) {
     const size_t nv = r.nv, nc = r.nc, np = r.np, ny = r.ny;
-    std::vector<double> L(r.H, r.H + nv * nv);
-    for (size_t i = 0; i < nv; ++i)
-        for (size_t j = 0; j < i; ++j) L[i * nv + j] = L[j * nv + i] = 0.5 * (r.H[i * nv + j] + r.H[j * nv + i]);
     rc = TMPC_E_INVALID;
-    for (size_t i = 0; i < nv * nv; ++i)
-        if (!std::isfinite(r.H[i])) return "H has a non-finite entry";
-    if (!chol(L, r.nv)) return "H is not positive definite";
-    std::vector<double> Hinv(nv * nv, 0.0), col(nv);
-    for (size_t j = 0; j < nv; ++j) {
-        std::fill(col.begin(), col.end(), 0.0);
-        col[j] = 1.0;
-        chol_solve(L, r.nv, col.data());
-        for (size_t i = 0; i < nv; ++i) Hinv[i * nv + j] = col[i];
-    }
-    for (size_t i = 0; i < nv; ++i)
-        for (size_t j = 0; j < i; ++j) Hinv[i * nv + j] = Hinv[j * nv + i] = 0.5 * (Hinv[i * nv + j] + Hinv[j * nv + i]);
+    std::vector<double> Hinv;
+    if (const std::string msg = spd_inverse(r.H, r.nv, Hinv); !msg.empty()) return msg;
     std::vector<double> W(nc * nv), HinvF(nv * np);
     for (size_t i = 0; i < nc; ++i)
         for (size_t j = 0; j < nv; ++j) {
@@ -177,11 +187,11 @@ unsigned sens_blocks(int64_t B, int n_cu, int nv, int np) {
     return static_cast<unsigned>(std::clamp<int64_t>(B, 1, per_cu * std::max(n_cu, 1)));
 }
 
+}  // namespace
+
 // The model of variant k of a handle from its condensed form: F = [F1 F2], Ebar = [E 0], the output map and the map back from the outputs
-struct HostModel {
-    Mat F, Eb, Y, Yp, Rec;
-};
-std::string host_model(const tmpc_handle *h, int k, HostModel &hm, int &rc) {
+// (HostModel: tmpc_host.hpp)
+std::string tmpc_host::host_model(const tmpc_handle *h, int k, HostModel &hm, int &rc) {
     const tmpc::Condensed &c = h->v[k].c;
     const int nx = c.nx, nu = c.nu, N = c.N, nv = c.nv, nc = c.nc, nvf = c.nvf, nth = c.nth, np = 2 * nx, ny = N * nu + 2 * nx + nu;
     rc = TMPC_E_UNSUPPORTED;
@@ -237,6 +247,9 @@ std::string host_model(const tmpc_handle *h, int k, HostModel &hm, int &rc) {
     rc = TMPC_OK;
     return std::string();
 }
+
+namespace {
+
 std::string handle_model(tmpc_handle *h, int k, int &rc) {
     HostModel hm;
     if (const std::string msg = host_model(h, k, hm, rc); !msg.empty()) return msg;
@@ -408,6 +421,14 @@ int call_host(tmpc_handle *h, const char *who, const SensCall &c) {
 }
 
 }  // namespace
+
+// The region signatures of a solved batch for tmpc_law_learn: the sensitivity kernel in its one-column mode with a zero ybar (HOST pointers)
+int tmpc_host::sens_signatures(tmpc_handle *h, const char *who, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                               const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, int32_t *flag, int32_t *n_active, uint32_t *active) {
+    const size_t b = static_cast<size_t>(std::max<int64_t>(B, 0)), nx = h ? h->nx : 0, ny = h ? h->N * h->nu + 2 * h->nx + h->nu : 0;
+    std::vector<double> ybar(b * ny, 0.0), pbar(b * 2 * nx + 1);
+    return call_host(h, who, {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, tmpc::SENS_MODE_VJP, ybar.data(), pbar.data(), flag, n_active, active});
+}
 
 extern "C" {
 
