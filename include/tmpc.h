@@ -1012,6 +1012,38 @@ int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny,
                      const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order, const int32_t *order,
                      int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries);
 
+/*
+ * The closed loops through the explicit law.  A trajectory returns to the same few regions step after step, and inside a loop the law has
+ * the hint that makes it cheap: the region of the step before.
+ *
+ * tmpc_mc_set_law: with on != 0 the following tmpc_mc_run, tmpc_mc_run_plants and tmpc_mc_open look [x_hat | ref_k] of every trajectory up
+ * in the handle's table (of the problem the step would solve) before each solve, and solve the misses only.  The hint of trajectory b at
+ * step t is its region at step t-1; -1 at t = 0 and after a miss.  At most max_tries candidates are tried per step, the hint included
+ * (<= 0: all).  The table is the handle's at the start of the run; a session honours the setting as it was at open.  A hit writes what
+ * tmpc_law_eval writes -- u_nom, x_nom0, xu_ss, status TMPC_STATUS_OPTIMAL, iters 0 -- which the state machines read as after a solve,
+ * counts in the region's hit counter (tmpc_law_get_stats), and with warm start on leaves the trajectory's working-set record as it is.
+ * A trajectory that has stopped is passed over.  tmpc_mc_run with one problem on the one-wave-per-QP kernel still takes one launch for the
+ * sweep by the TMPC_MC_FUSED_* rule (tmpc_mc_last_fused: 1) where the problem's kernel shape has a factored block (the cart-pole's
+ * shapes); every other loop takes per step the law's launch, the solve launches of the misses and the state-machine launch -- the extended
+ * controller too (tmpc_mc_last_fused: 0).  Both forms give the same bytes.
+ * miss_capacity >= 0: the rows of the miss log.  Works on a host-only handle, where it only stores the setting.  TMPC_E_INVALID while a
+ * session is open and for miss_capacity < 0; TMPC_E_UNSUPPORTED on a regulator handle -- and, reported by the run, for a problem that
+ * keeps the unpriced auxiliaries of the literal terminal row.  tmpc_mc_replay and tmpc_reg_run ignore the setting.  With the law off
+ * every loop is what it was.
+ *
+ * tmpc_mc_get_law_stats: per trajectory of the last such loop, or of the session tmpc_mc_close just ended: the steps answered from the
+ * table, the candidates tested in total, and the region of the last step taken (-1: a miss).  Any of the three may be NULL.
+ * TMPC_E_INVALID where there is no such loop, the law was off, or B differs.
+ *
+ * tmpc_mc_get_law_misses: the log of the same loop -- [x_hat | ref_k] (x_k [.][nx], ref [.][nx]) and problem id of the steps that missed,
+ * exactly as the law read them, appended on the device through one counter.  The log keeps the first miss_capacity entries drawn and the
+ * counter goes on counting: *n_total is the number of misses of the run, and min(n_total, miss_capacity, capacity) rows come back.  The
+ * order of the rows is not defined.  Solved and handed to tmpc_law_learn, the log of a pilot sweep is the table of the sweep that follows.
+ */
+int tmpc_mc_set_law(tmpc_handle *h, int on, int max_tries, int64_t miss_capacity);
+int tmpc_mc_get_law_stats(tmpc_handle *h, int64_t B, int32_t *hits, int64_t *tries, int32_t *region_last);
+int tmpc_mc_get_law_misses(tmpc_handle *h, int64_t capacity, int64_t *n_total, double *x_k, double *ref, uint8_t *variant);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,7 +231,7 @@ class TubeTrackingMPC(TubeRegulatorMPC):
 
     def open_closed_loop(self, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, extended: bool = False, X=None, U=None,
                          warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None,
-                         channel=None, series: bool = False) -> "ClosedLoopSession":
+                         channel=None, series: bool = False, law=None) -> "ClosedLoopSession":
         """The closed loop of run_closed_loop around a plant of the CALLER's, one time step per call (include/tmpc.h:
         tmpc_mc_open): `with mpc.open_closed_loop(...) as s: u = s.step(x) ...; stats = s.stats`.  The session runs the same
         state machines and solves on the device; the caller gives x_t and gets the applied u_t back.  th_u / ga_u (B, T): the
@@ -241,18 +241,19 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         ref: (T,) position reference, or a full-state form -- (T, nx), (B, T, nx), (K, T, nx) with ref_id (B,), or (nx,) together
         with T (see run_closed_loop); such a session also takes step(x, ref_next): the reference of the next solve, online.
         channel: the Gilbert-Elliott loss channel of the session (see run_closed_loop; p_loss may then be None).
-        series: the session keeps its per-step record (see run_closed_loop); the rows of steps not taken are zero."""
+        series: the session keeps its per-step record (see run_closed_loop); the rows of steps not taken are zero.
+        law: the session's steps go through the explicit law (see run_closed_loop)."""
         from . import _native
         if self._handle is None:
             raise RuntimeError("setup_optimization() has not been called")
         _native.mc_set_actuator(self._handle, self._smart_actuator)
         info = _native.mc_open(self._handle, p_loss, ref, th_u, ga_u, x0=x0, T=T, Z=None if self._smart_actuator else self._Z,
                                X=X, U=U, extended=extended, warm_start=warm_start, capture=capture, timing=timing,
-                               device_rng=device_rng, ref_id=ref_id, channel=channel, series=series)
+                               device_rng=device_rng, ref_id=ref_id, channel=channel, series=series, law=law)
         return ClosedLoopSession(self, info)
 
     def _run_closed_loop_around(self, plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng,
-                                ref_id=None, T=None, channel=None, series=False):
+                                ref_id=None, T=None, channel=None, series=False, law=None):
         """run_closed_loop(plant=callable): a session driven by plant(x, u) -> x_plus on device tensors, + w[:, t] as the host loop adds it."""
         import torch
         dev = torch.device("cuda", self._device)
@@ -268,7 +269,7 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         wd = None if w is None else torch.as_tensor(np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(B, T, nx).transpose(1, 0, 2)), device=dev)
         with torch.cuda.device(dev):
             with self.open_closed_loop(p_loss, ref, th_u, ga_u, x0=x0, T=T, extended=extended, warm_start=warm_start, capture=capture,
-                                       timing=timing, device_rng=device_rng, ref_id=ref_id, channel=channel, series=series) as s:
+                                       timing=timing, device_rng=device_rng, ref_id=ref_id, channel=channel, series=series, law=law) as s:
                 for t in range(T):
                     xp = plant(x, s.step(x))
                     x = (xp if wd is None else xp + wd[t]).contiguous()
@@ -278,7 +279,7 @@ class TubeTrackingMPC(TubeRegulatorMPC):
 
     def run_closed_loop(self, p_loss, ref, th_u=None, ga_u=None, w=None, x0=None, extended: bool = False, plant=None,
                         warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, fused=None, ref_id=None,
-                        T=None, channel=None, series: bool = False) -> dict:
+                        T=None, channel=None, series: bool = False, law=None) -> dict:
         """The lossy-network closed loop of the reference's Monte-Carlo scripts (results_linear_system.py:209-291)
         for a batch of trajectories, resident on the device (include/tmpc.h: tmpc_mc_run): ONE launch for the whole sweep
         where the controller has one QP (a wavefront keeps its trajectory for all T steps: solve, state machines, solve, ...;
@@ -306,7 +307,11 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         series: keep what happens in time (tmpc_mc_set_series) -> out["series"], (T, B) arrays: e, the tracking-error term of every step
         (its sum over t is err2), and per step the flags alive, lost_up, lost_down, adopted, tube, not_optimal, overrun, the solve's
         iters and the age t - s_t of the played sequence; _native.mc_series_stats(handle, group, q) then gives the ensemble's counts,
-        sums, maxima and exact quantiles per time step and group on the device.  A recording loop runs per time step (loop_mode 0)."""
+        sums, maxima and exact quantiles per time step and group on the device.  A recording loop runs per time step (loop_mode 0).
+        law: None -- every step is solved; True, an int (max_tries) or dict(max_tries=, miss_capacity=) -- every step is first looked up in
+        the table of explicit_law() with the trajectory's last region as the hint, and only the misses are solved (tmpc_mc_set_law; one
+        launch for the sweep as without it).  The result gains law_hits, law_tries, law_region (B,) and law_misses(), which fetches the log
+        of the states that missed: explicit_law().learn_from_misses(out) turns a pilot sweep into the table of the next one."""
         from . import _native
         if self._handle is None:
             raise RuntimeError("setup_optimization() has not been called")
@@ -315,13 +320,13 @@ class TubeTrackingMPC(TubeRegulatorMPC):
             _native.mc_set_actuator(self._handle, self._smart_actuator)
             out = _native.mc_run_plants(self._handle, plant, p_loss, ref, th_u, ga_u, w, x0=x0, Z=None if self._smart_actuator else self._Z,
                                         extended=extended, warm_start=warm_start, capture=capture, timing=timing, device_rng=device_rng,
-                                        ref_id=ref_id, T=T, channel=channel, series=series)
+                                        ref_id=ref_id, T=T, channel=channel, series=series, law=law)
             if timing:
                 self._computational_times.extend(out["solve_time_mean"].tolist())
             return out
         if callable(plant):
             out = self._run_closed_loop_around(plant, p_loss, ref, th_u, ga_u, w, x0, extended, warm_start, capture, timing, device_rng,
-                                               ref_id=ref_id, T=T, channel=channel, series=series)
+                                               ref_id=ref_id, T=T, channel=channel, series=series, law=law)
             if timing:
                 self._computational_times.extend(out["solve_time_mean"].tolist())
             return out
@@ -330,7 +335,7 @@ class TubeTrackingMPC(TubeRegulatorMPC):
         out = _native.mc_run(self._handle, p_loss, ref, th_u, ga_u, w, x0=x0, Z=None if self._smart_actuator else self._Z,
                              extended=extended, warm_start=warm_start, capture=capture, timing=timing,
                              physics_substeps=0 if plant in (None, "linear") else 10, device_rng=device_rng, fused=fused,
-                             ref_id=ref_id, T=T, channel=channel, series=series)
+                             ref_id=ref_id, T=T, channel=channel, series=series, law=law)
         if timing:
             self._computational_times.extend(out["solve_time_mean"].tolist())
         return out

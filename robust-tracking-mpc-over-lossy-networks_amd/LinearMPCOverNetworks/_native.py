@@ -141,6 +141,11 @@ def lib():
         L.tmpc_mc_get_link_stats.restype = C.c_int
         L.tmpc_mc_set_series.argtypes = [C.c_void_p, C.c_int]
         L.tmpc_mc_set_series.restype = C.c_int
+        L.tmpc_mc_set_law.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64]
+        L.tmpc_mc_get_law_stats.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmpc_mc_get_law_misses.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("tmpc_mc_set_law", "tmpc_mc_get_law_stats", "tmpc_mc_get_law_misses"):
+            getattr(L, name).restype = C.c_int
         L.tmpc_mc_get_series.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.tmpc_mc_get_series.restype = C.c_int
         L.tmpc_mc_series_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_void_p] * 16
@@ -734,7 +739,47 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
-def _set_loop_options(h: Handle, timing, warm_start, capture, fused="keep", series: bool = False):
+def _law_setting(law):
+    """(on, max_tries, miss_capacity) of the `law` argument of mc_run / mc_run_plants / mc_open: None or False -- off; True -- every
+    candidate, no miss log; an int -- max_tries; a dict with max_tries (default 0: all) and miss_capacity (default 0)."""
+    if law is None or law is False:
+        return 0, 0, 0
+    if law is True:
+        return 1, 0, 0
+    if isinstance(law, dict):
+        extra = set(law) - {"max_tries", "miss_capacity"}
+        if extra:
+            raise ValueError(f"law: unknown keys {sorted(extra)} (max_tries, miss_capacity)")
+        return 1, int(law.get("max_tries", 0)), int(law.get("miss_capacity", 0))
+    return 1, int(law), 0
+
+
+def mc_law_stats(h: Handle, B: int) -> dict:
+    """include/tmpc.h: tmpc_mc_get_law_stats -- per trajectory of the last loop run through the explicit law: hits (B,) int32, tries (B,)
+    int64, region (B,) int32 (the region of the last step taken, -1: a miss)."""
+    out = dict(hits=np.empty(B, np.int32), tries=np.empty(B, np.int64), region=np.empty(B, np.int32))
+    if lib().tmpc_mc_get_law_stats(h.ptr, B, out["hits"].ctypes.data, out["tries"].ctypes.data, out["region"].ctypes.data) != 0:
+        raise RuntimeError(h.error())
+    return out
+
+
+def mc_law_misses(h: Handle, capacity=None) -> dict:
+    """include/tmpc.h: tmpc_mc_get_law_misses -- the miss log of the last loop run through the explicit law: n_total (the misses of the
+    run), x_k (n, nx), ref (n, nx), variant (n,) uint8 of the n = min(n_total, miss_capacity, capacity) rows kept (capacity None: all
+    that were kept).  The order of the rows is not defined."""
+    n_total = C.c_int64(0)
+    if lib().tmpc_mc_get_law_misses(h.ptr, 0, C.addressof(n_total), None, None, None) != 0:
+        raise RuntimeError(h.error())
+    n = min(int(n_total.value), int(getattr(h, "law_miss_capacity", 0)))
+    if capacity is not None:
+        n = min(n, int(capacity))
+    x, r, v = np.empty((n, h.nx)), np.empty((n, h.nx)), np.empty(n, np.uint8)
+    if n and lib().tmpc_mc_get_law_misses(h.ptr, n, None, x.ctypes.data, r.ctypes.data, v.ctypes.data) != 0:
+        raise RuntimeError(h.error())
+    return dict(n_total=int(n_total.value), x_k=x, ref=r, variant=v)
+
+
+def _set_loop_options(h: Handle, timing, warm_start, capture, fused="keep", series: bool = False, law=None):
     """The per-call settings of a tracking loop (mc_run, mc_open): tmpc_set_solve_timing, tmpc_mc_set_warm_start, tmpc_mc_set_capture,
     tmpc_mc_set_series and -- mc_run; a session has one launch form and leaves the setting alone -- tmpc_mc_set_fused.  THE place where
     a new per-call loop option is set."""
@@ -745,6 +790,10 @@ def _set_loop_options(h: Handle, timing, warm_start, capture, fused="keep", seri
     for call, arg in calls:
         if call(h.ptr, arg) != 0:
             raise RuntimeError(h.error())
+    on, max_tries, miss_capacity = _law_setting(law)
+    if lib().tmpc_mc_set_law(h.ptr, on, max_tries, miss_capacity) != 0:
+        raise RuntimeError(h.error())
+    h.law_miss_capacity = miss_capacity      # (mc_law_misses: how many rows the loop's log can hold)
 
 
 def _set_device_rng(h: Handle, device_rng=None, draws_w: bool = True):
@@ -769,7 +818,7 @@ def _check_set(P, dim: int, who: str):
     return HA, hb, HA.shape[0]
 
 
-def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode: int, capture, timing, series: bool = False) -> dict:
+def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode: int, capture, timing, series: bool = False, law=None) -> dict:
     """Completes the result of a tracking loop (mc_run, mc_close) over the `steps` steps taken of T: the recorded trajectory, the
     solve times, the link statistics and the derived statistics.  THE place where a new loop output is fetched."""
     n = steps
@@ -788,6 +837,10 @@ def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode
     h.series_shape = (B, T) if series else None
     if series:
         out["series"] = mc_get_series(h, B, T)       # (T, B) arrays; rows of steps a session did not take are zero
+    if _law_setting(law)[0]:
+        st = mc_law_stats(h, B)
+        out["law_hits"], out["law_tries"], out["law_region"] = st["hits"], st["tries"], st["region"]
+        out["law_misses"] = lambda capacity=None: mc_law_misses(h, capacity)      # (valid until the handle's next loop)
     out["loop_mode"] = loop_mode      # 1: one launch per sweep; 2: one launch per problem and step; 0: solve launches + a state-machine launch per step
     out["fused"] = loop_mode == 1
     out["tracking_error"] = np.sqrt(out["err2"]) / max(n, 1)
@@ -798,7 +851,7 @@ def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode
 
 def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: bool = False, warm_start: bool = False,
            capture=None, timing: bool = False, physics_substeps: int = 0, device_rng=None, fused=None, ref_id=None, T=None,
-           channel=None, series: bool = False) -> dict:
+           channel=None, series: bool = False, law=None) -> dict:
     """include/tmpc.h: tmpc_mc_run -- the closed loop over the lossy network, resident on the device.
     warm_start: tmpc_mc_set_warm_start for this call; capture: index of a trajectory to record (tmpc_mc_set_capture) ->
     x_traj (T, nx), x_nom_traj (T, nx), u_traj (T, nu) in the result; timing: per trajectory the mean and the maximum
@@ -819,8 +872,11 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     lost_down, max_gap, overrun (also as the dict link_stats) with either loss model.
     series: keep the per-step record (tmpc_mc_set_series) -> result["series"], a dict of (T, B) arrays: e, the error term of every
     step, word, and the word's fields alive, lost_up, lost_down, adopted, tube, not_optimal, overrun, iters, age; mc_series_stats then
-    reduces it on the device.  Such a loop runs per time step (loop_mode 0, whatever `fused` says)."""
-    _set_loop_options(h, timing, warm_start, capture, fused, series)
+    reduces it on the device.  Such a loop runs per time step (loop_mode 0, whatever `fused` says).
+    law: the loop looks every step up in the handle's explicit-law table first and solves the misses only (tmpc_mc_set_law) -- True, an
+    int (max_tries) or a dict(max_tries=, miss_capacity=); the result gains law_hits, law_tries, law_region (B,) and law_misses(), a
+    function that fetches the miss log (mc_law_misses)."""
+    _set_loop_options(h, timing, warm_start, capture, fused, series, law)
     c, ptr = _contiguous, _ptr
     p_loss, ch_par, n_traj = loop_batch("mc_run", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if T is None and device_rng is None and th_u is not None:
@@ -855,7 +911,7 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
         if lib().tmpc_mc_get_physics_error(h.ptr, B, ptr(out["err2_physics"])) != 0:
             raise RuntimeError(h.error())
         out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * physics_substeps)
-    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing, series)
+    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing, series, law)
 
 
 def _family_models(who: str, plant, nx: int, nu: int, B=None):
@@ -910,12 +966,12 @@ def plant_step(plant, x, u, w=None, x_plus=None, stream=None):
 
 def mc_run_plants(h: Handle, plant, p_loss, ref, th_u=None, ga_u=None, w=None, x0=None, Z=None, X=None, U=None, extended: bool = False,
                   warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, T=None, channel=None,
-                  series: bool = False) -> dict:
+                  series: bool = False, law=None) -> dict:
     """include/tmpc.h: tmpc_mc_run_plants -- the closed loop of mc_run with a plant per trajectory: `plant` is a montecarlo.PlantFamily of
     B plants, cart-poles or linear models; the stepped session and the plant kernel alternate on the device for T steps.  The arguments
     are mc_run's (`fused` does not apply) plus the check sets X, U of mc_open; the result has mc_run's keys -- with
-    tracking_error_physics for a cart-pole family -- plus x_violations and u_violations.  series: as in mc_run."""
-    _set_loop_options(h, timing, warm_start, capture, series=series)
+    tracking_error_physics for a cart-pole family -- plus x_violations and u_violations.  series, law: as in mc_run."""
+    _set_loop_options(h, timing, warm_start, capture, series=series, law=law)
     c, ptr = _contiguous, _ptr
     p_loss, ch_par, n_traj = loop_batch("mc_run_plants", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
     if T is None and device_rng is None and th_u is not None:
@@ -951,18 +1007,19 @@ def mc_run_plants(h: Handle, plant, p_loss, ref, th_u=None, ga_u=None, w=None, x
         raise RuntimeError(f"tmpc_mc_run_plants failed ({rc}): {msg}")
     if cart:
         out["tracking_error_physics"] = np.sqrt(out["err2_physics"]) / (T * substeps)
-    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing, series)
+    return _tracking_result(h, out, B, T, T, int(lib().tmpc_mc_last_fused(h.ptr)), capture, timing, series, law)
 
 
 def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=None, X=None, U=None, extended: bool = False,
             warm_start: bool = False, capture=None, timing: bool = False, device_rng=None, ref_id=None, channel=None,
-            series: bool = False) -> dict:
+            series: bool = False, law=None) -> dict:
     """include/tmpc.h: tmpc_mc_open -- opens the stepped closed loop around a plant of the caller's.  p_loss (B,), ref (T,)
     or a full-state form (mc_run; (nx,) together with T: a constant full state -- the table of a session steered by ref_next),
     th_u / ga_u (B, T) loss uniforms (None with device_rng = (seed, first_trajectory[, ignored]): Philox block 0, the draws of
     mc_run), x0 (B, nx) or None; T: steps the session may take (default: len(ref)); Z / X / U: tube cross-section and the check
     sets for x_t / u_t (polytopes or None).  No disturbance is drawn: w is the plant's.  channel: the Gilbert-Elliott loss channel of
     the session (mc_run; p_loss may then be None).  series: the session keeps its per-step record (mc_run), which mc_close returns.
+    law: the session's steps go through the explicit law (mc_run); mc_close returns its counters and miss log.
     Returns what mc_close needs."""
     c, ptr = _contiguous, _ptr
     p_loss, ch_par, B = loop_batch("mc_open", p_loss, channel, None if device_rng is not None else th_u, x0, ref_id, h.nx)
@@ -973,7 +1030,7 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
     T = T_ref if T is None else int(T)
     if (ref.shape[0] if ref is not None else T_ref) < T:
         raise ValueError("mc_open: ref must cover the T steps of the session")
-    _set_loop_options(h, timing, warm_start, capture, series=series)
+    _set_loop_options(h, timing, warm_start, capture, series=series, law=law)
     _set_device_rng(h, device_rng, draws_w=False)
     if device_rng is not None:
         th_u = ga_u = None
@@ -992,7 +1049,7 @@ def mc_open(h: Handle, p_loss, ref, th_u=None, ga_u=None, x0=None, T=None, Z=Non
         msg = h.error()
         mc_set_channel(h, None)          # (no session was opened: the setter is free)
         raise RuntimeError(f"tmpc_mc_open failed ({rc}): {msg}")
-    return dict(B=B, T=T, capture=capture, timing=bool(timing), full_ref=ref is None, series=bool(series))
+    return dict(B=B, T=T, capture=capture, timing=bool(timing), full_ref=ref is None, series=bool(series), law=law)
 
 
 def mc_step(h: Handle, info: dict, x, u=None, stream=None, ref_next=None):
@@ -1046,7 +1103,7 @@ def mc_close(h: Handle, info: dict) -> dict:
     if rc != 0:
         raise RuntimeError(f"tmpc_mc_close failed ({rc}): {h.error()}")
     out["steps"] = int(steps.value)
-    return _tracking_result(h, out, B, T, out["steps"], 0, info.get("capture"), info.get("timing"), info.get("series", False))
+    return _tracking_result(h, out, B, T, out["steps"], 0, info.get("capture"), info.get("timing"), info.get("series", False), info.get("law"))
 
 
 def reg_run(h: Handle, x0, T: int, w=None, device_rng=None, X=None, U=None, Z=None, capture=None, plant=None) -> dict:

@@ -145,6 +145,15 @@ class ExplicitLaw:
         xs = np.asarray(x, dtype=np.float64).reshape(-1, self._h.nx)
         return _native.law_learn(self._h, xs, ref, out, variant=variant, act_tol=act_tol)
 
+    def learn_from_misses(self, result, act_tol: float = 0.0):
+        """The regions of the steps a closed loop through the law missed (run_closed_loop(law=dict(miss_capacity=..)): `result` is what
+        it returned, or the dict of _native.mc_law_misses): solves the logged [x_hat | ref_k] and learns them -> (ids, number of new
+        regions).  A pilot sweep with an empty table and a full log, then this, is the table of the sweep that follows."""
+        m = result["law_misses"]() if "law_misses" in result else result
+        if len(m["x_k"]) == 0:
+            return np.zeros(0, np.int32), 0
+        return self.learn(m["x_k"], m["ref"], variant=m["variant"] if self._h.nvariants > 1 else None, act_tol=act_tol)
+
     def add(self, words, variant: int = 0):
         """Adds working sets given as bit words (sensitivity's `active`) -> ids."""
         from . import _native

@@ -337,6 +337,102 @@ class _LinkStats:
         return dict(lost_up=self.lost_up, lost_down=self.lost_down, max_gap=self.max_gap, overrun=self.overrun)
 
 
+class LawPackets:
+    """The host twin of the device loops through the explicit law (include/tmpc.h: tmpc_mc_set_law): a `packets_fn` for
+    run_remote_tube_mpc that looks every step up in a table of critical regions first -- the trajectory's region of the step before as
+    the hint, -1 at t = 0 and after a miss -- and hands only the misses to `packets_fn` (normally TubeTrackingMPC.determine_packets, or
+    an oracle's).  It keeps the device's bookkeeping: hits (B,), tries (B,), region (B,) of the last step, the hit counters per region,
+    the miss log (the first miss_capacity [x_hat | ref] and variant ids) and n_total.
+
+    lookup(k, P (n, 2 nx), hint (n,), max_tries) -> (region (n,), tries (n,), y (n, ny)) for the instances of problem k, y = [u_nom
+    (N nu) | x_nom0 (nx) | x_ss (nx) | u_ss (nu)]: `from_tables` builds one from numpy tables (explicit_law.region_law / locate, no
+    GPU), `from_law` from an ExplicitLaw on the device.  K: the steady-state gain of the packet's last column u_ss + K x_ss."""
+
+    def __init__(self, packets_fn, lookup, K, N: int, max_tries: int = 0, miss_capacity: int = 0):
+        self._fn, self._lookup, self._K, self._N = packets_fn, lookup, np.atleast_2d(np.asarray(K, dtype=np.float64)), int(N)
+        self.max_tries, self.miss_capacity = int(max_tries), int(miss_capacity)
+        self.hits = self.tries = self.region = None
+        self.region_hits = [{}, {}]
+        self.steps = 0               # instances seen: hits + misses
+        self.n_total, self.miss_x, self.miss_ref, self.miss_variant = 0, [], [], []
+
+    @classmethod
+    def from_tables(cls, packets_fn, tables, K, N, orders=None, **kw):
+        """tables: one list of explicit_law.region_law dicts per problem (a single list: problem 0)."""
+        from .explicit_law import locate
+        if len(tables) == 0 or isinstance(tables[0], dict) or tables[0] is None:
+            tables = [tables]
+        orders = [None] * len(tables) if orders is None else orders
+
+        def lookup(k, P, hint, max_tries):
+            return locate(tables[k], P, hint, orders[k], max_tries)
+        return cls(packets_fn, lookup, K, N, **kw)
+
+    @classmethod
+    def from_law(cls, mpc, law=None, **kw):
+        """The table of `law` (default mpc.explicit_law()) on the device, the solver of `mpc` behind it."""
+        law = mpc.explicit_law() if law is None else law
+        nx = mpc._nx
+
+        def lookup(k, P, hint, max_tries):
+            out = law.evaluate(P[:, :nx], P[:, nx:], variant=None if mpc._handle.nvariants == 1 else np.full(len(P), k, np.uint8),
+                               hint=hint, max_tries=max_tries, want_traj=False)
+            y = np.c_[out["u_nom"].reshape(len(P), -1), out["x_nom0"], out["x_ss"], out["u_ss"]]
+            return out["region"], out["tries"], y
+        return cls(mpc.determine_packets, lookup, mpc.get_steady_state_controller_gain(), mpc._N, **kw)
+
+    def __call__(self, x_hat, ref, gamma=None):
+        x_hat, ref = np.asarray(x_hat, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+        nb, nx = x_hat.shape
+        nu, N = self._K.shape[0], self._N
+        if self.hits is None:
+            self.hits, self.tries, self.region = np.zeros(nb, np.int32), np.zeros(nb, np.int64), np.full(nb, -1, np.int32)
+        var = np.zeros(nb, np.uint8) if gamma is None else np.asarray(gamma, dtype=np.uint8)
+        P = np.c_[x_hat, ref]
+        region, y = np.full(nb, -1, np.int32), np.full((nb, N * nu + 2 * nx + nu), np.nan)
+        for k in np.unique(var):
+            sel = np.flatnonzero(var == k)
+            reg, tries, yk = self._lookup(int(k), P[sel], self.region[sel], self.max_tries)
+            region[sel] = reg
+            self.tries[sel] += tries
+            if yk.shape[1] == y.shape[1]:            # (an empty table has no rows of y)
+                y[sel] = yk
+            for r in reg[reg >= 0]:
+                self.region_hits[int(k)][int(r)] = self.region_hits[int(k)].get(int(r), 0) + 1
+        hit = region >= 0
+        self.region = region
+        self.hits += hit
+        self.steps += nb
+        U = np.empty((nb, nu, N + 1))
+        x_nom0, status, iters = np.empty((nb, nx)), np.zeros(nb, np.int32), np.zeros(nb, np.int32)
+        if hit.any():
+            yh = y[hit]
+            u_nom, x_ss, u_ss = yh[:, :N * nu].reshape(-1, N, nu), yh[:, N * nu + nx:N * nu + 2 * nx], yh[:, N * nu + 2 * nx:]
+            U[hit] = np.concatenate([u_nom, (u_ss + x_ss @ self._K.T)[:, None, :]], axis=1).transpose(0, 2, 1)
+            x_nom0[hit] = yh[:, N * nu:N * nu + nx]
+        miss = np.flatnonzero(~hit)
+        if len(miss):
+            for b in miss:
+                if self.n_total < self.miss_capacity:
+                    self.miss_x.append(x_hat[b].copy())
+                    self.miss_ref.append(ref[b].copy())
+                    self.miss_variant.append(int(var[b]))
+                self.n_total += 1
+            res = self._fn(x_hat[miss], ref[miss]) if gamma is None else self._fn(x_hat[miss], ref[miss], var[miss])
+            Um, xm, sm, im = _packets(res)
+            U[miss], x_nom0[miss], status[miss] = Um, xm, sm
+            iters[miss] = im
+        return U, x_nom0, status, iters
+
+    def result(self) -> dict:
+        """law_hits, law_tries, law_region as the device loops return them, and the miss log (dict of n_total, x_k, ref, variant)."""
+        nx = self._K.shape[1]
+        return dict(law_hits=self.hits, law_tries=self.tries, law_region=self.region,
+                    misses=dict(n_total=self.n_total, x_k=np.array(self.miss_x, dtype=np.float64).reshape(-1, nx),
+                                ref=np.array(self.miss_ref, dtype=np.float64).reshape(-1, nx),
+                                variant=np.array(self.miss_variant, np.uint8)))
+
+
 def run_remote_tube_mpc(packets_fn, A, B, K, K_plant, N, Z, p_loss, ref, th_u, ga_u, w, x0=None, extended: bool = False,
                         plant=None, capture=None, observer=None, channel=None, series: bool = False):
     """Closed loop of the remote tube-based MPC over a lossy network for a batch of trajectories:
@@ -643,7 +739,7 @@ def plant_callable(plant):
 def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240301, rank: int = 0, world: int = 1,
              extended: bool = False, device=None, on_device: bool = False, plant=None, warm_start: bool = False,
              timing: bool = False, device_rng: bool = False, force_collective: bool = False, ref_id=None, mean_burst=None,
-             link_stats: bool = False, series=None):
+             link_stats: bool = False, series=None, law=None):
     """The Monte-Carlo sweep of results_linear_system.py:147-301 (BASELINE config 4): len(p_loss) x n_mc
     trajectories of T steps, sharded over `world` ranks (one process per GPU, contiguous p_loss-balanced
     shards), every time step of a shard solved by one kernel launch, statistics all-gathered at the end.
@@ -660,7 +756,9 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     same uniforms (a rate above 1 - 1 / mean_burst keeps independent losses, whose bursts last 1 / (1 - p) on average; every rate must be below 1).  link_stats: four more columns at the end of the table: lost_up, lost_down, max_gap, overrun.
     series: None -- nothing more; True or a sequence of quantiles (True: 0.5, 0.95) -- the loops keep their per-step record and a third
     value is returned, the record's ensemble statistics per time step and loss rate (series_stats, (T, len(p_loss)) tables; on the device
-    tmpc_mc_series_stats).  One rank only: quantiles of shards do not merge (ValueError with world > 1)."""
+    tmpc_mc_series_stats).  One rank only: quantiles of shards do not merge (ValueError with world > 1).
+    law: None -- every step is solved; else the loops go through the controller's explicit-law table (run_closed_loop's `law` on the device,
+    LawPackets.from_law in the host loop of the tube controller) and solve the misses only."""
     if series is not None and series is not False and world > 1:
         raise ValueError("mc_sweep: series needs world == 1 (order statistics of shards do not merge)")
     want_series = series is not None and series is not False
@@ -699,14 +797,20 @@ def mc_sweep(mpc, model: dict, p_loss, n_mc: int, T: int, ref, seed: int = 20240
     if on_device:        # state machines on the GPU as well (tmpc_mc_run); otherwise the host loop around determine_packets
         out = mpc.run_closed_loop(p_loss[pi[lo:hi]], ref, th, ga, w, extended=extended, plant=plant, warm_start=warm_start,
                                   timing=timing, device_rng=(seed, lo, model["w_bound"]) if device_rng else None, ref_id=ids,
-                                  T=T if ids is not None else None, channel=channel, **(dict(series=True) if want_series else {}))
+                                  T=T if ids is not None else None, channel=channel, **(dict(series=True) if want_series else {}),
+                                  **({} if law is None else dict(law=law)))
     elif getattr(mpc, "_smart_actuator", False):       # TrackingMPC: the comparator's loop (results_linear_system.py:262-287)
         out = run_remote_tracking_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(), mpc._N,
                                       p_loss[pi[lo:hi]], ref, th, ga, w, channel=channel, plant=None if plant is None else plant_callable(plant),
                                       series=want_series)
         out["tube_violations"] = np.zeros(hi - lo, dtype=np.int32)
     else:
-        out = run_remote_tube_mpc(mpc.determine_packets, model["A"], model["B"], mpc.get_steady_state_controller_gain(),
+        fn = mpc.determine_packets
+        if law is not None and law is not False:
+            from . import _native
+            _, max_tries, miss_capacity = _native._law_setting(law)
+            fn = LawPackets.from_law(mpc, max_tries=max_tries, miss_capacity=miss_capacity)
+        out = run_remote_tube_mpc(fn, model["A"], model["B"], mpc.get_steady_state_controller_gain(),
                                   mpc.get_ancillary_controller_gain(), mpc._N, mpc._Z, p_loss[pi[lo:hi]], ref, th, ga, w,
                                   extended=extended, plant=None if plant is None else plant_callable(plant), channel=channel, series=want_series)
     cols = [out["tracking_error"], out["tube_violations"], out["not_optimal"]]

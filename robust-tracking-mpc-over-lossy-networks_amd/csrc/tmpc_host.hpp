@@ -18,6 +18,7 @@
 #include "tmpc_condense.hpp"
 #include "tmpc_device.hpp"
 #include "tmpc_hazard.hpp"
+#include "tmpc_law.hpp"
 
 namespace tmpc_host __attribute__((visibility("hidden"))) {
 
@@ -104,6 +105,8 @@ struct LoopRecords {
     uint32_t *ser_w = nullptr;
     int64_t ser_B = 0;
     int ser_T = 0;
+    tmpc::LawLoop law{};         // tmpc_mc_set_law: the per-trajectory counters and the miss log, where the loop left them in the arena
+    int64_t law_B = 0;           // 0: the last loop did not go through the law
 };
 
 // One launch lane of a device handle: a non-blocking stream and everything a solve launch on it mutates, so that launches on
@@ -143,6 +146,8 @@ struct McSession {
     bool full_ref = false;               // opened with a reference table: st.ref_tab is set and the _ref steps are allowed
     double *ref_stage = nullptr;         // device staging of tmpc_mc_step_ref's ref_next (full_ref)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;     // caller's stream -> handle's stream, and back
+    bool law = false;                    // opened with the law on (tmpc_mc_set_law): ll is what every step's law launch is given
+    tmpc::LawLoop ll{};
     char *pin = nullptr;                 // pinned host block [x_t | u_t | ref_next] of tmpc_mc_step[_ref] (nullptr: copies from / to the caller's memory)
 };
 
@@ -183,6 +188,8 @@ struct LoopSettings {
     int64_t pm_B = 0;
     std::vector<double> pm;
     int series = 0;              // tmpc_mc_set_series: the tracking loops keep their per-step record
+    int law = 0, law_max_tries = 0;      // tmpc_mc_set_law: the tracking loops look into the explicit law's table before each solve
+    int64_t law_miss_cap = 0;
 };
 struct LawState;                 // the explicit law's tables (tmpc_law.cpp), created by the first tmpc_law_* call
 struct SensState;                // what the sensitivity entry points keep on the device (tmpc_sens.cpp), created by the first such call
@@ -280,6 +287,13 @@ int sens_signatures(tmpc_handle *h, const char *who, int64_t B, const double *x_
 void release_law(tmpc_handle *h);
 // the solve launches of one call without its timing events: one per variant, `io.variant` the selector (tmpc_law.cpp runs them behind its own kernel)
 int enqueue_solves(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const *ws);
+// (tmpc_law.cpp) the closed loops through the law.  law_loop_begin: the refusals of a run with the law on (nvar problems in use), the
+// models and the tables' descriptions brought up to date; fills ll.t.  enqueue_law_loop: one step -- the law's launch over
+// [x_hat | ref_k] (variant: the problem selector or nullptr; skip: the trajectories that have stopped) with hint = region = ll.region,
+// then the solve launches of the misses with the warm-start records ws, between the timing events of an ordinary solve call.
+int law_loop_begin(tmpc_handle *h, const char *who, int nvar, tmpc::LawLoop &ll);
+int enqueue_law_loop(tmpc_handle *h, Lane &lane, const char *who, int64_t B, const double *x_hat, const double *ref_k, const uint8_t *variant,
+                     const uint8_t *skip, const tmpc::LawLoop &ll, int32_t *const *ws);
 // (tmpc_offline.cpp) cart-pole rows {M, m, b, I, g, l, Th} of n trajectories: empty, or the message naming trajectory and field
 std::string cartpole_rows_error(const char *who, const double *rows, int64_t n);
 }  // namespace tmpc_host

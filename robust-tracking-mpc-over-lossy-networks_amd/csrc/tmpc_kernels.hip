@@ -48,6 +48,8 @@
 #include "tmpc_launch.hpp"
 #include "tmpc_wave.hpp"
 #include "tmpc_mc_step.hpp"
+#include "tmpc_law.hpp"
+#include "tmpc_law_wave.hpp"
 
 namespace tmpc {
 
@@ -428,7 +430,17 @@ struct McStepArg {
     int t;
     uint8_t *gamma_out;          // arrival flags written by this step = problem selector of the NEXT step (the selector read in this
 };                               // step is the other of two buffers: a trajectory must not be taken by both launches of a step)
+// 3: as 1, through the explicit law (closed_loop_law, tmpc_fused_law.hip): before each solve the wave looks its [x_hat | ref_k] up in
+// the handle's table of critical regions -- the region of the step before as the hint -- and a hit writes the region's affine law
+// where the solve would have written and goes straight to the state machines.  Both records lie in device memory and are read through
+// the constant address space.
+struct McLawArg {
+    const McFused *rec;
+    const LawLoop *law;
+};
 template <int FUSED> using McArg = std::conditional_t<FUSED == 1, const McFused *, std::conditional_t<FUSED == 2, McStepArg, McNone>>;
+// (what solve_body takes; McArg is what the launch functions of FUSED = 0 / 1 / 2 pass on, and stays as it is: its spelling is part of their names)
+template <int FUSED> using McBodyArg = std::conditional_t<FUSED == 3, McLawArg, McArg<FUSED>>;
 #if defined(TMPC_HOST_SIM)
 typedef const McFused *McRecord;
 __device__ __forceinline__ McRecord mc_record(const McFused *p) { return p; }
@@ -442,6 +454,19 @@ __device__ __forceinline__ McRecord mc_record(const McFused *p) {
     return (McRecord)((static_cast<uintptr_t>(hi) << 32) | lo);
 }
 #endif
+#if defined(TMPC_HOST_SIM)
+typedef const LawLoop *LawRecord;
+__device__ __forceinline__ LawRecord law_record(const LawLoop *p) { return p; }
+#else
+typedef const __attribute__((address_space(4))) LawLoop *LawRecord;
+__device__ __forceinline__ LawRecord law_record(const LawLoop *p) {
+    unsigned lo = static_cast<unsigned>(reinterpret_cast<uintptr_t>(p)), hi = static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) >> 32);
+    asm volatile("" : "+v"(lo), "+v"(hi));
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    return (LawRecord)((static_cast<uintptr_t>(hi) << 32) | lo);
+}
+#endif
 
 // The body of both kernels below (inlined into each: one persistent workgroup per CU, a wave per work item)
 template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB, int FUSED>
@@ -451,7 +476,7 @@ __device__ __forceinline__ void solve_body(
     double *__restrict__ u_nom, double *__restrict__ x_nom0, double *__restrict__ xu_ss,
     double *__restrict__ x_nom, int32_t *__restrict__ status, int32_t *__restrict__ iters,
     const int32_t *ws_in, int32_t *ws_out, unsigned long long *__restrict__ next_item,      // (ws_in may alias ws_out: the closed loop updates the records in place)
-    const McArg<FUSED> mc) {
+    const McBodyArg<FUSED> mc) {
     using SH = Shape<NV, DP, DS, KC, CP, CS, tile_rows(NV, WPB)>;
     using WL = WaveLds<SH>;
     constexpr int RS = SH::RS, FD = SH::FD, FC = SH::FC, NDP = SH::NDP, NCCP = SH::NCCP, KT = SH::KT, WCAP = SH::WCAP, LDG = SH::LDG;
@@ -542,6 +567,7 @@ __device__ __forceinline__ void solve_body(
 
         int n_steps = 1;
         if constexpr (FUSED == 1) n_steps = mc_record(mc)->T;
+        if constexpr (FUSED == 3) n_steps = mc_record(mc.rec)->T;
         for (int t_mc = 0; t_mc < n_steps; ++t_mc) {        // (FUSED: the time steps of trajectory b; otherwise the one solve of instance b)
         // ------------------------------------------------------------ per-instance data
         TMPC_REFRESH();
@@ -554,6 +580,57 @@ __device__ __forceinline__ void solve_body(
             if (lane < nx) { xin[lane] = x_k[b * nx + lane]; xin[nx + lane] = ref[b * nx + lane]; }
         }
         wave_lds_fence();
+        // FUSED == 3: the explicit law first.  p = xin is in the wave's LDS; hit or miss is wave-uniform.
+        bool law_hit = false;
+        if constexpr (FUSED == 3) {
+            const LawRecord lr = law_record(mc.law);
+            const int np = 2 * nx;
+            const bool finite = __ballot(lane < np && !law_finite(xin[lane < np ? lane : 0])) == 0ull;
+            int32_t *const region = lr->region;
+            int tried = 0;
+            const int win = finite ? law_find(lr->t[0].S, lr->t[0].order, lr->t[0].R, lr->t[0].n_order, lr->t[0].nrowp, np, xin,
+                                              __builtin_amdgcn_readfirstlane(region[b]), lr->max_tries, lane, tried)
+                                   : -1;
+            if (win >= 0) {
+                // y = Ky p + ky = [u_nom | x_nom0 | xu_ss], the lanes over its rows
+                const int ny0 = N * nu, ny = ny0 + 2 * nx + nu;
+                const double *Kt = lr->t[0].K;
+                for (int j = lane; j < ny; j += WAVE) {
+                    const double s = law_row(Kt, win, ny, np, xin, j);
+                    if (j < ny0) u_nom[b * ny0 + j] = s;
+                    else if (j < ny0 + nx) x_nom0[b * nx + (j - ny0)] = s;
+                    else xu_ss[b * (nx + nu) + (j - ny0 - nx)] = s;
+                }
+                if (lane == 0) {
+                    status[b] = TMPC_STATUS_OPTIMAL;
+                    iters[b] = 0;
+                    if (qp.ticks) qp.ticks[b] = 0;
+                    region[b] = win;
+                    lr->hits[b] += 1;
+                    lr->tries[b] += tried;
+                    unsigned long long *th = lr->t[0].hits;
+                    if (th) atomicAdd(th + win, 1ull);
+                }
+                law_hit = true;
+            } else {
+                // a miss: logged through the one counter, then solved like any step of the fused loop
+                unsigned long long *mn = lr->miss_n;
+                unsigned long long slot = 0;
+                if (lane == 0) {
+                    region[b] = -1;
+                    lr->tries[b] += tried;
+                    slot = atomicAdd(mn, 1ull);
+                }
+                const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(slot & 0xffffffffull)));
+                const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(slot >> 32)));
+                const long long at = static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
+                if (at < lr->miss_cap) {
+                    if (lane < np) lr->miss_p[at * np + lane] = xin[lane];
+                    if (lane == 0) lr->miss_var[at] = 0;
+                }
+            }
+        }
+        if (!law_hit) {
         int st = TMPC_STATUS_MAX_ITER;
         int it_done = 0;
 #ifdef TMPC_ITERS_TOTAL
@@ -1555,6 +1632,7 @@ __device__ __forceinline__ void solve_body(
         STAMP(8);
         if (b == 0 && lane == 0 && qp.dbg) { for (int p_ = 0; p_ < 16; ++p_) qp.dbg[p_] = tph[p_]; }
 #endif
+        }           // (!law_hit)
         wave_lds_fence();
         if constexpr (FUSED != 0) {
             // the trajectory's state machines for step t_mc: packet, losses, actuator, statistics, plant, estimator, next reference.
@@ -1567,6 +1645,7 @@ __device__ __forceinline__ void solve_body(
             int t_now = t_mc, t_all = n_steps;
             uint8_t *gamma_out = nullptr;
             if constexpr (FUSED == 1) mr = mc_record(mc);
+            else if constexpr (FUSED == 3) mr = mc_record(mc.rec);
             else { mr = mc_record(mc.rec); t_now = mc.t; t_all = mr->T; gamma_out = mc.gamma_out; }
             const int t_next = t_now + 1 < t_all ? t_now + 1 : t_now;
             const double *rseq = mr->ref_seq;
@@ -1608,6 +1687,17 @@ __global__ __launch_bounds__(WAVE *WPB, 1) void closed_loop_step_kernel(
     int32_t *__restrict__ status, int32_t *__restrict__ iters, int32_t *ws, unsigned long long *__restrict__ next_item,
     const McStepArg mc) {
     solve_body<NV, DP, DS, KC, CP, CS, WPB, 2>(qp, variant_id, B, nullptr, nullptr, variant, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
+                                               next_item, mc);
+}
+
+// the fused closed loop through the explicit law (tmpc_mc_set_law with one problem): as closed_loop_kernel, each step's solve behind a look
+// into the table of critical regions
+template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB>
+__global__ __launch_bounds__(WAVE *WPB, 1) void closed_loop_law(
+    const DeviceQP qp, const int64_t B, double *__restrict__ u_nom, double *__restrict__ x_nom0, double *__restrict__ xu_ss,
+    int32_t *__restrict__ status, int32_t *__restrict__ iters, int32_t *ws, unsigned long long *__restrict__ next_item,
+    const McLawArg mc) {
+    solve_body<NV, DP, DS, KC, CP, CS, WPB, 3>(qp, 0, B, nullptr, nullptr, nullptr, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
                                                next_item, mc);
 }
 
@@ -1680,8 +1770,21 @@ Ret with_shape(const KernelShape &s, Ret miss, F &&f) {
 // tmpc_kernels.hip / tmpc_fused.hip / tmpc_fused_step.hip (which defines that launch function alone, below).  tests/wavesim,
 // one translation unit per binary: the binary of the extended controller holds closed_loop_step_kernel only, the others
 // everything else -- the fused loop on the bench shape alone under TMPC_SIM_SHAPES (one instantiation less per binary).
+// FUSED = 3 (tmpc_fused_law.hip): the shapes whose closed_loop_law keeps within the registers of its solve_kernel twin's budget
+// (tests/test_law_loop.py reads the code-object notes); the handles of the others run the law per time step.  tests/wavesim: behind
+// TMPC_SIM_LAW_LOOP only, on the bench shape.
+// The dense-single shapes (no factored block) are left out: the law's walk costs them 28 - 29 registers over solve_kernel, 22 in <16,0,4,0,0,0>.
+template <class T> struct factored_block : std::false_type {};
+template <int NV, int DP, int DS, int KC, int CP, int CS> struct factored_block<ShapeTag<NV, DP, DS, KC, CP, CS>> : std::bool_constant<(KC > 0)> {};
 template <class T, int FUSED>
 constexpr bool instantiated() {
+#if defined(TMPC_HOST_SIM) && !defined(TMPC_SIM_LAW_LOOP)
+    if (FUSED == 3) return false;
+#elif defined(TMPC_HOST_SIM)
+    return FUSED == 3 && std::is_same_v<T, ShapeTag<11, 1, 0, 5, 4, 0>>;       // (that binary holds nothing else: a third of the compile)
+#else
+    if (FUSED == 3) return factored_block<T>::value;
+#endif
 #if !defined(TMPC_HOST_SIM)
     return true;
 #elif defined(TMPC_SIM_SHAPES_EXT)
@@ -1740,6 +1843,28 @@ hipError_t launch_solve_mc_step(const DeviceQP &qp, const KernelShape &s, int va
 hipError_t launch_solve_mc(const DeviceQP &qp, const KernelShape &s, int64_t B, double *u_nom, double *x_nom0, double *xu_ss,
                            int32_t *status, int32_t *iters, int32_t *ws, const McFused *mc, WorkCounter *wc, int n_cu, hipStream_t stream) {
     return launch_shape<1>(qp, s, 0, BatchIO{B, nullptr, nullptr, nullptr, u_nom, x_nom0, xu_ss, nullptr, status, iters}, ws, ws, wc, n_cu, stream, mc);
+}
+#endif
+#if defined(TMPC_SIM_LAW_LOOP) || (defined(TMPC_FUSED_TU) && TMPC_FUSED_TU == 3)
+hipError_t launch_solve_mc_law(const DeviceQP &qp, const KernelShape &s, int64_t B, double *u_nom, double *x_nom0, double *xu_ss, int32_t *status,
+                               int32_t *iters, int32_t *ws, const McFused *mc, const LawLoop *law, WorkCounter *wc, int n_cu, hipStream_t stream) {
+    // (launch_wpb's grid, workgroup and LDS, with this kernel's arguments)
+    return with_shape(s, hipErrorInvalidValue, [&]<int... S>(ShapeTag<S...> tag) -> hipError_t {
+        if constexpr (instantiated<decltype(tag), 3>()) {
+            using SH = typename ShapeTag<S...>::SH;
+            constexpr int WPB = ShapeTag<S...>::WPB;
+            const size_t lds = kernel_lds_bytes<SH>(WPB, 4 * qp.nks);
+            if (lds > 160 * 1024) return hipErrorInvalidValue;
+            const unsigned blocks = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(B, n_cu)));
+            unsigned long long *next_item = nullptr;
+            if (const hipError_t e = next_word(wc, stream, &next_item); e != hipSuccess) return e;
+            return launch_grid(closed_loop_law<S..., WPB>, blocks, WAVE * WPB, lds, stream, qp, B, u_nom, x_nom0, xu_ss, status, iters, ws, next_item,
+                               McLawArg{mc, law});
+        } else return hipErrorInvalidValue;
+    });
+}
+bool law_fused_compiled(const KernelShape &s) {
+    return with_shape(s, false, [](auto tag) { return instantiated<decltype(tag), 3>(); });
 }
 #endif
 #if defined(TMPC_HOST_SIM) || !defined(TMPC_FUSED_TU)

@@ -373,6 +373,10 @@ struct LawCall {
     double *u_nom, *x_nom0, *xu_ss, *x_nom;
     int32_t *status, *iters, *region, *tries;
     bool fallback;
+    // a closed loop's step (enqueue_law_loop): nullptr elsewhere
+    const tmpc::LawLoop *loop = nullptr;
+    const uint8_t *skip = nullptr;
+    int32_t *const *ws = nullptr;
 };
 
 int check_call(tmpc_handle *h, const char *who, const LawCall &c) {
@@ -418,10 +422,14 @@ int enqueue_law(tmpc_handle *h, Lane &lane, const char *who, const LawCall &c) {
     a.ny0 = N * nu; a.ny1 = nx; a.Y0 = c.u_nom; a.Y1 = c.x_nom0; a.Y2 = c.xu_ss;
     a.x_nom = c.x_nom; a.A = s.dAB; a.Bm = s.dAB ? s.dAB + static_cast<size_t>(nx) * nx : nullptr; a.nx = nx; a.nu = nu; a.N = N;
     a.status = c.status; a.iters = c.iters; a.region = c.region; a.tries = c.tries; a.todo = todo; a.fallback = c.fallback ? 1 : 0;
+    if (c.loop) {
+        a.skip = c.skip; a.acc_hits = c.loop->hits; a.acc_tries = c.loop->tries;
+        a.miss_n = c.loop->miss_n; a.miss_cap = c.loop->miss_cap; a.miss_p = c.loop->miss_p; a.miss_var = c.loop->miss_var;
+    }
     if (const int rc = begin_timed_launch(h, lane)) return rc;       // (tmpc_last_kernel_ms reads the pair)
     HIP_TRY(h, tmpc::launch_law(a, tmpc::law_blocks(c.B, h->n_cu), lane.stream));
     if (c.fallback)                       // the handle's ordinary solve launches, the misses selected by `todo`
-        if (const int rc = enqueue_solves(h, lane, {c.B, c.x_k, c.ref, todo, c.u_nom, c.x_nom0, c.xu_ss, c.x_nom, c.status, c.iters}, nullptr)) return rc;
+        if (const int rc = enqueue_solves(h, lane, {c.B, c.x_k, c.ref, todo, c.u_nom, c.x_nom0, c.xu_ss, c.x_nom, c.status, c.iters}, c.ws)) return rc;
     HIP_TRY(h, hipEventRecord(h->ev1, lane.stream));
     h->timed = true;
     return TMPC_OK;
@@ -505,6 +513,36 @@ int table_entry(tmpc_handle *h, const char *who, int variant) {
 }
 
 }  // namespace
+
+namespace tmpc_host {
+
+int law_loop_begin(tmpc_handle *h, const char *who, int nvar, tmpc::LawLoop &ll) {
+    if (h->regulator) { h->err = std::string(who) + ": a regulator handle is not supported by the explicit law (tracking handles only)"; return TMPC_E_UNSUPPORTED; }
+    for (int k = 0; k < nvar; ++k)
+        if (h->v[k].c.off_aux >= 0) {
+            h->err = std::string(who) + ": with the law on (tmpc_mc_set_law), variant " + std::to_string(k) + " keeps the unpriced auxiliaries of the literal terminal row, which the outputs do not determine (give HTP / hTP)";
+            return TMPC_E_UNSUPPORTED;
+        }
+    for (int k = 0; k < nvar; ++k)
+        if (const int rc = ensure_model(h, who, k)) return rc;
+    if (const int rc = upload_tables(h, who)) return rc;
+    for (int k = 0; k < 2; ++k) {
+        const LawVariant &v = h->law->v[k];
+        tmpc::LawTable &t = ll.t[k];
+        t.nrow = v.m.nrow(); t.nrowp = v.m.nrowp(); t.R = static_cast<int>(v.regions.size()); t.n_order = static_cast<int>(v.order.size());
+        t.S = v.dS; t.K = v.dK; t.order = v.dorder; t.hits = v.dhits;
+    }
+    return TMPC_OK;
+}
+
+int enqueue_law_loop(tmpc_handle *h, Lane &lane, const char *who, int64_t B, const double *x_hat, const double *ref_k, const uint8_t *variant,
+                     const uint8_t *skip, const tmpc::LawLoop &ll, int32_t *const *ws) {
+    LawCall c{B, x_hat, ref_k, variant, ll.region, ll.max_tries, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it, ll.region, nullptr, true};
+    c.loop = &ll; c.skip = skip; c.ws = ws;
+    return enqueue_law(h, lane, who, c);
+}
+
+}  // namespace tmpc_host
 
 extern "C" {
 

@@ -30,6 +30,7 @@
 #include "tmpc_device.hpp"
 #include "tmpc_launch.hpp"
 #include "tmpc_law.hpp"
+#include "tmpc_law_wave.hpp"
 
 namespace tmpc {
 
@@ -39,38 +40,12 @@ constexpr int LAW_THREADS = 64 * LAW_WAVES;
 constexpr int LAW_LDS_P = LAW_MAX_NP, LAW_LDS_U = LAW_MAX_NV, LAW_LDS_X = 2 * LAW_MAX_NX;
 constexpr int LAW_LDS_WAVE = LAW_LDS_P + LAW_LDS_U + LAW_LDS_X;      // doubles of LDS per wave: p | u_nom | x_i, x_{i+1}
 
-__device__ inline bool law_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }          // (false for NaN)
-
 #ifdef TMPC_HOST_SIM
 __device__ inline void law_lds_fence() { sim::wave_fence(); }
 #else
 // Orders one wave's LDS traffic for the compiler (the hardware runs the DS instructions of a wave in issue order).
 __device__ inline void law_lds_fence() { asm volatile("" ::: "memory"); }
 #endif
-
-// s + sum_q col[q stride] p[q], eight loads in flight at a time: one candidate's chunk is a chain of dependent fused multiply-adds behind
-// loads that do not depend on each other, and issued one by one they cost an L2 round trip each
-__device__ inline double law_dot(const double *col, int stride, const double *p, int np, double s) {
-    int q = 0;
-    for (; q + 8 <= np; q += 8, col += 8 * static_cast<size_t>(stride)) {
-        double v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = col[static_cast<size_t>(i) * stride];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s = fma(v[i], p[q + i], s);
-    }
-    if (q + 4 <= np) {
-        double v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = col[static_cast<size_t>(i) * stride];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s = fma(v[i], p[q + i], s);
-        q += 4;
-        col += 4 * static_cast<size_t>(stride);
-    }
-    for (; q < np; ++q, col += stride) s = fma(*col, p[q], s);
-    return s;
-}
 
 // Entry j of y = [Y0 | Y1 | Y2] of instance b
 __device__ inline double *law_y(const LawArgs &a, int64_t b, int j) {
@@ -101,10 +76,16 @@ __global__ __launch_bounds__(LAW_THREADS) void law_kernel(const LawArgs a) {
 
     for (int64_t b = static_cast<int64_t>(blockIdx.x) * nwave + wave; b < a.B; b += static_cast<int64_t>(gridDim.x) * nwave) {
         // ---- 1: inputs
+        if (a.skip && a.skip[b]) {        // (a closed loop's trajectory that has stopped: nothing is evaluated, counted or solved)
+            if (lane == 0 && a.todo) a.todo[b] = LAW_TODO_DONE;
+            continue;
+        }
         const int var = a.variant ? a.variant[b] : 0;
         double v = 0.0;
         if (lane < np) v = lane < a.np0 ? a.P0[b * a.np0 + lane] : a.P1[b * (np - a.np0) + (lane - a.np0)];
-        const bool refused = __ballot(!law_finite(v)) != 0ull || var >= a.nvariants;
+        const bool finite = __ballot(!law_finite(v)) == 0ull;
+        const bool looped = a.acc_hits != nullptr;       // (a closed loop's step: a non-finite p is left to the solve as a miss)
+        const bool refused = (!finite && !looped) || var >= a.nvariants;
         if (refused) {
             law_fill_nan(a, b, lane);
             if (lane == 0) {
@@ -123,27 +104,23 @@ __global__ __launch_bounds__(LAW_THREADS) void law_kernel(const LawArgs a) {
         // ---- 2, 3: the candidates
         const LawTable t = a.t[var];
         const int h = a.hint ? a.hint[b] : -1;
-        const bool hinted = h >= 0 && h < t.R;
-        const size_t rstride = static_cast<size_t>(np + 1) * t.nrowp;
-        int tried = 0, win = -1;
-        for (int c = hinted ? -1 : 0; c < t.n_order && (a.max_tries <= 0 || tried < a.max_tries); ++c) {
-            const int r = c < 0 ? h : t.order[c];
-            if (c >= 0 && hinted && r == h) continue;
-            ++tried;
-            const double *Sr = t.S + static_cast<size_t>(r) * rstride;
-            bool inside = true;
-            for (int base = 0; base < t.nrowp; base += 64) {
-                const double *col = Sr + base + lane;
-                double s = col[static_cast<size_t>(np) * t.nrowp];
-                s = law_dot(col, t.nrowp, pv, np, s);
-                if (__ballot(!(s >= 0.0)) != 0ull) { inside = false; break; }
-            }
-            if (inside) { win = r; break; }
-        }
+        int tried = 0;
+        const int win = finite ? law_find(t.S, t.order, t.R, t.n_order, t.nrowp, np, pv, h, a.max_tries, lane, tried) : -1;
 
         // ---- 5: a miss
         if (win < 0) {
             if (!a.fallback) law_fill_nan(a, b, lane);
+            if (a.miss_n) {               // the log: the row's slot through the one counter, which counts on past the capacity
+                unsigned long long slot = 0;
+                if (lane == 0) slot = atomicAdd(a.miss_n, 1ull);
+                const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(slot & 0xffffffffull)));
+                const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(slot >> 32)));
+                const long long at = static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
+                if (at < a.miss_cap) {
+                    if (lane < np) a.miss_p[at * np + lane] = v;
+                    if (lane == 0) a.miss_var[at] = static_cast<uint8_t>(var);
+                }
+            }
             if (lane == 0) {
                 if (!a.fallback) {
                     if (a.status) a.status[b] = TMPC_STATUS_NUMERICAL;
@@ -151,17 +128,15 @@ __global__ __launch_bounds__(LAW_THREADS) void law_kernel(const LawArgs a) {
                 }
                 a.region[b] = -1;
                 if (a.tries) a.tries[b] = tried;
+                if (a.acc_tries) a.acc_tries[b] += tried;
                 if (a.todo) a.todo[b] = static_cast<uint8_t>(var);
             }
             continue;
         }
 
         // ---- 4: the winner's law
-        const double *Kr = t.K + static_cast<size_t>(win) * (np + 1) * ny;
         for (int j = lane; j < ny; j += 64) {
-            const double *col = Kr + j;
-            double s = col[static_cast<size_t>(np) * ny];
-            s = law_dot(col, ny, pv, np, s);
+            const double s = law_row(t.K, win, ny, np, pv, j);
             *law_y(a, b, j) = s;
             if (a.x_nom) {
                 if (j < a.ny0) uv[j] = s;
@@ -193,6 +168,8 @@ __global__ __launch_bounds__(LAW_THREADS) void law_kernel(const LawArgs a) {
             if (a.iters) a.iters[b] = 0;
             a.region[b] = win;
             if (a.tries) a.tries[b] = tried;
+            if (a.acc_tries) a.acc_tries[b] += tried;
+            if (a.acc_hits) a.acc_hits[b] += 1;
             if (a.todo) a.todo[b] = LAW_TODO_DONE;
             if (t.hits) atomicAdd(t.hits + win, 1ull);
         }

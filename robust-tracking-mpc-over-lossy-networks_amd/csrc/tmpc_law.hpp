@@ -56,6 +56,30 @@ struct LawArgs {
     int32_t *tries;          // [B] or NULL
     uint8_t *todo;           // [B] or NULL: the variant id of a miss, LAW_TODO_DONE otherwise
     int fallback;            // 1: a miss leaves y, x_nom, status and iters to the solve launches that follow
+    // A closed loop's step (tmpc_mc_set_law; all NULL / 0 elsewhere): an instance with skip[b] != 0 (a trajectory that has stopped) is
+    // passed over, a non-finite p is a miss like any other (the solve that follows gives its verdict as it does without the law),
+    // hits and candidates add up per trajectory, and a miss appends its p and variant to the log through one counter.
+    const uint8_t *skip;     // [B] or NULL
+    int32_t *acc_hits;       // [B] or NULL
+    long long *acc_tries;    // [B] or NULL
+    unsigned long long *miss_n;       // one counter, or NULL: no log
+    long long miss_cap;      // rows of the log; the counter goes on counting beyond
+    double *miss_p;          // [miss_cap][np]
+    uint8_t *miss_var;       // [miss_cap]
+};
+
+// What the fused closed loop (closed_loop_law, tmpc_fused_law.hip) reads of the law: in device memory, read through the constant
+// address space like the loop's own record.  The tables are those of the handle at the start of the run.
+struct LawLoop {
+    LawTable t[2];
+    int max_tries;           // <= 0: all
+    int32_t *region;         // [B]: the hint of a step going in, its region coming out (-1: a miss)
+    int32_t *hits;           // [B]
+    long long *tries;        // [B]
+    unsigned long long *miss_n;
+    long long miss_cap;
+    double *miss_p;          // [miss_cap][np]
+    uint8_t *miss_var;       // [miss_cap]
 };
 
 unsigned law_blocks(int64_t B, int n_cu);

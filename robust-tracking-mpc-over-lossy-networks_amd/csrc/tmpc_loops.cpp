@@ -86,6 +86,7 @@ struct TrackingLoop {
     SetRows Z, X, U;
     const McReplay *rp;         // (tmpc_mc_replay solves nothing and is given its arrival flags: it ignores the reference table and the channel)
     bool host_draws, full_ref, channel, series;       // (series: tmpc_mc_set_series -- ignored by tmpc_mc_replay like the other two)
+    bool law;                   // tmpc_mc_set_law (ignored by tmpc_mc_replay)
 };
 
 // The argument checks of the tracking loops, in the order each entry point has always reported them (it differs between the resident
@@ -99,6 +100,7 @@ int check_tracking_loop(tmpc_handle *h, TrackingLoop &q) {
     q.full_ref = !q.rp && h->loop.ref_K > 0;
     q.channel = !q.rp && h->loop.ch_B > 0;
     q.series = !q.rp && h->loop.series != 0;
+    q.law = !q.rp && h->loop.law != 0;
     if (q.session && h->regulator) return refuse("a regulator handle has no stepped loop");
     if (q.session && (q.B <= 0 || q.T <= 0 || q.Z.rows < 0 || q.X.rows < 0 || q.U.rows < 0)) return refuse("need B > 0, T > 0 and row counts >= 0");
     if (q.B < 0 || q.T < 0 || (!q.p_loss && !q.channel) || (!q.ref && !q.full_ref) || (q.host_draws && (!q.th_u || !q.ga_u || (!q.session && !q.w))) ||
@@ -119,7 +121,7 @@ int check_tracking_loop(tmpc_handle *h, TrackingLoop &q) {
 // that nothing of an earlier loop reaches this one.  ws: the warm-start sets; s: the session, whose extra pieces (the caller's sets and
 // counters, the staging of tmpc_mc_step[_ref]) go in between -- nullptr for a run, whose arena is the list below without them.  The caller
 // adds what is its own, carves and calls link_block_carved.  THE place where a new loop option gets its device memory.
-void tracking_pieces(tmpc_handle *h, const TrackingLoop &q, tmpc::McModel &m, tmpc::McState &st, int32_t **ws, McSession *s) {
+void tracking_pieces(tmpc_handle *h, const TrackingLoop &q, tmpc::McModel &m, tmpc::McState &st, int32_t **ws, McSession *s, tmpc::LawLoop *ll) {
     const LoopSettings &L = h->loop;
     const size_t nx = h->nx, nu = h->nu, N = h->N, b = static_cast<size_t>(q.B), t_ = static_cast<size_t>(q.T);
     m.nx = h->nx; m.nu = h->nu; m.N = h->N; m.extended = q.extended ? 1 : 0; m.rZ = q.Z.rows;
@@ -186,6 +188,17 @@ void tracking_pieces(tmpc_handle *h, const TrackingLoop &q, tmpc::McModel &m, tm
         a.piece(&st.ser_w, t_ * b * 4, nullptr, 0);
         st.ser_B = q.B;
     }
+    if (q.law) {            // the law's bookkeeping: hint / region (-1: 0xFF bytes), the two accumulators, the miss log and its counter
+        const size_t cap = static_cast<size_t>(L.law_miss_cap);
+        ll->max_tries = L.law_max_tries;
+        ll->miss_cap = L.law_miss_cap;
+        a.piece(&ll->region, b * 4, nullptr, 0xFF);
+        a.piece(&ll->hits, b * 4, nullptr, 0);
+        a.piece(&ll->tries, b * 8, nullptr, 0);
+        a.piece(&ll->miss_n, 8, nullptr, 0);
+        a.piece(&ll->miss_p, cap * 2 * nx * 8);
+        a.piece(&ll->miss_var, cap);
+    }
     if (q.rp) {
         // (plain controller: the packets carry no x_nom_0; the state machines then never read it -- zeros)
         a.piece(&st.rp_U, b * t_ * (N + 1) * nu * 8, q.rp->U);
@@ -198,7 +211,8 @@ void tracking_pieces(tmpc_handle *h, const TrackingLoop &q, tmpc::McModel &m, tm
 // The end of a tracking loop: enqueues the copy-back of its statistics (a NULL destination: not wanted) and of the link counters, waits,
 // and leaves what the getters read (LoopRecords; the arena stays as it is until the next loop).  T: the rows of a recorded trajectory.
 using McCounter = std::pair<int32_t *, const int32_t *>;      // (host destination, device counter)
-int fetch_tracking_results(tmpc_handle *h, const tmpc::McState &st, int64_t B, int T, double *err2, double *consistent, std::initializer_list<McCounter> counters) {
+int fetch_tracking_results(tmpc_handle *h, const tmpc::McState &st, const tmpc::LawLoop *ll, int64_t B, int T, double *err2, double *consistent,
+                           std::initializer_list<McCounter> counters) {
     const size_t b = static_cast<size_t>(B);
     if (err2) HIP_TRY(h, hipMemcpyAsync(err2, st.err2, b * 8, hipMemcpyDeviceToHost, h->stream));
     if (consistent) HIP_TRY(h, hipMemcpyAsync(consistent, st.consistent, b * 8, hipMemcpyDeviceToHost, h->stream));
@@ -212,6 +226,7 @@ int fetch_tracking_results(tmpc_handle *h, const tmpc::McState &st, int64_t B, i
     if (st.tick_sum) { h->rec.tick_sum = st.tick_sum; h->rec.tick_max = st.tick_max; h->rec.tick_B = B; }
     h->rec.link_B = B;
     if (st.ser_w) { h->rec.ser_e = st.ser_e; h->rec.ser_w = st.ser_w; h->rec.ser_B = B; h->rec.ser_T = T; }
+    if (ll) { h->rec.law = *ll; h->rec.law_B = B; }
     return TMPC_OK;
 }
 
@@ -227,6 +242,10 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
     const std::vector<double> ref_unused(q.full_ref ? static_cast<size_t>(T) : 0, 0.0);
     const double *const ref = q.full_ref ? ref_unused.data() : q.ref;
     if (const int rc = begin_loop(h, B)) return rc;
+    // through the explicit law (tmpc_mc_set_law): the table as it stands now
+    tmpc::LawLoop ll{};
+    if (q.law)
+        if (const int rc = law_loop_begin(h, q.who, extended ? 2 : 1, ll)) return rc;
     const size_t nx = h->nx, nu = h->nu, b = static_cast<size_t>(B), t_ = static_cast<size_t>(T);
     // ONE launch for the whole sweep where the controller has one problem and it runs on the wave kernel: a wave keeps its
     // trajectory for all T steps, solve and state machines alternating inside the kernel (tmpc_fused.hip).  The work item of
@@ -234,7 +253,9 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
     // of trajectories would run on a nearly empty card, so TMPC_MC_FUSED_AUTO fuses when the rounds are at least 85 % full
     // (or there is a single round) and otherwise keeps the launch per time step, whose work item is one solve.
     // (a loop that keeps its per-step record runs per time step: the fused kernels are compiled without the recording)
-    bool fuse = !rp && !extended && !q.series && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]);
+    // (through the law: closed_loop_law, where the shape has one -- DESIGN.md 7n; the other shapes look the law up per time step)
+    bool fuse = !rp && !extended && !q.series && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]) &&
+                (!q.law || tmpc::law_fused_compiled(h->v[0].shape));
     if (fuse && h->loop.fused == TMPC_MC_FUSED_AUTO) {
         const int64_t slots = tmpc::resident_waves(h->v[0].shape, h->n_cu);
         const int64_t rounds = slots > 0 ? (B + slots - 1) / slots : 0;
@@ -244,7 +265,8 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
     // its trajectories inside (closed_loop_step_kernel) -- two launches per step where the plain per-step loop has three
     // (TMPC_MC_FUSED_AUTO: from one round of resident waves on -- below that a step is the latency of its launches, and the state
     // machines inside BOTH of them lengthen it: 200 trajectories at N = 20 0.0345 s with three launches per step, 0.0367 s with two)
-    bool step_fuse = !rp && extended && !q.series && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]) && !use_block(h, h->v[1]);
+    // (through the law the three-launch form below: the hits need their state machines run too)
+    bool step_fuse = !rp && extended && !q.series && !q.law && h->loop.fused != TMPC_MC_FUSED_OFF && !use_block(h, h->v[0]) && !use_block(h, h->v[1]);
     if (step_fuse && h->loop.fused == TMPC_MC_FUSED_AUTO) step_fuse = B >= tmpc::resident_waves(h->v[1].shape, h->n_cu);
     // the fused kernels' record {model, state, T, reference}: uploaded once the state is carved; lives until the final synchronise
     tmpc::McFused mf{};
@@ -252,14 +274,16 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
         tmpc::McModel m{};
         tmpc::McState st{};
         int32_t *ws[2] = {nullptr, nullptr};
-        tracking_pieces(h, q, m, st, ws, nullptr);
+        tracking_pieces(h, q, m, st, ws, nullptr, &ll);
         Arena &a = h->arena;
         uint8_t *gam[2] = {nullptr, nullptr};           // selector read in a step / arrival flags written in it: swapped every step
         tmpc::McFused *d_mf = nullptr;                  // the record itself lives in the arena: the kernel reads it field by field
+        tmpc::LawLoop *d_ll = nullptr;                  // (and the law's, for closed_loop_law)
         if (fuse || step_fuse) {
             a.piece(&mf.ref_seq, t_ * 8, ref);
             if (step_fuse) a.piece(&gam[1], b, nullptr, 1);
             a.piece(&d_mf, sizeof(mf));
+            if (q.law) a.piece(&d_ll, sizeof(ll));
         }
         HIP_TRY(h, a.carve(h->stream));
         link_block_carved(st, b);
@@ -270,6 +294,7 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
             st.ticks = h->want_ticks ? h->lane[0].ticks.as<long long>() : nullptr;
             mf.m = m; mf.st = st; mf.T = T;
             HIP_TRY(h, hipMemcpyAsync(d_mf, &mf, sizeof(mf), hipMemcpyHostToDevice, h->stream));
+            if (d_ll) HIP_TRY(h, hipMemcpyAsync(d_ll, &ll, sizeof(ll), hipMemcpyHostToDevice, h->stream));
         }
         if (step_fuse) {
             // (Measured and dropped: the two launches of a step on two streams, so that the second one's workgroups start on the CUs the
@@ -285,8 +310,12 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
             h->rec.fused = 2;
         } else if (fuse) {
             if (const int r2 = begin_timed_launch(h, h->lane[0])) return r2;          // (the launch counts in tmpc_kernel_ms_total like any solve launch)
-            HIP_TRY(h, tmpc::launch_solve_mc(h->v[0].d, h->v[0].shape, B, h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[0], d_mf, &h->lane[0].wc, h->n_cu,
-                                             h->stream));
+            if (q.law)
+                HIP_TRY(h, tmpc::launch_solve_mc_law(h->v[0].d, h->v[0].shape, B, h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[0], d_mf, d_ll,
+                                                     &h->lane[0].wc, h->n_cu, h->stream));
+            else
+                HIP_TRY(h, tmpc::launch_solve_mc(h->v[0].d, h->v[0].shape, B, h->d_u, h->d_x0, h->d_ss, h->d_st, h->d_it, ws[0], d_mf, &h->lane[0].wc,
+                                                 h->n_cu, h->stream));
             HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
             h->timed = true;
             h->rec.fused = 1;
@@ -295,8 +324,9 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
             // (round 3: mc_pre, the variant check, the solve, mc_post, mc_tube).  With injected packets nothing is solved.
             for (int t = 0; t < T; ++t) {
                 if (!rp) {
-                    const int r2 = enqueue(h, h->lane[0], {B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it},
-                                           ws, true);
+                    const int r2 = q.law ? enqueue_law_loop(h, h->lane[0], q.who, B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, st.dead, ll, ws)
+                                         : enqueue(h, h->lane[0], {B, st.x_hat, st.ref_k, extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr,
+                                                                   h->d_st, h->d_it}, ws, true);
                     if (r2) return r2;
                     st.ticks = h->want_ticks ? h->lane[0].ticks.as<long long>() : nullptr;       // (allocated by the first enqueue)
                 }
@@ -309,7 +339,8 @@ int mc_run_impl(tmpc_handle *h, TrackingLoop q, double *err2, int32_t *tube_viol
             HIP_TRY(h, hipMemcpyAsync(rp->trace_i, st.trace_i, b * t_ * 3 * 4, hipMemcpyDeviceToHost, h->stream));
         }
         if (x_final) HIP_TRY(h, hipMemcpyAsync(x_final, st.x, b * nx * 8, hipMemcpyDeviceToHost, h->stream));
-        return fetch_tracking_results(h, st, B, T, err2, consistent, {{tube_viol, st.tube_viol}, {not_optimal, st.not_optimal}, {iters_sum, st.iters_sum}});
+        return fetch_tracking_results(h, st, q.law ? &ll : nullptr, B, T, err2, consistent,
+                                      {{tube_viol, st.tube_viol}, {not_optimal, st.not_optimal}, {iters_sum, st.iters_sum}});
     };
     return finish_loop(h, run());
 }
@@ -326,8 +357,10 @@ int session_step(tmpc_handle *h, const char *who, const double *x_t, double *u_t
     auto step = [&]() -> int {
         HIP_TRY(h, hipSetDevice(h->device));
         tmpc::McState &st = s.st;
-        if (const int rc = enqueue(h, h->lane[0], {s.B, st.x_hat, st.ref_k, s.extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr, h->d_st, h->d_it},
-                                   s.warm ? s.ws : nullptr, true))
+        if (const int rc = s.law ? enqueue_law_loop(h, h->lane[0], who, s.B, st.x_hat, st.ref_k, s.extended ? st.gamma : nullptr, st.dead, s.ll,
+                                                    s.warm ? s.ws : nullptr)
+                                 : enqueue(h, h->lane[0], {s.B, st.x_hat, st.ref_k, s.extended ? st.gamma : nullptr, h->d_u, h->d_x0, h->d_ss, nullptr,
+                                                           h->d_st, h->d_it}, s.warm ? s.ws : nullptr, true))
             return rc;
         st.ticks = st.tick_sum ? h->lane[0].ticks.as<long long>() : nullptr;       // (timed at open; allocated by the first enqueue)
         // the solve did not need x_t; the state machines do
@@ -397,10 +430,16 @@ int open_session(tmpc_handle *h, const TrackingLoop &q, More more) {
     if (const int rc = begin_loop(h, q.B)) return rc;
     const size_t nx = h->nx, nu = h->nu, b = static_cast<size_t>(q.B);
     McSession &s = h->ses;
+    s.law = false;
+    s.ll = tmpc::LawLoop{};
+    if (q.law) {
+        if (const int rc = law_loop_begin(h, q.who, q.extended ? 2 : 1, s.ll)) return rc;
+        s.law = true;
+    }
     auto open = [&]() -> int {
         s.m = tmpc::McModel{}; s.st = tmpc::McState{}; s.ext = tmpc::McExternal{};
         s.warm = h->loop.warm != 0;
-        tracking_pieces(h, q, s.m, s.st, s.ws, &s);
+        tracking_pieces(h, q, s.m, s.st, s.ws, &s, &s.ll);
         more(h->arena, s);
         HIP_TRY(h, h->arena.carve(h->stream));
         link_block_carved(s.st, b);
@@ -432,7 +471,7 @@ int fetch_session_results(tmpc_handle *h, double *err2, int32_t *tube_viol, int3
                           int32_t *iters_sum) {
     McSession &s = h->ses;
     HIP_TRY(h, hipSetDevice(h->device));
-    return fetch_tracking_results(h, s.st, s.B, s.T, err2, consistent, {{tube_viol, s.st.tube_viol}, {x_viol, s.ext.x_viol}, {u_viol, s.ext.u_viol},
+    return fetch_tracking_results(h, s.st, s.law ? &s.ll : nullptr, s.B, s.T, err2, consistent, {{tube_viol, s.st.tube_viol}, {x_viol, s.ext.x_viol}, {u_viol, s.ext.u_viol},
                                                                         {not_optimal, s.st.not_optimal}, {iters_sum, s.st.iters_sum}});
 }
 
@@ -794,6 +833,62 @@ int tmpc_series_stats(int device, int64_t B, int32_t T, const double *e, const u
     if (const hipError_t err = hipMemcpy(rec.p + n * 8, word, n * 4, hipMemcpyHostToDevice); err != hipSuccess) return fail("upload", err);
     const SeriesOut out{{n_alive, n_nan, lost_up, lost_down, adopted, tube, not_optimal, overrun, age_max, iters_max}, {age_sum, iters_sum}, {e_sum, e_max}, e_q, kernel_ms};
     return series_reduce(who, g_create_error, reinterpret_cast<const double *>(rec.p), reinterpret_cast<const uint32_t *>(rec.p + n * 8), B, T, G, group, n_q, q, out, nullptr);
+}
+
+int tmpc_mc_set_law(tmpc_handle *h, int on, int max_tries, int64_t miss_capacity) {
+    if (!h || session_bars(h, "tmpc_mc_set_law")) return TMPC_E_INVALID;
+    if (h->regulator) { h->err = "tmpc_mc_set_law: a regulator handle is not supported by the explicit law (tracking handles only)"; return TMPC_E_UNSUPPORTED; }
+    if (miss_capacity < 0) { h->err = "tmpc_mc_set_law: miss_capacity < 0"; return TMPC_E_INVALID; }
+    h->loop.law = on ? 1 : 0;
+    h->loop.law_max_tries = max_tries;
+    h->loop.law_miss_cap = miss_capacity;
+    return TMPC_OK;
+}
+
+// the law's record the getters read: is there one?
+static bool law_record_missing(tmpc_handle *h, const char *who, int64_t B, bool any_B) {
+    if (h->rec.law_B > 0 && (any_B || B == h->rec.law_B)) return false;
+    h->err = std::string(who) + ": no tracking loop of this B has run through the explicit law (tmpc_mc_set_law before tmpc_mc_run, tmpc_mc_run_plants or tmpc_mc_open)";
+    return true;
+}
+
+int tmpc_mc_get_law_stats(tmpc_handle *h, int64_t B, int32_t *hits, int64_t *tries, int32_t *region_last) {
+    if (!h) return TMPC_E_INVALID;
+    if (h->ses.open) { h->err = "tmpc_mc_get_law_stats: a stepped closed loop is open on this handle (tmpc_mc_close first)"; return TMPC_E_INVALID; }
+    if (law_record_missing(h, "tmpc_mc_get_law_stats", B, false)) return TMPC_E_INVALID;
+    const size_t b = static_cast<size_t>(B);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, sync_lanes(h));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the accumulators are copied as they are");
+    if (hits) HIP_TRY(h, hipMemcpy(hits, h->rec.law.hits, b * 4, hipMemcpyDeviceToHost));
+    if (tries) HIP_TRY(h, hipMemcpy(tries, h->rec.law.tries, b * 8, hipMemcpyDeviceToHost));
+    if (region_last) HIP_TRY(h, hipMemcpy(region_last, h->rec.law.region, b * 4, hipMemcpyDeviceToHost));
+    return TMPC_OK;
+}
+
+int tmpc_mc_get_law_misses(tmpc_handle *h, int64_t capacity, int64_t *n_total, double *x_k, double *ref, uint8_t *variant) {
+    const char *who = "tmpc_mc_get_law_misses";
+    if (!h) return TMPC_E_INVALID;
+    if (capacity < 0) { h->err = std::string(who) + ": capacity < 0"; return TMPC_E_INVALID; }
+    if (h->ses.open) { h->err = std::string(who) + ": a stepped closed loop is open on this handle (tmpc_mc_close first)"; return TMPC_E_INVALID; }
+    if (law_record_missing(h, who, 0, true)) return TMPC_E_INVALID;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, sync_lanes(h));
+    unsigned long long total = 0;
+    HIP_TRY(h, hipMemcpy(&total, h->rec.law.miss_n, 8, hipMemcpyDeviceToHost));
+    if (n_total) *n_total = static_cast<int64_t>(total);
+    const size_t rows = static_cast<size_t>(std::min<int64_t>({static_cast<int64_t>(total), static_cast<int64_t>(h->rec.law.miss_cap), capacity})), nx = h->nx;
+    if (rows == 0) return TMPC_OK;
+    if (x_k || ref) {
+        std::vector<double> p(rows * 2 * nx);
+        HIP_TRY(h, hipMemcpy(p.data(), h->rec.law.miss_p, p.size() * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < rows; ++i) {
+            if (x_k) std::copy(p.begin() + i * 2 * nx, p.begin() + i * 2 * nx + nx, x_k + i * nx);
+            if (ref) std::copy(p.begin() + i * 2 * nx + nx, p.begin() + (i + 1) * 2 * nx, ref + i * nx);
+        }
+    }
+    if (variant) HIP_TRY(h, hipMemcpy(variant, h->rec.law.miss_var, rows, hipMemcpyDeviceToHost));
+    return TMPC_OK;
 }
 
 int tmpc_mc_set_warm_start(tmpc_handle *h, int on) {
