@@ -740,7 +740,10 @@ int tmpc_get_dims(const tmpc_handle *h, int variant, int32_t *nv, int32_t *nc, i
 /*
  * How the nc rows are stored: nd general ("dense") rows of width nv and one block of ncc rows of rank kc kept in factored
  * form Hc * Psi (the terminal set acts on [x_N; theta] only, TubeTrackingMPC.py:149; the initial-state set of the
- * packet-received problem on x_0 only, :278); nc = nd + ncc, ncc = kc = 0 when nothing is factored.  bench.py prices the
+ * packet-received problem on x_0 only, :278); nc = nd + ncc, ncc = kc = 0 when nothing is factored.  The figures are those of
+ * the layout the variant's kernel reads: the wave kernel's lane packing moves the rows of a partly filled last slot of the
+ * block to the dense class (cart-pole N = 10: 120 / 384 / 5; 92 / 412 / 5 with TMPC_NO_LANE_PACKING=1 in the environment of
+ * tmpc_create), the workgroup-per-QP kernel keeps every row dense.  bench.py prices the
  * factored block at its rank in `roofline_factored`.  Added without an ABI bump: a new export, nothing else changed.
  */
 int tmpc_get_factoring(const tmpc_handle *h, int variant, int32_t *nd, int32_t *ncc, int32_t *kc);

@@ -124,12 +124,36 @@ int upload_wave(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
         found = tmpc::pick_config(c.nv, static_cast<int>(dpair.size()), static_cast<int>(dsing.size()), use_fact ? c.kc : 0,
                                   static_cast<int>(cpair.size()), static_cast<int>(csing.size()), &v.shape);
     }
-    if (found) {
-        // the dense functionals in use must fit the LDS next to the workspaces of the shape's waves
+    // rows of dense functionals staged in LDS: up to the last one in use, in whole k-steps of the MFMA pass
+    auto dense_rows = [&]() {
         const int last = dsing.empty() ? static_cast<int>(dpair.size()) : v.shape.dp * 64 + static_cast<int>(dsing.size());
-        if (tmpc::lds_bytes(v.shape, 4 * ((last + 3) / 4)) > 160 * 1024) found = false;
-    }
+        return 4 * ((last + 3) / 4);
+    };
+    // the dense functionals in use must fit the LDS next to the workspaces of the shape's waves
+    if (found && tmpc::lds_bytes(v.shape, dense_rows()) > 160 * 1024) found = false;
     if (!found) return TMPC_OK;                                  // wave_ok stays false: the block kernel takes the variant
+    // Lane packing (pairs + factored block only).  The factored pairs beyond the last full slot -- 14 of the 206 of the cart-pole's terminal
+    // set -- go to idle lanes of the dense paired slots where all of them fit: a factored row is a row of Gs like any other (Hc Psi), a lane of
+    // a dense slot costs the same whether it holds a functional or padding, and the kernel then runs the body compiled without the last
+    // factored slot (DeviceQP::ncs; only the shapes that hold one: skips_empty_slots).  Paired slots still hold complete pairs only.
+    // TMPC_NO_LANE_PACKING=1 keeps the unpacked layout (tests, A/Bs).
+    int ncs = v.shape.cp + v.shape.cs;
+    {
+        const char *e = std::getenv("TMPC_NO_LANE_PACKING");
+        const int full = static_cast<int>(cpair.size()) / 64, need = static_cast<int>(cpair.size()) - 64 * full;
+        const int idle = 64 * v.shape.dp - static_cast<int>(dpair.size());
+        if (use_pairs && use_fact && csing.empty() && full == ncs - 1 && full > 0 && need > 0 && need <= idle && tmpc::skips_empty_slots(v.shape) &&
+            !(e && std::atoi(e) != 0)) {
+            dpair.insert(dpair.end(), cpair.end() - need, cpair.end());
+            cpair.resize(cpair.size() - need);
+            if (tmpc::lds_bytes(v.shape, dense_rows()) <= 160 * 1024) {
+                ncs = full;
+            } else {        // (the two-slot shapes are sized for 96 of their 128 dense rows: back to the unpacked layout)
+                cpair.insert(cpair.end(), dpair.end() - need, dpair.end());
+                dpair.resize(dpair.size() - need);
+            }
+        }
+    }
     const int NVP = v.shape.nvp, DP = v.shape.dp, DS = v.shape.ds, KCP = v.shape.kcp, CP = v.shape.cp, CS = v.shape.cs;
     const int NDP = (DP + DS) * 64, NCCP = (CP + CS) * 64, RS = 2 * DP + DS + 2 * CP + CS;
     const int kc = use_fact ? c.kc : 0;
@@ -182,12 +206,12 @@ int upload_wave(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     tmpc::DeviceQP &d = v.d;
     int rc;
     if ((rc = upload_common(h, v, p, d, NVP))) return rc;
-    d.nd = use_fact ? c.nd : c.nc; d.ncc = use_fact ? c.ncc : 0; d.kc = kc;
-    {
-        // k-steps (4 functionals each) of the MFMA pass over the dense functionals: up to the last one in use
-        const int last = dsing.empty() ? static_cast<int>(dpair.size()) : DP * 64 + static_cast<int>(dsing.size());
-        d.nks = (last + 3) / 4;
-    }
+    // what this layout keeps dense and what factored (tmpc_get_factoring): the rows, not Condensed's split
+    d.ncc = 2 * static_cast<int>(cpair.size()) + static_cast<int>(csing.size());
+    d.nd = c.nc - d.ncc;
+    d.kc = d.ncc > 0 ? kc : 0;
+    d.nks = dense_rows() / 4;          // k-steps (4 functionals each) of the MFMA pass over the dense functionals
+    d.ncs = ncs;
     if ((rc = upload(h, v, Gt.data(), Gt.size(), &d.Gt))) return rc;
     if ((rc = upload(h, v, Hct.data(), Hct.size(), &d.Hct))) return rc;
     if ((rc = upload(h, v, Psi.data(), Psi.size(), &d.Psi))) return rc;
@@ -281,7 +305,7 @@ int upload_block(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     }
     int rc;
     if ((rc = upload_common(h, v, p, v.db, NVP))) return rc;
-    v.db.nd = c.nc; v.db.ncc = 0; v.db.kc = 0; v.db.nks = 0;
+    v.db.nd = c.nc; v.db.ncc = 0; v.db.kc = 0; v.db.nks = 0; v.db.ncs = 0;
     v.db.Gt = v.db.Hct = v.db.Psi = v.db.g0p = v.db.Esp = v.db.cip = nullptr;
     v.db.vmask = nullptr; v.db.row_of = nullptr;
     v.bq.ncp = ncp;
@@ -1003,10 +1027,14 @@ int tmpc_get_dims(const tmpc_handle *h, int variant, int32_t *nv, int32_t *nc, i
 
 int tmpc_get_factoring(const tmpc_handle *h, int variant, int32_t *nd, int32_t *ncc, int32_t *kc) {
     if (!h || variant < 0 || variant >= h->nvariants) return TMPC_E_INVALID;
-    const tmpc::Condensed &c = h->v[variant].c;
-    if (nd) *nd = c.nd;
-    if (ncc) *ncc = c.ncc;
-    if (kc) *kc = c.kc;
+    // the layout the variant's kernel reads: the wave kernel's slots (lane packing moves rows of the low-rank block to the dense class), or
+    // the block kernel's, all dense; a host-only handle that no kernel covers has neither and reports the condensed QP's split
+    const Variant &v = h->v[variant];
+    const bool none = !v.wave_ok && v.tiles == 0;
+    const tmpc::DeviceQP &d = use_block(h, v) ? v.db : v.d;
+    if (nd) *nd = none ? v.c.nd : d.nd;
+    if (ncc) *ncc = none ? v.c.ncc : d.ncc;
+    if (kc) *kc = none ? v.c.kc : d.kc;
     return TMPC_OK;
 }
 

@@ -31,7 +31,7 @@ constexpr int WS_STRIDE = 40;
 struct DeviceQP {
     int nx, nu, N;
     int nv, nc, npar, nth;
-    int nd, ncc, kc;      // dense rows, factored rows (nc = nd + ncc), factor width
+    int nd, ncc, kc;      // dense rows, factored rows (nc = nd + ncc), factor width -- of THIS layout (tmpc_get_factoring), not of Condensed
     int nks;              // k-steps of the MFMA pass over the dense functionals (4 functionals each)
     int off_theta, off_x0, off_aux;
     int max_iter, always_infeasible;
@@ -55,6 +55,9 @@ struct DeviceQP {
     const double *Tzs;    // [nvf][nv]  z_full = Tzs zs + Txf x_k (Dv folded in); NULL: z_full = Dv .* zs  (tmpc_condense.hpp: Tz, Tx)
     const double *Txf;    // [nvf][nx]
     int nvf;              // length of z_full = [u | theta | x_0 | aux]; the outputs are read from it at off_theta / off_x0
+    int ncs;              // factored slots in use: CP + CS, or CP + CS - 1 where the functionals of the last, partly filled slot sit on
+                          // idle lanes of the dense slots (tmpc_api.cpp: upload_wave); the kernel then runs its body compiled without that
+                          // slot.  (In the padding behind nvf: no other kernel argument moves.)
     const double *Mth;    // [nx+nu][nth]
     const double *A;      // [nx][nx]
     const double *B;      // [nx][nu]
@@ -107,6 +110,7 @@ bool pick_config(int nv, int nd2, int nd1, int kc, int nc2, int nc1, KernelShape
 size_t lds_bytes(const KernelShape &shape, int grows);      // grows = 4 * nks rows of dense functionals staged in LDS
 const char *kernel_name(const KernelShape &shape);
 bool parks_in_lds(const KernelShape &shape);               // the hand-over iterate stays in LDS: no DeviceQP::save slot needed
+bool skips_empty_slots(const KernelShape &shape);          // the shape's kernels honour DeviceQP::ncs < CP + CS (lane packing, tmpc_api.cpp)
 
 // Work counters of the persistent grids (wave kernel and block kernel): every launch draws its instances from a fresh, zeroed device word of
 // a ring that is cleared in one piece when it has gone round -- no reset and no extra stream operation per launch.

@@ -174,6 +174,11 @@ struct Shape {
     static constexpr int FD = DP_ + DS_, FC = CP_ + CS_;          // functional slots per lane: dense, factored
     static constexpr int NDP = FD * WAVE, NCCP = FC * WAVE;
     static constexpr int RS = 2 * DP_ + DS_ + 2 * CP_ + CS_;      // row sides per lane
+    // The shapes whose kernels hold a second body, compiled for all factored slots but the last (TMPC_SOLVE_BODY), and whose problems
+    // tmpc_api.cpp therefore packs (skips_empty_slots): the bench shape.  (A slot count read at run time, one branch per pass and slot, cost
+    // the one-wave-per-SIMD shapes registers they do not have -- solve_kernel<22,2,0,5,4,0,4> spilled 40 instead of 4, <24,...> 100,
+    // closed_loop_law<12,1,0,5,4,0,8> took a private segment -- and the bench shape 3 % of its launch: DESIGN.md 5.1.)
+    static constexpr bool SKIPS = NV_ == 11 && DP_ == 1 && DS_ == 0 && KC_ == 5 && CP_ == 4 && CS_ == 0;
     static constexpr int NT = NV_ * (NV_ + 1) / 2, KT = KC_ * (KC_ + 1) / 2;
     static constexpr int WCAP = NV_ <= 24 ? 24 : 28;              // max rows in the refinement's working set (<= WS_CAP)
     // Row strides of the small LDS matrices that are read with the row on the lane (Hs, Hs^-1, the normal matrix, the expanded
@@ -372,13 +377,14 @@ __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const d
 }
 
 // The FACTORED functionals: KC-wide left factor, so W = Hc' D Hc has only KT entries; one pass.
-template <class SH>
+// NCS: the factored slots in use, the first NCS of the shape's FC (see solve_body)
+template <class SH, int NCS>
 __device__ __forceinline__ void sweep_a_factored(const double *Hct, const double (&s)[SH::RS], const double (&lam)[SH::RS],
                                                  const double *rpw, double (&rs)[SH::RS], double &gap_l, double obj_l,
                                                  double *red, double *csums, int lane) {
     constexpr int KC = SH::KC, KT = SH::KT, NCCP = SH::NCCP;
     double acc[KT + KC + 2];   // initialised by the first slot's products; the last two entries carry the wave's complementarity gap and objective
-    static_for<SH::FC>([&](auto kc_) {
+    static_for<NCS>([&](auto kc_) {
         constexpr int kc = decltype(kc_)::value;
         const int r = lane + kc * WAVE;
         double hc[KC];
@@ -469,7 +475,8 @@ __device__ __forceinline__ LawRecord law_record(const LawLoop *p) {
 #endif
 
 // The body of both kernels below (inlined into each: one persistent workgroup per CU, a wave per work item)
-template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB, int FUSED>
+// NCS: the factored slots in use, a compile-time count (TMPC_SOLVE_BODY below picks the instantiation)
+template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB, int FUSED, int NCS>
 __device__ __forceinline__ void solve_body(
     const DeviceQP &qp, const int variant_id, const int64_t B,
     const double *__restrict__ x_k, const double *__restrict__ ref, const uint8_t *__restrict__ variant,
@@ -498,6 +505,11 @@ __device__ __forceinline__ void solve_body(
     int lane = lane_k;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: the workspace addresses stay scalar
     const int nx = qp.nx, nu = qp.nu, N = qp.N, nc = qp.nc;
+    // The factored slots in use are the first NCS, so the row sides in use are the first RSL: every pass over the factored slots and every
+    // loop over the row sides stops there.  The sides beyond are padding wherever they are still read: s = 1, lambda = 0, never in the
+    // working set.
+    constexpr int RSL = NCS == FC ? RS : SH::cbase(NCS);
+    static_assert(NCS == FC || (SH::SKIPS && NCS == FC - 1), "the slot counts a layout of this shape can have");
 
     // ---- stage the shared model once per workgroup (coalesced, L2-resident source)
     for (int i = tid; i < (grows + ZERO_ROWS) * LDG; i += blockDim.x) Gt[i] = (i < grows * LDG) ? qp.Gt[i] : 0.0;
@@ -669,26 +681,27 @@ __device__ __forceinline__ void solve_body(
             constexpr size_t PL = static_cast<size_t>(RS) * WAVE;
             for (int c0 = 0; c0 < nx; c0 += 4) {
                 double ev[4][RS];
+                // (the sides of a skipped factored slot are not formed: nothing reads their h)
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const size_t cu = static_cast<size_t>(c0 + u < nx ? c0 + u : nx - 1);      // (planes beyond nx: a valid address, weight 0)
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) ev[u][i] = E0[cu * PL + i * WAVE];
+                    for (int i = 0; i < RSL; ++i) ev[u][i] = E0[cu * PL + i * WAVE];
                 }
                 if (c0 == 0) {
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) hv[i] = qp.g0p[i * WAVE + lane];
+                    for (int i = 0; i < RSL; ++i) hv[i] = qp.g0p[i * WAVE + lane];
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const double xc = c0 + u < nx ? xin[c0 + u] : 0.0;
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) hv[i] = fma(ev[u][i], xc, hv[i]);
+                    for (int i = 0; i < RSL; ++i) hv[i] = fma(ev[u][i], xc, hv[i]);
                 }
             }
             double hmax = 1.0;
 #pragma unroll
-            for (int i = 0; i < RS; ++i) {
+            for (int i = 0; i < RSL; ++i) {
                 if (valid(i)) hmax = fmax(hmax, fabs(hv[i]));
                 hw[i * WAVE + lane] = hv[i];
             }
@@ -728,7 +741,7 @@ __device__ __forceinline__ void solve_body(
                     if (valid(i)) smin = vmin(smin, sl[i]);
                 }
             });
-            static_for<FC>([&](auto kc_) {
+            static_for<NCS>([&](auto kc_) {
                 constexpr int kc = decltype(kc_)::value;
                 const double gz = fact_dot<SH, kc>(Hct, czv, lane);
 #pragma unroll
@@ -738,6 +751,8 @@ __device__ __forceinline__ void solve_body(
                     if (valid(i)) smin = vmin(smin, sl[i]);
                 }
             });
+#pragma unroll
+            for (int i = RSL; i < RS; ++i) sl[i] = 1.0;
             return smin;
         };
 
@@ -803,7 +818,7 @@ __device__ __forceinline__ void solve_body(
                     const double park_mu = WL::PARK_LDS ? *reinterpret_cast<const double *>(park + RS * WAVE) : 0.0;
                     const double park_thr = 1e3 * try_tol * hn;        // (try_tol is a hundredth of the hand-over's by now)
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) {
+                    for (int i = 0; i < RSL; ++i) {
                         const bool vl = valid(i);
                         const double raw = s[i];
                         double sv, lv;
@@ -827,6 +842,8 @@ __device__ __forceinline__ void solve_body(
                         rpn0 = vmax_abs(rpn0, rp0);
                         rs[i] = 1.0;
                     }
+#pragma unroll
+                    for (int i = RSL; i < RS; ++i) { s[i] = 1.0; lam[i] = 0.0; rs[i] = 1.0; }
                     wave_lds_fence();
                     it0 = resume_it;
                     resume_it = -1;
@@ -844,7 +861,7 @@ __device__ __forceinline__ void solve_body(
                     // which sets the launch time of a batch, by more (the oracle and the block kernel alike).
                     double l1 = 0.0;
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) l1 = vmax(l1, valid(i) ? -s[i] * qp.cip[i * WAVE + lane] : 0.0);
+                    for (int i = 0; i < RSL; ++i) l1 = vmax(l1, valid(i) ? -s[i] * qp.cip[i * WAVE + lane] : 0.0);
                     l1 = wave_max(l1);
 #ifdef TMPC_LAM0_ONE
                     const double lam0 = l1 < 0.0 ? 2.0 : 1.0;      // (diagnostic builds: the round-3 start)
@@ -852,7 +869,7 @@ __device__ __forceinline__ void solve_body(
                     const double lam0 = fmin(fmax(sqrt(sqrt(l1)), 1.0), 1e3);
 #endif
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) {
+                    for (int i = 0; i < RSL; ++i) {
                         const bool vl = valid(i);
                         const double raw = s[i];
                         s[i] = vl ? fmax(raw, fl) : 1.0;
@@ -862,6 +879,8 @@ __device__ __forceinline__ void solve_body(
                         rpn0 = vmax_abs(rpn0, rp0);
                         rs[i] = 1.0;
                     }
+#pragma unroll
+                    for (int i = RSL; i < RS; ++i) { s[i] = 1.0; lam[i] = 0.0; rs[i] = 1.0; }
                     wave_lds_fence();
                 }
                 rpn0 = readlane_d(wave_max(rpn0), 0);       // (wave-uniform, like kappa: scalar registers, none of the lanes')
@@ -886,7 +905,7 @@ __device__ __forceinline__ void solve_body(
                     if constexpr (FD > 0) sweep_a_dense<SH>(Gt, qp.nks, s, lam, rpw, rs, gap_l, dtw, Mf, sums, lane);
                     if constexpr (KC > 0) {
                         TMPC_REFRESH();
-                        sweep_a_factored<SH>(Hct, s, lam, rpw, rs, gap_l, obj_l, red, csums, lane);
+                        sweep_a_factored<SH, NCS>(Hct, s, lam, rpw, rs, gap_l, obj_l, red, csums, lane);
                         // fold the factored block into the dense totals: P = W Psi now, Psi' P when the rows of M are formed
                         for (int idx = lane; idx < KC * NV; idx += WAVE) {
                             const int a = idx / NV, j = idx - a * NV;
@@ -952,7 +971,7 @@ __device__ __forceinline__ void solve_body(
                             double accl[KC];
 #pragma unroll
                             for (int a = 0; a < KC; ++a) accl[a] = 0.0;
-                            static_for<FC>([&](auto kc_) {
+                            static_for<NCS>([&](auto kc_) {
                                 constexpr int kc = decltype(kc_)::value;
                                 const int r = lane + kc * WAVE;
                                 double dl2 = lam[SH::cbase(kc)];
@@ -988,7 +1007,7 @@ __device__ __forceinline__ void solve_body(
                             const double lmax = wave_max(lmax_l);
                             double hl = 0.0;       // (h is formed on the fly: its LDS region holds r_p here)
 #pragma unroll
-                            for (int i = 0; i < RS; ++i) {
+                            for (int i = 0; i < RSL; ++i) {
                                 const int sl = i * WAVE + lane;
                                 double hv = qp.g0p[sl];
                                 for (int c = 0; c < nx; ++c) hv += qp.Esp[static_cast<size_t>(c) * (RS * WAVE) + sl] * xin[c];
@@ -1130,7 +1149,7 @@ __device__ __forceinline__ void solve_body(
                             if constexpr (!ONE) wave_sums_part<SH, 0, NBD>(acc, red, sums, lane);   // overwrites G'(d.rp0), G'lam (consumed)
                         }
                         if constexpr (KC > 0) {
-                            static_for<FC>([&](auto kc_) {
+                            static_for<NCS>([&](auto kc_) {
                                 constexpr int kc = decltype(kc_)::value;
                                 const int r = lane + kc * WAVE;
                                 double hc[KC];
@@ -1212,7 +1231,7 @@ __device__ __forceinline__ void solve_body(
                             for (int sd = 0; sd < SH::dsides(kd); ++sd) side_step(SH::dbase(kd) + sd, sd == 1, gdz);
                             if constexpr (WPB == 8 || TMPC_FENCE_ALL) row_fence();
                         });
-                        static_for<FC>([&](auto kc_) {
+                        static_for<NCS>([&](auto kc_) {
                             constexpr int kc = decltype(kc_)::value;
                             const double gdz = fact_dot<SH, kc>(Hct, cdzv, lane);
 #pragma unroll
@@ -1221,8 +1240,9 @@ __device__ __forceinline__ void solve_body(
                     }
                     rho = wave_max(rho);
                     const double alpha = rho > tau ? tau / rho : 1.0;
+                    // (the sides of a skipped factored slot keep s = 1, lambda = 0: neither sweep has written their directions)
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) {
+                    for (int i = 0; i < RSL; ++i) {
                         s[i] = fma(alpha, rs[i], s[i]);
                         lam[i] = fma(alpha, wv_[i], lam[i]);
                     }
@@ -1258,7 +1278,7 @@ __device__ __forceinline__ void solve_body(
                     // parked in LDS: every hand-over, a store per row side (WaveLds::PARK_LDS has the form of the continuation)
                     if (want_polish) {
 #pragma unroll
-                        for (int i = 0; i < RS; ++i) park[i * WAVE + lane] = __float_as_uint(static_cast<float>(lam[i]));
+                        for (int i = 0; i < RSL; ++i) park[i * WAVE + lane] = __float_as_uint(static_cast<float>(lam[i]));
                         if (lane == 0) *reinterpret_cast<double *>(park + RS * WAVE) = mu_hand;
                         saved = true;
                         wave_lds_fence();
@@ -1274,7 +1294,7 @@ __device__ __forceinline__ void solve_body(
                     saved = __ballot(amb) != 0ull;
                     if (saved) {
 #pragma unroll
-                        for (int i = 0; i < RS; ++i) {
+                        for (int i = 0; i < RSL; ++i) {
                             save[i * WAVE + lane] = static_cast<float>(s[i]);
                             save[(RS + i) * WAVE + lane] = static_cast<float>(lam[i]);
                         }
@@ -1311,7 +1331,7 @@ __device__ __forceinline__ void solve_body(
                         // whatever is wrongly dropped comes back through the verification of ALL rows below.
                         int cnt = 0;
 #pragma unroll
-                        for (int i = 0; i < RS; ++i) cnt += __popcll(__ballot(inW[i]));
+                        for (int i = 0; i < RSL; ++i) cnt += __popcll(__ballot(inW[i]));      // (no side of a skipped slot is ever in W)
                         if (cnt > WCAP) {
                             double ym = 0.0;
 #pragma unroll
@@ -1329,7 +1349,7 @@ __device__ __forceinline__ void solve_body(
                         }
                     }
 #pragma unroll
-                    for (int i = 0; i < RS; ++i) {
+                    for (int i = 0; i < RSL; ++i) {
                         const unsigned long long bal = __ballot(inW[i]);
                         const int pos = m + __popcll(bal & ((1ull << lane) - 1ull));
                         if (inW[i] && pos < WCAP) { Widx[pos] = i * WAVE + lane; yv[pos] = yall[i]; }
@@ -1506,7 +1526,7 @@ __device__ __forceinline__ void solve_body(
 #pragma unroll
                             for (int sd = 0; sd < SH::dsides(kd); ++sd) check_side(SH::dbase(kd) + sd, sd ? -gz : gz);
                         });
-                        static_for<FC>([&](auto kc_) {
+                        static_for<NCS>([&](auto kc_) {
                             constexpr int kc = decltype(kc_)::value;
                             const double gz = fact_dot<SH, kc>(Hct, cdzav, lane);
 #pragma unroll
@@ -1659,6 +1679,22 @@ __device__ __forceinline__ void solve_body(
     }
 }
 
+// The body for the layout at hand: all factored slots in use, or -- in the shapes that pack their lanes (Shape::SKIPS) -- all but the last.
+// One wave-uniform branch at kernel entry (DeviceQP::ncs is a kernel argument); each side is compiled for its slot count, so the packed
+// one carries neither the skipped slot's registers nor a branch per pass.  (A macro: the kernels hand their own arguments on, and the
+// shapes without a second body compile to what they were.)
+#define TMPC_SOLVE_BODY(FUSED, ...)                                                                     \
+    do {                                                                                                \
+        constexpr int FC_ = CP + CS;                                                                    \
+        if constexpr (Shape<NV, DP, DS, KC, CP, CS, tile_rows(NV, WPB)>::SKIPS) {                       \
+            if (qp.ncs < FC_) {                                                                         \
+                solve_body<NV, DP, DS, KC, CP, CS, WPB, FUSED, FC_ - 1>(__VA_ARGS__);                   \
+                return;                                                                                 \
+            }                                                                                           \
+        }                                                                                               \
+        solve_body<NV, DP, DS, KC, CP, CS, WPB, FUSED, FC_>(__VA_ARGS__);                               \
+    } while (0)
+
 // tmpc_solve_batch and the per-step closed loop: a work item is one QP
 template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB>
 __global__ __launch_bounds__(WAVE *WPB, 1) void solve_kernel(
@@ -1667,7 +1703,7 @@ __global__ __launch_bounds__(WAVE *WPB, 1) void solve_kernel(
     double *__restrict__ u_nom, double *__restrict__ x_nom0, double *__restrict__ xu_ss,
     double *__restrict__ x_nom, int32_t *__restrict__ status, int32_t *__restrict__ iters,
     const int32_t *ws_in, int32_t *ws_out, unsigned long long *__restrict__ next_item) {
-    solve_body<NV, DP, DS, KC, CP, CS, WPB, 0>(qp, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, ws_in, ws_out,
+    TMPC_SOLVE_BODY(0, qp, variant_id, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters, ws_in, ws_out,
                                                    next_item, McNone{});
 }
 // the fused closed loop (tmpc_mc_run with one problem): a work item is one TRAJECTORY, all of its T steps
@@ -1676,7 +1712,7 @@ __global__ __launch_bounds__(WAVE *WPB, 1) void closed_loop_kernel(
     const DeviceQP qp, const int64_t B, double *__restrict__ u_nom, double *__restrict__ x_nom0, double *__restrict__ xu_ss,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, int32_t *ws, unsigned long long *__restrict__ next_item,
     const McFused *mc) {
-    solve_body<NV, DP, DS, KC, CP, CS, WPB, 1>(qp, 0, B, nullptr, nullptr, nullptr, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
+    TMPC_SOLVE_BODY(1, qp, 0, B, nullptr, nullptr, nullptr, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
                                                next_item, mc);
 }
 // the extended controller's closed loop: the QPs of problem `variant_id` at time step mc.t, each followed by its trajectory's state machines
@@ -1686,7 +1722,7 @@ __global__ __launch_bounds__(WAVE *WPB, 1) void closed_loop_step_kernel(
     double *__restrict__ u_nom, double *__restrict__ x_nom0, double *__restrict__ xu_ss,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, int32_t *ws, unsigned long long *__restrict__ next_item,
     const McStepArg mc) {
-    solve_body<NV, DP, DS, KC, CP, CS, WPB, 2>(qp, variant_id, B, nullptr, nullptr, variant, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
+    TMPC_SOLVE_BODY(2, qp, variant_id, B, nullptr, nullptr, variant, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
                                                next_item, mc);
 }
 
@@ -1697,7 +1733,7 @@ __global__ __launch_bounds__(WAVE *WPB, 1) void closed_loop_law(
     const DeviceQP qp, const int64_t B, double *__restrict__ u_nom, double *__restrict__ x_nom0, double *__restrict__ xu_ss,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, int32_t *ws, unsigned long long *__restrict__ next_item,
     const McLawArg mc) {
-    solve_body<NV, DP, DS, KC, CP, CS, WPB, 3>(qp, 0, B, nullptr, nullptr, nullptr, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
+    TMPC_SOLVE_BODY(3, qp, 0, B, nullptr, nullptr, nullptr, u_nom, x_nom0, xu_ss, nullptr, status, iters, ws, ws,
                                                next_item, mc);
 }
 
@@ -1883,6 +1919,10 @@ size_t lds_bytes(const KernelShape &s, int grows) {
 
 bool parks_in_lds(const KernelShape &s) {
     return with_shape(s, false, [](auto tag) { return WaveLds<typename decltype(tag)::SH>::PARK_LDS; });
+}
+
+bool skips_empty_slots(const KernelShape &s) {
+    return with_shape(s, false, [](auto tag) { return decltype(tag)::SH::SKIPS; });
 }
 
 const char *kernel_name(const KernelShape &s) {
