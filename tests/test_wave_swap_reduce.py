@@ -1,6 +1,11 @@
 """The register wave sums of csrc/tmpc_wave.hpp (wv::swap_reduce_to_lds: v_permlane32_swap / v_permlane16_swap halvings, then one
 round of the transposition tile; wv::wave_sum2) on the host execution model of tests/wavesim/hip_sim.hpp.  CPU only.
 
+What runs here is the project's MODEL of the instructions, not the instructions: under TMPC_HOST_SIM wv::permlane_swap is an emulation
+written from the manual and the DPP moves are hip_sim.hpp's.  This file checks the routine's lane maps and arithmetic on that model (and
+its memory safety under the sanitizers); that the model and the hardware agree is tests/test_wave_primitives_gpu.py, which runs the same
+cases on the device and compares the totals with this program's bit for bit.
+
 For every count of values 1 ... 32 and both tile heights of the kernels (12 and 16 rows), and for the 44 and 52 values of sweep B at
 N = 20 (12 rows; 52 values take two rounds of the tile), with random values and with values of
 mixed signs and magnitudes (1e-12 ... 1e6): every total agrees with the float64 sum over the 64 lanes to within
