@@ -989,6 +989,35 @@ int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t 
  *   a region that holds no p); order [n_order] ids; P [B][np]; out_y [B][ny] (NaN for a miss); hint and tries may be NULL.  Limits:
  *   1 <= nv <= 128, 0 <= nc <= 2^20, 1 <= np <= 32, 1 <= ny <= 4096, n_sets and n_order <= 2^20.
  *
+ * Hops.  A candidate that fails tells where to look next: row i < nc of its polyhedron is the slack (i outside the working set) or the
+ * multiplier (i inside) of constraint i, so the region across the facet of a failing row i has the working set with bit i flipped.
+ *   The key of a working set A is the XOR over i in A of z(i), z = splitmix64 of i + 1:
+ *     x = (i + 1) * 0x9E3779B97F4A7C15;  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *   (64-bit, wrapping); the empty set has key 0, and the neighbour across row i has key(A) ^ z(i) whichever side i is on.  Per table the
+ *   device holds key [R] and an open-addressed table slot [n_slot] of int32 ids, -1 for empty: n_slot is the power of two >= max(64, 2 R),
+ *   ids are inserted in increasing order at key & (n_slot - 1) with linear probing, a key already present keeps the earlier id, a lookup
+ *   compares key[slot[j]] and stops at an empty slot.  A 64-bit collision costs one wasted test, never an answer.  The host builds both
+ *   wherever the table changes (tmpc_law_add, tmpc_law_learn, tmpc_law_clear; tmpc_law_reorder leaves them alone).
+ * tmpc_law_set_hops(h, max_hops) / tmpc_law_get_hops(h, &max_hops): a handle-wide setting, 0 by default, read by tmpc_law_eval[_device],
+ *   tmpc_law_solve[_device] and the loops of tmpc_mc_set_law (at the start of a run; a session at its open).  With max_hops > 0 the search
+ *   of an instance is a CHAIN, then the walk:
+ *     the chain starts at the hint where it is a valid id, otherwise at order[0], otherwise there is none.  The current region r is tested
+ *     (it counts in tries); if it accepts, it is the answer.  Otherwise, with i the LOWEST failing row (a NaN row fails), the chain ends
+ *     if -- looked at in this order -- i >= nc (a parameter-only row); r has no key (a refused set of tmpc_qp_law_eval_hops); the
+ *     neighbour's key is absent from the hash; the neighbour is the region tested immediately before r (a two-cycle); max_hops hops have
+ *     been made; max_tries > 0 candidates have been tested.  Otherwise r becomes the neighbour.
+ *     The walk is the search order without the chain's start, under the same max_tries; regions the chain visited may be tested again.
+ *   Acceptance is the KKT test, so whatever the chain finds is the minimiser, and nothing that hits without hops can miss with them.
+ *   max_hops = 0 is the search described above, unchanged.  The setter waits for the launch lanes; max_hops < 0 and an open session:
+ *   TMPC_E_INVALID; a regulator handle: TMPC_E_UNSUPPORTED; on a host-only handle it only stores the value.
+ * tmpc_law_get_hop_stats(h, variant, stats) / tmpc_law_clear_hop_stats(h, variant): six counters per variant in device memory, added to
+ *   with max_hops > 0 only -- stats[0] chains that hit (the start's own hit included), [1] regions the chains tested, chains ended [2] by an
+ *   absent neighbour, [3] by max_hops, [4] by a two-cycle, [5] by a parameter-only row; a chain ended by max_tries or at a region without
+ *   a key counts in none of [2..5].  Both wait for the lanes; tmpc_law_clear clears the variant's counters too; zeros on a host-only handle.
+ * tmpc_law_find_key(h, variant, key, &id): the id the host's hash holds under a key, -1: none.  Works on a host-only handle.
+ * tmpc_qp_law_eval_hops: the arguments of tmpc_qp_law_eval, then max_hops >= 0 and stats (int64 [6] or NULL); tmpc_qp_law_eval is this
+ *   entry at max_hops = 0.
+ *
  * Refused before anything touches the device: NULL arguments or B < 0 (TMPC_E_INVALID); an open stepped session (TMPC_E_INVALID); a
  * regulator handle (TMPC_E_UNSUPPORTED); a variant that keeps unpriced auxiliaries (TMPC_E_UNSUPPORTED); for the evaluating entries and
  * tmpc_law_learn a host-only handle (TMPC_E_DEVICE).  Added without an ABI bump: new exports, nothing else changed.
@@ -1014,6 +1043,15 @@ int tmpc_get_param_rows(tmpc_handle *h, int variant, double *gp0, double *Ep);
 int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G, const double *g0,
                      const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order, const int32_t *order,
                      int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries);
+int tmpc_law_set_hops(tmpc_handle *h, int max_hops);
+int tmpc_law_get_hops(tmpc_handle *h, int *max_hops);
+int tmpc_law_get_hop_stats(tmpc_handle *h, int variant, int64_t *stats);
+int tmpc_law_clear_hop_stats(tmpc_handle *h, int variant);
+int tmpc_law_find_key(tmpc_handle *h, int variant, uint64_t key, int32_t *id);
+int tmpc_qp_law_eval_hops(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G, const double *g0,
+                          const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order, const int32_t *order,
+                          int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries, int max_hops,
+                          int64_t *stats);
 
 /*
  * The closed loops through the explicit law.  A trajectory returns to the same few regions step after step, and inside a loop the law has
@@ -1021,7 +1059,8 @@ int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny,
  *
  * tmpc_mc_set_law: with on != 0 the following tmpc_mc_run, tmpc_mc_run_plants and tmpc_mc_open look [x_hat | ref_k] of every trajectory up
  * in the handle's table (of the problem the step would solve) before each solve, and solve the misses only.  The hint of trajectory b at
- * step t is its region at step t-1; -1 at t = 0 and after a miss.  At most max_tries candidates are tried per step, the hint included
+ * step t is its region at step t-1; -1 at t = 0 and after a miss (with tmpc_law_set_hops > 0 such a step chains from order[0]; tries
+ * include the chains' tests).  At most max_tries candidates are tried per step, the hint included
  * (<= 0: all).  The table is the handle's at the start of the run; a session honours the setting as it was at open.  A hit writes what
  * tmpc_law_eval writes -- u_nom, x_nom0, xu_ss, status TMPC_STATUS_OPTIMAL, iters 0 -- which the state machines read as after a solve,
  * counts in the region's hit counter (tmpc_law_get_stats), and with warm start on leaves the trajectory's working-set record as it is.

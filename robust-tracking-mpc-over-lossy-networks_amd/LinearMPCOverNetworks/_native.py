@@ -225,8 +225,15 @@ def lib():
         L.tmpc_get_param_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.tmpc_qp_law_eval.argtypes = ([C.c_int] + [C.c_int32] * 4 + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                                                             C.c_void_p, C.c_int] + [C.c_void_p] * 3)
+        L.tmpc_qp_law_eval_hops.argtypes = L.tmpc_qp_law_eval.argtypes + [C.c_int, C.c_void_p]
+        L.tmpc_law_set_hops.argtypes = [C.c_void_p, C.c_int]
+        L.tmpc_law_get_hops.argtypes = [C.c_void_p, C.c_void_p]
+        L.tmpc_law_get_hop_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tmpc_law_clear_hop_stats.argtypes = [C.c_void_p, C.c_int]
+        L.tmpc_law_find_key.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
         for name in ("tmpc_law_add", "tmpc_law_learn", "tmpc_law_get_stats", "tmpc_law_reorder", "tmpc_law_clear", "tmpc_law_get_region", "tmpc_get_param_rows",
-                     "tmpc_qp_law_eval"):
+                     "tmpc_qp_law_eval", "tmpc_qp_law_eval_hops", "tmpc_law_set_hops", "tmpc_law_get_hops", "tmpc_law_get_hop_stats",
+                     "tmpc_law_clear_hop_stats", "tmpc_law_find_key"):
             getattr(L, name).restype = C.c_int
         _lib = L
     return _lib
@@ -741,17 +748,32 @@ def _ptr(a):
 
 def _law_setting(law):
     """(on, max_tries, miss_capacity) of the `law` argument of mc_run / mc_run_plants / mc_open: None or False -- off; True -- every
-    candidate, no miss log; an int -- max_tries; a dict with max_tries (default 0: all) and miss_capacity (default 0)."""
+    candidate, no miss log; an int -- max_tries; a dict with max_tries (default 0: all) and miss_capacity (default 0) -- and optionally
+    max_hops, the handle-wide setting of tmpc_law_set_hops, which `_law_hops` reads."""
     if law is None or law is False:
         return 0, 0, 0
     if law is True:
         return 1, 0, 0
     if isinstance(law, dict):
-        extra = set(law) - {"max_tries", "miss_capacity"}
+        extra = set(law) - {"max_tries", "miss_capacity", "max_hops"}
         if extra:
-            raise ValueError(f"law: unknown keys {sorted(extra)} (max_tries, miss_capacity)")
+            raise ValueError(f"law: unknown keys {sorted(extra)} (max_tries, miss_capacity, max_hops)")
         return 1, int(law.get("max_tries", 0)), int(law.get("miss_capacity", 0))
     return 1, int(law), 0
+
+
+def _law_hops(law):
+    """max_hops of the `law` argument where it is a dict that names it, else None: the loop runs with the handle's setting (tmpc_law_set_hops)."""
+    return int(law["max_hops"]) if isinstance(law, dict) and "max_hops" in law else None
+
+
+def _restore_law_hops(h: Handle):
+    """Puts back the handle's tmpc_law_set_hops value that a loop's law=dict(max_hops=) replaced (a session's: at its close -- the setter
+    is refused while it is open)."""
+    before = getattr(h, "law_hops_before", None)
+    if before is not None:
+        h.law_hops_before = None
+        law_set_hops(h, before)
 
 
 def mc_law_stats(h: Handle, B: int) -> dict:
@@ -793,6 +815,11 @@ def _set_loop_options(h: Handle, timing, warm_start, capture, fused="keep", seri
     on, max_tries, miss_capacity = _law_setting(law)
     if lib().tmpc_mc_set_law(h.ptr, on, max_tries, miss_capacity) != 0:
         raise RuntimeError(h.error())
+    _restore_law_hops(h)                     # (a loop that failed before its end)
+    if _law_hops(law) is not None:           # for this loop alone: the handle's own value comes back at its end (_tracking_result)
+        before = law_get_hops(h)
+        law_set_hops(h, _law_hops(law))
+        h.law_hops_before = before
     h.law_miss_capacity = miss_capacity      # (mc_law_misses: how many rows the loop's log can hold)
 
 
@@ -821,6 +848,7 @@ def _check_set(P, dim: int, who: str):
 def _tracking_result(h: Handle, out: dict, B: int, T: int, steps: int, loop_mode: int, capture, timing, series: bool = False, law=None) -> dict:
     """Completes the result of a tracking loop (mc_run, mc_close) over the `steps` steps taken of T: the recorded trajectory, the
     solve times, the link statistics and the derived statistics.  THE place where a new loop output is fetched."""
+    _restore_law_hops(h)
     n = steps
     if capture is not None:
         xt, xn, ut = np.empty((T, h.nx)), np.empty((T, h.nx)), np.empty((T, h.nu))
@@ -874,7 +902,7 @@ def mc_run(h: Handle, p_loss, ref, th_u, ga_u, w, x0=None, Z=None, extended: boo
     step, word, and the word's fields alive, lost_up, lost_down, adopted, tube, not_optimal, overrun, iters, age; mc_series_stats then
     reduces it on the device.  Such a loop runs per time step (loop_mode 0, whatever `fused` says).
     law: the loop looks every step up in the handle's explicit-law table first and solves the misses only (tmpc_mc_set_law) -- True, an
-    int (max_tries) or a dict(max_tries=, miss_capacity=); the result gains law_hits, law_tries, law_region (B,) and law_misses(), a
+    int (max_tries) or a dict(max_tries=, miss_capacity=, max_hops=); max_hops replaces the handle's tmpc_law_set_hops for this loop alone; the result gains law_hits, law_tries, law_region (B,) and law_misses(), a
     function that fetches the miss log (mc_law_misses)."""
     _set_loop_options(h, timing, warm_start, capture, fused, series, law)
     c, ptr = _contiguous, _ptr
@@ -1484,9 +1512,40 @@ def law_get_region(h: Handle, i: int, variant: int = 0) -> dict:
     return out
 
 
-def qp_law_eval(H, F, G, g0, Ebar, Y, Yp, words, order, P, hint=None, max_tries: int = 0, device: int = 0) -> dict:
+def law_set_hops(h: Handle, max_hops: int):
+    """include/tmpc.h: tmpc_law_set_hops -- the handle-wide bound of the hops of a search (0: none)."""
+    _law_check("tmpc_law_set_hops", lib().tmpc_law_set_hops(h.ptr, int(max_hops)), h)
+
+
+def law_get_hops(h: Handle) -> int:
+    n = C.c_int(0)
+    _law_check("tmpc_law_get_hops", lib().tmpc_law_get_hops(h.ptr, C.addressof(n)), h)
+    return int(n.value)
+
+
+HOP_STATS = ("chain_hits", "chain_tests", "ended_absent", "ended_cap", "ended_cycle", "ended_param_row")
+
+
+def law_hop_stats(h: Handle, variant: int = 0, clear: bool = False):
+    """include/tmpc.h: tmpc_law_get_hop_stats -> the six counters (6,) int64, in the order of HOP_STATS; clear: tmpc_law_clear_hop_stats after."""
+    st = np.zeros(6, np.int64)
+    _law_check("tmpc_law_get_hop_stats", lib().tmpc_law_get_hop_stats(h.ptr, int(variant), st.ctypes.data), h)
+    if clear:
+        _law_check("tmpc_law_clear_hop_stats", lib().tmpc_law_clear_hop_stats(h.ptr, int(variant)), h)
+    return st
+
+
+def law_find_key(h: Handle, key: int, variant: int = 0) -> int:
+    """include/tmpc.h: tmpc_law_find_key -> the id stored under the key (explicit_law.signature_key) in the table's hash, or -1."""
+    i = C.c_int32(-1)
+    _law_check("tmpc_law_find_key", lib().tmpc_law_find_key(h.ptr, int(variant), C.c_uint64(int(key)), C.addressof(i)), h)
+    return int(i.value)
+
+
+def qp_law_eval(H, F, G, g0, Ebar, Y, Yp, words, order, P, hint=None, max_tries: int = 0, device: int = 0, max_hops=None, want_stats: bool = False) -> dict:
     """include/tmpc.h: tmpc_qp_law_eval -- the law kernel on raw condensed data, without a handle -> y (B, ny), region, tries; arguments as
-    LinearMPCOverNetworks.explicit_law.locate on a table of region_law(model, decode(words[i]))."""
+    LinearMPCOverNetworks.explicit_law.locate on a table of region_law(model, decode(words[i])).  max_hops not None: tmpc_qp_law_eval_hops,
+    with want_stats the six counters as `stats` (6,) int64."""
     H, F, G, g0, Ebar, Y, Yp = (_contiguous(a) for a in (H, F, G, g0, Ebar, Y, Yp))
     nv, npar = F.shape
     nc, ny = g0.shape[0], Y.shape[0]
@@ -1497,9 +1556,14 @@ def qp_law_eval(H, F, G, g0, Ebar, Y, Yp, words, order, P, hint=None, max_tries:
     B = P.shape[0]
     hint = None if hint is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hint, dtype=np.int32).reshape(-1), (B,)))
     out = dict(y=np.empty((B, ny)), region=np.empty(B, np.int32), tries=np.empty(B, np.int32))
-    rc = lib().tmpc_qp_law_eval(int(device), nv, nc, npar, ny, H.ctypes.data, F.ctypes.data, G.ctypes.data if nc else None, g0.ctypes.data if nc else None,
-                                Ebar.ctypes.data if nc else None, Y.ctypes.data, Yp.ctypes.data, words.shape[0], words.ctypes.data if words.size else None,
-                                order.shape[0], order.ctypes.data if order.size else None, B, P.ctypes.data, _ptr(hint), int(max_tries),
-                                out["y"].ctypes.data, out["region"].ctypes.data, out["tries"].ctypes.data)
-    _law_check("tmpc_qp_law_eval", rc)
+    args = (int(device), nv, nc, npar, ny, H.ctypes.data, F.ctypes.data, G.ctypes.data if nc else None, g0.ctypes.data if nc else None,
+            Ebar.ctypes.data if nc else None, Y.ctypes.data, Yp.ctypes.data, words.shape[0], words.ctypes.data if words.size else None,
+            order.shape[0], order.ctypes.data if order.size else None, B, P.ctypes.data, _ptr(hint), int(max_tries),
+            out["y"].ctypes.data, out["region"].ctypes.data, out["tries"].ctypes.data)
+    if max_hops is None:
+        _law_check("tmpc_qp_law_eval", lib().tmpc_qp_law_eval(*args))
+    else:
+        if want_stats:
+            out["stats"] = np.zeros(6, np.int64)
+        _law_check("tmpc_qp_law_eval_hops", lib().tmpc_qp_law_eval_hops(*args, int(max_hops), out["stats"].ctypes.data if want_stats else None))
     return out

@@ -80,11 +80,70 @@ def region_law(model: dict, rows):
     return dict(rows=A, Ky=Y @ Kz + Yp, ky=Y @ kz, Kz=Kz, kz=kz, Kl=Kl, kl=kl, S=S, s=s)
 
 
-def locate(table, P, hint=None, order=None, max_tries: int = 0):
-    """The kernel's search: per instance the hint first where it is a valid id, then `order` (default: 0 .. R-1) without the hint, at most
-    max_tries candidates (<= 0: all); the first region with S p + s >= 0 in every row wins.  An entry of `table` that is None (a refused
-    set) holds no p.  -> region (B,) int32 (-1: a miss), tries (B,) int32, y (B, ny) (NaN for a miss and for a non-finite p, whose
-    tries are 0)."""
+_M64 = (1 << 64) - 1
+HOP_STATS = ("chain_hits", "chain_tests", "ended_absent", "ended_cap", "ended_cycle", "ended_param_row")      # include/tmpc.h: tmpc_law_get_hop_stats
+
+
+def key_bit(i: int) -> int:
+    """include/tmpc.h: z(i), splitmix64 of i + 1."""
+    x = ((int(i) + 1) * 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def signature_key(rows) -> int:
+    """The key of the working set `rows` (include/tmpc.h): the XOR of z(i) over its rows; 0 for the empty set."""
+    k = 0
+    for i in set(int(i) for i in rows):
+        k ^= key_bit(i)
+    return k
+
+
+NO_KEY = _M64                             # csrc/tmpc_law.hpp: LAW_NO_KEY, the key of a region without a working set
+
+
+def hash_slots(keys):
+    """The open-addressed table over the regions' keys as csrc/tmpc_law.cpp builds it (include/tmpc.h): n_slot the power of two
+    >= max(64, 2 R), ids in increasing order at key & (n_slot - 1) with linear probing, a key already present keeps the earlier id, a
+    region without a key (NO_KEY) is left out -> slot (n_slot,) int32, -1: empty."""
+    n = 64
+    while n < 2 * len(keys):
+        n *= 2
+    slot = np.full(n, -1, np.int32)
+    for i, k in enumerate(keys):
+        if int(k) == NO_KEY:
+            continue
+        j = int(k) & (n - 1)
+        while slot[j] >= 0 and int(keys[slot[j]]) != int(k):
+            j = (j + 1) & (n - 1)
+        if slot[j] < 0:
+            slot[j] = i
+    return slot
+
+
+def hash_find(keys, slot, key: int) -> int:
+    """The lookup of the kernel (csrc/tmpc_law_wave.hpp: law_lookup): the id under `key`, -1 where the probe reaches an empty slot."""
+    n = len(slot)
+    j = int(key) & (n - 1)
+    for _ in range(n):
+        if slot[j] < 0:
+            return -1
+        if int(keys[slot[j]]) == int(key):
+            return int(slot[j])
+        j = (j + 1) & (n - 1)
+    return -1
+
+
+def locate(table, P, hint=None, order=None, max_tries: int = 0, max_hops: int = 0, nc=None, stats=None):
+    """The kernel's search (csrc/tmpc_law_wave.hpp: law_find).  Per instance a chain, then a walk, at most max_tries candidates in all
+    (<= 0: all); the first region tested with S p + s >= 0 in every row wins.  The chain starts at the hint where it is a valid id, with
+    max_hops > 0 otherwise at order[0]; a region that fails hands over to the region whose working set differs in the LOWEST failing row,
+    and the chain ends -- the conditions in this order -- at a row >= nc (default: every row is a constraint's), at an entry that is None,
+    at a neighbour the table does not hold (of equal sets the first counts), at the region the chain came from, after max_hops hops, at
+    max_tries.  With max_hops = 0 the chain is the hint alone.  The walk is `order` (default: 0 .. R-1) without the chain's start.  An
+    entry of `table` that is None (a refused set) holds no p.  stats: an int64 array (6,) (HOP_STATS) that the chains add to.
+    -> region (B,) int32 (-1: a miss), tries (B,) int32, y (B, ny) (NaN for a miss and for a non-finite p, whose tries are 0)."""
     P = np.asarray(P, dtype=np.float64)
     P = P.reshape(-1, P.shape[-1])
     B, R = P.shape[0], len(table)
@@ -92,21 +151,72 @@ def locate(table, P, hint=None, order=None, max_tries: int = 0):
     hint = np.full(B, -1) if hint is None else np.broadcast_to(np.asarray(hint, dtype=np.int64).reshape(-1), (B,))
     ny = next((t["Ky"].shape[0] for t in table if t is not None), 0)
     region, tries, y = np.full(B, -1, np.int32), np.zeros(B, np.int32), np.full((B, ny), np.nan)
+    index = {}
+    if max_hops > 0:
+        for r, t in enumerate(table):
+            if t is not None:
+                index.setdefault(frozenset(int(i) for i in t["rows"]), r)
+
+    def fail_row(r, p):
+        """The lowest failing row of region r at p, -1: none."""
+        t = table[r]
+        if t is None:
+            return 0
+        bad = np.flatnonzero(~(t["S"] @ p + t["s"] >= 0.0))
+        return int(bad[0]) if len(bad) else -1
+
     for b in range(B):
         p = P[b]
         if not np.isfinite(p).all():
             continue
         hinted = 0 <= hint[b] < R
-        cand = ([int(hint[b])] if hinted else []) + [int(r) for r in order if not (hinted and r == hint[b])]
-        for r in cand:
-            if max_tries > 0 and tries[b] >= max_tries:
-                break
-            tries[b] += 1
-            t = table[r]
-            if t is not None and np.all(t["S"] @ p + t["s"] >= 0.0):
-                region[b] = r
-                y[b] = t["Ky"] @ p + t["ky"]
-                break
+        start = int(hint[b]) if hinted else (int(order[0]) if max_hops > 0 and len(order) else -1)
+        if start >= 0:
+            r, prev, hops, end = start, -1, 0, None
+            while True:
+                tries[b] += 1
+                i = fail_row(r, p)
+                if max_hops > 0 and stats is not None:
+                    stats[1] += 1
+                if i < 0:
+                    region[b], end = r, 0
+                    break
+                if max_hops <= 0:
+                    break
+                t = table[r]
+                if t is not None and i >= (len(t["s"]) if nc is None else nc):
+                    end = 5
+                    break
+                if t is None:
+                    break
+                nb = index.get(frozenset(int(j) for j in t["rows"]) ^ {i}, -1)
+                if nb < 0:
+                    end = 2
+                    break
+                if nb == prev:
+                    end = 4
+                    break
+                if hops == max_hops:
+                    end = 3
+                    break
+                if max_tries > 0 and tries[b] == max_tries:
+                    break
+                prev, r, hops = r, nb, hops + 1
+            if max_hops > 0 and stats is not None and end is not None:
+                stats[end] += 1
+        if region[b] < 0:
+            for r in order:
+                if max_tries > 0 and tries[b] >= max_tries:
+                    break
+                if r == start:
+                    continue
+                tries[b] += 1
+                if fail_row(int(r), p) < 0:
+                    region[b] = r
+                    break
+        if region[b] >= 0:
+            t = table[region[b]]
+            y[b] = t["Ky"] @ p + t["ky"]
     return region, tries, y
 
 
@@ -168,6 +278,22 @@ class ExplicitLaw:
         """The law with the solver behind it: every instance answered as by `_solve`; region >= 0 where the table answered."""
         from . import _native
         return _native.law_solve(self._h, x, ref, variant, hint, DEFAULT_MAX_TRIES if max_tries is None else max_tries, want_traj)
+
+    def set_hops(self, n: int):
+        """tmpc_law_set_hops: a search whose hint (or first candidate) fails hops to the neighbouring region across the failing row, at
+        most n times, before it walks the search order; 0: off.  Handle-wide: evaluate, solve and the closed loops through the law."""
+        from . import _native
+        _native.law_set_hops(self._h, n)
+
+    @property
+    def max_hops(self) -> int:
+        from . import _native
+        return _native.law_get_hops(self._h)
+
+    def hop_stats(self, variant: int = 0, clear: bool = False) -> dict:
+        """The chains' counters of a variant since the table was cleared (HOP_STATS); clear: zero them after reading."""
+        from . import _native
+        return dict(zip(HOP_STATS, (int(v) for v in _native.law_hop_stats(self._h, variant, clear))))
 
     def reorder(self, variant=None):
         """Sorts the search order by descending hits (ties by id); the ids stay."""

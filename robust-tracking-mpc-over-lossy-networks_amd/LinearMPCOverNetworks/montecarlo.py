@@ -346,35 +346,44 @@ class LawPackets:
 
     lookup(k, P (n, 2 nx), hint (n,), max_tries) -> (region (n,), tries (n,), y (n, ny)) for the instances of problem k, y = [u_nom
     (N nu) | x_nom0 (nx) | x_ss (nx) | u_ss (nu)]: `from_tables` builds one from numpy tables (explicit_law.region_law / locate, no
-    GPU), `from_law` from an ExplicitLaw on the device.  K: the steady-state gain of the packet's last column u_ss + K x_ss."""
+    GPU), `from_law` from an ExplicitLaw on the device.  K: the steady-state gain of the packet's last column u_ss + K x_ss.
 
-    def __init__(self, packets_fn, lookup, K, N: int, max_tries: int = 0, miss_capacity: int = 0):
+    max_hops > 0 (tmpc_law_set_hops): the lookup is called as lookup(k, P, hint, max_tries, max_hops, stats) and adds the chains' six
+    counters to stats = hop_stats[k] (explicit_law.HOP_STATS); tries include the chains' tests."""
+
+    def __init__(self, packets_fn, lookup, K, N: int, max_tries: int = 0, miss_capacity: int = 0, max_hops: int = 0):
         self._fn, self._lookup, self._K, self._N = packets_fn, lookup, np.atleast_2d(np.asarray(K, dtype=np.float64)), int(N)
-        self.max_tries, self.miss_capacity = int(max_tries), int(miss_capacity)
+        self.max_tries, self.miss_capacity, self.max_hops = int(max_tries), int(miss_capacity), int(max_hops)
+        self.hop_stats = np.zeros((2, 6), np.int64)
         self.hits = self.tries = self.region = None
         self.region_hits = [{}, {}]
         self.steps = 0               # instances seen: hits + misses
         self.n_total, self.miss_x, self.miss_ref, self.miss_variant = 0, [], [], []
 
     @classmethod
-    def from_tables(cls, packets_fn, tables, K, N, orders=None, **kw):
-        """tables: one list of explicit_law.region_law dicts per problem (a single list: problem 0)."""
+    def from_tables(cls, packets_fn, tables, K, N, orders=None, ncs=None, **kw):
+        """tables: one list of explicit_law.region_law dicts per problem (a single list: problem 0).  ncs: per problem the number of rows
+        that belong to a constraint (the rows of G; the parameter-only rows follow them) -- None: all of them; read by the hops only."""
         from .explicit_law import locate
         if len(tables) == 0 or isinstance(tables[0], dict) or tables[0] is None:
             tables = [tables]
         orders = [None] * len(tables) if orders is None else orders
+        ncs = [None] * len(tables) if ncs is None else ([ncs] * len(tables) if np.isscalar(ncs) else ncs)
 
-        def lookup(k, P, hint, max_tries):
-            return locate(tables[k], P, hint, orders[k], max_tries)
+        def lookup(k, P, hint, max_tries, max_hops=0, stats=None):
+            return locate(tables[k], P, hint, orders[k], max_tries, max_hops, ncs[k], stats)
         return cls(packets_fn, lookup, K, N, **kw)
 
     @classmethod
     def from_law(cls, mpc, law=None, **kw):
-        """The table of `law` (default mpc.explicit_law()) on the device, the solver of `mpc` behind it."""
+        """The table of `law` (default mpc.explicit_law()) on the device, the solver of `mpc` behind it.  max_hops: set on the law's
+        handle (ExplicitLaw.set_hops), whose own counters (ExplicitLaw.hop_stats) count the chains -- hop_stats here stays zero."""
         law = mpc.explicit_law() if law is None else law
         nx = mpc._nx
+        if "max_hops" in kw:
+            law.set_hops(kw["max_hops"])
 
-        def lookup(k, P, hint, max_tries):
+        def lookup(k, P, hint, max_tries, max_hops=0, stats=None):
             out = law.evaluate(P[:, :nx], P[:, nx:], variant=None if mpc._handle.nvariants == 1 else np.full(len(P), k, np.uint8),
                                hint=hint, max_tries=max_tries, want_traj=False)
             y = np.c_[out["u_nom"].reshape(len(P), -1), out["x_nom0"], out["x_ss"], out["u_ss"]]
@@ -392,7 +401,10 @@ class LawPackets:
         region, y = np.full(nb, -1, np.int32), np.full((nb, N * nu + 2 * nx + nu), np.nan)
         for k in np.unique(var):
             sel = np.flatnonzero(var == k)
-            reg, tries, yk = self._lookup(int(k), P[sel], self.region[sel], self.max_tries)
+            if self.max_hops > 0:
+                reg, tries, yk = self._lookup(int(k), P[sel], self.region[sel], self.max_tries, self.max_hops, self.hop_stats[int(k)])
+            else:
+                reg, tries, yk = self._lookup(int(k), P[sel], self.region[sel], self.max_tries)
             region[sel] = reg
             self.tries[sel] += tries
             if yk.shape[1] == y.shape[1]:            # (an empty table has no rows of y)
@@ -427,7 +439,7 @@ class LawPackets:
     def result(self) -> dict:
         """law_hits, law_tries, law_region as the device loops return them, and the miss log (dict of n_total, x_k, ref, variant)."""
         nx = self._K.shape[1]
-        return dict(law_hits=self.hits, law_tries=self.tries, law_region=self.region,
+        return dict(law_hits=self.hits, law_tries=self.tries, law_region=self.region, hop_stats=self.hop_stats,
                     misses=dict(n_total=self.n_total, x_k=np.array(self.miss_x, dtype=np.float64).reshape(-1, nx),
                                 ref=np.array(self.miss_ref, dtype=np.float64).reshape(-1, nx),
                                 variant=np.array(self.miss_variant, np.uint8)))

@@ -599,10 +599,12 @@ __device__ __forceinline__ void solve_body(
             const int np = 2 * nx;
             const bool finite = __ballot(lane < np && !law_finite(xin[lane < np ? lane : 0])) == 0ull;
             int32_t *const region = lr->region;
-            int tried = 0;
-            const int win = finite ? law_find(lr->t[0].S, lr->t[0].order, lr->t[0].R, lr->t[0].n_order, lr->t[0].nrowp, np, xin,
-                                              __builtin_amdgcn_readfirstlane(region[b]), lr->max_tries, lane, tried)
+            int tried = 0, chain_tests = 0, chain_end = LAW_HOP_NONE;
+            const int max_hops = lr->max_hops;
+            const int win = finite ? law_find(&lr->t[0], np, xin, __builtin_amdgcn_readfirstlane(region[b]), lr->max_tries, lane, tried, max_hops,
+                                              chain_tests, chain_end)
                                    : -1;
+            if (lane == 0 && max_hops > 0) law_count_hops(lr->hop_stats, chain_tests, chain_end);
             if (win >= 0) {
                 // y = Ky p + ky = [u_nom | x_nom0 | xu_ss], the lanes over its rows
                 const int ny0 = N * nu, ny = ny0 + 2 * nx + nu;

@@ -26,21 +26,69 @@ struct LawRegion {
     std::vector<double> S, K;
 };
 
+// The hops' view of a table (include/tmpc.h): the key of each region's working set and the open-addressed table of ids over the keys
+struct LawKeys {
+    std::vector<unsigned long long> key;         // [R]; tmpc::LAW_NO_KEY: a region without a working set
+    std::vector<int32_t> slot;                   // [n_slot], -1: empty
+    static size_t slots_for(size_t R) {          // the power of two >= max(64, 2 R)
+        size_t n = 64;
+        while (n < 2 * R) n *= 2;
+        return n;
+    }
+    // ids in increasing order at key & (n_slot - 1), linear probing; a key already present keeps the earlier id
+    void rebuild() {
+        const size_t n = slots_for(key.size());
+        slot.assign(n, -1);
+        for (size_t id = 0; id < key.size(); ++id) {
+            if (key[id] == tmpc::LAW_NO_KEY) continue;
+            size_t j = key[id] & (n - 1);
+            while (slot[j] >= 0 && key[slot[j]] != key[id]) j = (j + 1) & (n - 1);
+            if (slot[j] < 0) slot[j] = static_cast<int32_t>(id);
+        }
+    }
+    int32_t find(unsigned long long k) const {
+        if (slot.empty()) return -1;
+        const size_t n = slot.size();
+        for (size_t j = k & (n - 1), c = 0; c < n; ++c, j = (j + 1) & (n - 1)) {
+            if (slot[j] < 0) return -1;
+            if (key[slot[j]] == k) return slot[j];
+        }
+        return -1;
+    }
+};
+
+unsigned long long key_of_words(const uint32_t *words, int nw) {
+    unsigned long long k = 0;
+    for (int w = 0; w < nw; ++w)
+        for (int bit = 0; bit < 32; ++bit)
+            if (words[w] >> bit & 1u) k ^= tmpc::law_key_bit(w * 32 + bit);
+    return k;
+}
+
 struct LawVariant {
     bool ready = false;
     LawModel m;
     std::vector<LawRegion> regions;
     std::map<std::vector<uint32_t>, int32_t> index;
     std::vector<int32_t> order;
+    LawKeys keys;                // rebuilt wherever `regions` changes; tmpc_law_reorder leaves it alone
     // the device copy: room for `cap` regions
     int cap = 0;
     double *dS = nullptr, *dK = nullptr;
     int32_t *dorder = nullptr;
     unsigned long long *dhits = nullptr;
+    unsigned long long *dkey = nullptr;          // [cap]
+    int32_t *dslot = nullptr;                    // [LawKeys::slots_for(cap)]
+    void rebuild_keys() {
+        keys.key.resize(regions.size());
+        for (size_t r = 0; r < regions.size(); ++r) keys.key[r] = key_of_words(regions[r].words.data(), static_cast<int>(regions[r].words.size()));
+        keys.rebuild();
+    }
     void release_device() {
-        for (void *p : {static_cast<void *>(dS), static_cast<void *>(dK), static_cast<void *>(dorder), static_cast<void *>(dhits)})
+        for (void *p : {static_cast<void *>(dS), static_cast<void *>(dK), static_cast<void *>(dorder), static_cast<void *>(dhits), static_cast<void *>(dkey),
+                        static_cast<void *>(dslot)})
             if (p) (void)hipFree(p);
-        dS = dK = nullptr; dorder = nullptr; dhits = nullptr; cap = 0;
+        dS = dK = nullptr; dorder = nullptr; dhits = nullptr; dkey = nullptr; dslot = nullptr; cap = 0;
     }
 };
 
@@ -48,6 +96,8 @@ struct LawState {
     LawVariant v[2];
     double *dAB = nullptr;       // A [nx][nx] | B [nx][nu] for the nominal trajectory
     tmpc::LawTable *dtab = nullptr;          // the two tables' descriptions as the kernel reads them, rewritten whenever a table changes
+    int max_hops = 0;            // tmpc_law_set_hops
+    unsigned long long *dstats = nullptr;    // [2][LAW_HOP_STATS] the hops' counters per variant, allocated with dtab
     DeviceBuffer todo[2];        // the selector bytes of a tmpc_law_solve call, one buffer per launch lane
     DeviceBuffer stage;          // the host-pointer entries' device copies
 };
@@ -59,6 +109,7 @@ void release_law(tmpc_handle *h) {
         for (LawVariant &v : s->v) v.release_device();
         if (s->dAB) (void)hipFree(s->dAB);
         if (s->dtab) (void)hipFree(s->dtab);
+        if (s->dstats) (void)hipFree(s->dstats);
         for (DeviceBuffer &b : s->todo) b.release();
         s->stage.release();
     }
@@ -266,6 +317,15 @@ int ensure_model(tmpc_handle *h, const char *who, int k) {
 
 int upload_tables(tmpc_handle *h, const char *who);
 
+// A variant's table as the kernels read it
+tmpc::LawTable describe(const LawVariant &v) {
+    tmpc::LawTable t;
+    t.nrow = v.m.nrow(); t.nrowp = v.m.nrowp(); t.R = static_cast<int>(v.regions.size()); t.n_order = static_cast<int>(v.order.size());
+    t.S = v.dS; t.K = v.dK; t.order = v.dorder; t.hits = v.dhits;
+    t.nc = v.m.nc; t.key = v.dkey; t.slot = v.dslot; t.n_slot = v.regions.empty() ? 0 : static_cast<int>(v.keys.slot.size());
+    return t;
+}
+
 // The device copy of a variant's table brought up to its host copy.  `first_new`: the regions from there on are new; a table that
 // outgrows its blocks moves to larger ones (hit counters carried over).  On TMPC_E_NOMEM nothing has changed on the device.
 int sync_device(tmpc_handle *h, const char *who, LawVariant &v, int first_new) {
@@ -278,7 +338,9 @@ int sync_device(tmpc_handle *h, const char *who, LawVariant &v, int first_new) {
         const bool ok = hipMalloc(reinterpret_cast<void **>(&n.dS), std::max<size_t>(cap * sS, 1) * d) == hipSuccess &&
                         hipMalloc(reinterpret_cast<void **>(&n.dK), cap * sK * d) == hipSuccess &&
                         hipMalloc(reinterpret_cast<void **>(&n.dorder), cap * sizeof(int32_t)) == hipSuccess &&
-                        hipMalloc(reinterpret_cast<void **>(&n.dhits), cap * sizeof(unsigned long long)) == hipSuccess;
+                        hipMalloc(reinterpret_cast<void **>(&n.dhits), cap * sizeof(unsigned long long)) == hipSuccess &&
+                        hipMalloc(reinterpret_cast<void **>(&n.dkey), cap * sizeof(unsigned long long)) == hipSuccess &&
+                        hipMalloc(reinterpret_cast<void **>(&n.dslot), LawKeys::slots_for(cap) * sizeof(int32_t)) == hipSuccess;
         if (!ok) {
             (void)hipGetLastError();
             n.release_device();
@@ -288,7 +350,7 @@ int sync_device(tmpc_handle *h, const char *who, LawVariant &v, int first_new) {
         HIP_TRY(h, hipMemset(n.dhits, 0, cap * sizeof(unsigned long long)));
         if (first_new > 0) HIP_TRY(h, hipMemcpy(n.dhits, v.dhits, first_new * sizeof(unsigned long long), hipMemcpyDeviceToDevice));
         v.release_device();
-        v.dS = n.dS; v.dK = n.dK; v.dorder = n.dorder; v.dhits = n.dhits; v.cap = cap;
+        v.dS = n.dS; v.dK = n.dK; v.dorder = n.dorder; v.dhits = n.dhits; v.dkey = n.dkey; v.dslot = n.dslot; v.cap = cap;
         first_new = 0;                    // (everything is uploaded again)
     }
     for (int r = first_new; r < R; ++r) {
@@ -296,12 +358,25 @@ int sync_device(tmpc_handle *h, const char *who, LawVariant &v, int first_new) {
         HIP_TRY(h, hipMemcpy(v.dK + r * sK, v.regions[r].K.data(), sK * d, hipMemcpyHostToDevice));
     }
     if (R) HIP_TRY(h, hipMemcpy(v.dorder, v.order.data(), R * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (R) {                              // (the keys and their hash whole: R + n_slot words)
+        HIP_TRY(h, hipMemcpy(v.dkey, v.keys.key.data(), R * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(v.dslot, v.keys.slot.data(), v.keys.slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
     return upload_tables(h, who);
 }
 
 // The tables' descriptions on the device, after any change of a table (the lanes are idle)
 int upload_tables(tmpc_handle *h, const char *who) {
     LawState &s = *h->law;
+    if (!s.dstats) {
+        if (hipMalloc(reinterpret_cast<void **>(&s.dstats), 2 * tmpc::LAW_HOP_STATS * sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            s.dstats = nullptr;
+            h->err = std::string(who) + ": out of device memory";
+            return TMPC_E_NOMEM;
+        }
+        HIP_TRY(h, hipMemset(s.dstats, 0, 2 * tmpc::LAW_HOP_STATS * sizeof(unsigned long long)));
+    }
     if (!s.dtab && hipMalloc(reinterpret_cast<void **>(&s.dtab), 2 * sizeof(tmpc::LawTable)) != hipSuccess) {
         (void)hipGetLastError();
         s.dtab = nullptr;
@@ -309,11 +384,7 @@ int upload_tables(tmpc_handle *h, const char *who) {
         return TMPC_E_NOMEM;
     }
     tmpc::LawTable t[2];
-    for (int k = 0; k < 2; ++k) {
-        const LawVariant &v = s.v[k];
-        t[k].nrow = v.m.nrow(); t[k].nrowp = v.m.nrowp(); t[k].R = static_cast<int>(v.regions.size()); t[k].n_order = static_cast<int>(v.order.size());
-        t[k].S = v.dS; t[k].K = v.dK; t[k].order = v.dorder; t[k].hits = v.dhits;
-    }
+    for (int k = 0; k < 2; ++k) t[k] = describe(s.v[k]);
     HIP_TRY(h, hipMemcpy(s.dtab, t, sizeof t, hipMemcpyHostToDevice));
     return TMPC_OK;
 }
@@ -341,11 +412,14 @@ int add_sets(tmpc_handle *h, const char *who, int k, int64_t n, const uint32_t *
     }
     const int added = static_cast<int>(v.regions.size()) - first_new;
     if (n_new) *n_new = added;
-    if (added == 0 || h->device < 0) return TMPC_OK;
+    if (added == 0) return TMPC_OK;
+    v.rebuild_keys();
+    if (h->device < 0) return TMPC_OK;
     const int rc = sync_device(h, who, v, first_new);
     if (rc == TMPC_E_NOMEM) {             // the table as it was
         for (int r = first_new; r < static_cast<int>(v.regions.size()); ++r) v.index.erase(v.regions[r].words);
         v.regions.resize(first_new);
+        v.rebuild_keys();
         v.order.erase(std::remove_if(v.order.begin(), v.order.end(), [first_new](int32_t id) { return id >= first_new; }), v.order.end());
         for (int64_t i = 0; ids && i < n; ++i)
             if (ids[i] >= first_new) ids[i] = -1;
@@ -422,6 +496,7 @@ int enqueue_law(tmpc_handle *h, Lane &lane, const char *who, const LawCall &c) {
     a.ny0 = N * nu; a.ny1 = nx; a.Y0 = c.u_nom; a.Y1 = c.x_nom0; a.Y2 = c.xu_ss;
     a.x_nom = c.x_nom; a.A = s.dAB; a.Bm = s.dAB ? s.dAB + static_cast<size_t>(nx) * nx : nullptr; a.nx = nx; a.nu = nu; a.N = N;
     a.status = c.status; a.iters = c.iters; a.region = c.region; a.tries = c.tries; a.todo = todo; a.fallback = c.fallback ? 1 : 0;
+    a.max_hops = c.loop ? c.loop->max_hops : s.max_hops; a.hop_stats = s.dstats;
     if (c.loop) {
         a.skip = c.skip; a.acc_hits = c.loop->hits; a.acc_tries = c.loop->tries;
         a.miss_n = c.loop->miss_n; a.miss_cap = c.loop->miss_cap; a.miss_p = c.loop->miss_p; a.miss_var = c.loop->miss_var;
@@ -506,6 +581,11 @@ int call_host(tmpc_handle *h, const char *who, const LawCall &c) {
     return TMPC_OK;
 }
 
+int qp_law_eval(const std::string &who, int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
+                const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order,
+                const int32_t *order, int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries,
+                int max_hops, int64_t *stats);
+
 // The start of the entries that read or change one variant's table
 int table_entry(tmpc_handle *h, const char *who, int variant) {
     if (!h) return TMPC_E_INVALID;
@@ -526,12 +606,9 @@ int law_loop_begin(tmpc_handle *h, const char *who, int nvar, tmpc::LawLoop &ll)
     for (int k = 0; k < nvar; ++k)
         if (const int rc = ensure_model(h, who, k)) return rc;
     if (const int rc = upload_tables(h, who)) return rc;
-    for (int k = 0; k < 2; ++k) {
-        const LawVariant &v = h->law->v[k];
-        tmpc::LawTable &t = ll.t[k];
-        t.nrow = v.m.nrow(); t.nrowp = v.m.nrowp(); t.R = static_cast<int>(v.regions.size()); t.n_order = static_cast<int>(v.order.size());
-        t.S = v.dS; t.K = v.dK; t.order = v.dorder; t.hits = v.dhits;
-    }
+    for (int k = 0; k < 2; ++k) ll.t[k] = describe(h->law->v[k]);
+    ll.max_hops = h->law->max_hops;       // (as it stands now: a session keeps it, like the table)
+    ll.hop_stats = h->law->dstats;
     return TMPC_OK;
 }
 
@@ -649,8 +726,57 @@ int tmpc_law_clear(tmpc_handle *h, int variant) {
     v.regions.clear();
     v.index.clear();
     v.order.clear();
+    v.rebuild_keys();
     if (h->device >= 0 && v.dhits) HIP_TRY(h, hipMemset(v.dhits, 0, v.cap * sizeof(unsigned long long)));
+    if (h->device >= 0 && h->law->dstats)
+        HIP_TRY(h, hipMemset(h->law->dstats + variant * tmpc::LAW_HOP_STATS, 0, tmpc::LAW_HOP_STATS * sizeof(unsigned long long)));
     return h->device >= 0 ? upload_tables(h, "tmpc_law_clear") : TMPC_OK;
+}
+
+int tmpc_law_set_hops(tmpc_handle *h, int max_hops) {
+    const char *who = "tmpc_law_set_hops";
+    if (!h) return TMPC_E_INVALID;
+    if (session_bars(h, who)) return TMPC_E_INVALID;
+    if (h->regulator) { h->err = std::string(who) + ": a regulator handle is not supported (tracking handles only)"; return TMPC_E_UNSUPPORTED; }
+    if (max_hops < 0) { h->err = std::string(who) + ": max_hops < 0"; return TMPC_E_INVALID; }
+    if (const int rc = ensure_state(h, who)) return rc;
+    if (const int rc = quiesce(h)) return rc;
+    h->law->max_hops = max_hops;
+    return TMPC_OK;
+}
+
+int tmpc_law_get_hops(tmpc_handle *h, int *max_hops) {
+    const char *who = "tmpc_law_get_hops";
+    if (!h) return TMPC_E_INVALID;
+    if (h->regulator) { h->err = std::string(who) + ": a regulator handle is not supported (tracking handles only)"; return TMPC_E_UNSUPPORTED; }
+    if (!max_hops) { h->err = std::string(who) + ": NULL argument"; return TMPC_E_INVALID; }
+    *max_hops = h->law ? h->law->max_hops : 0;
+    return TMPC_OK;
+}
+
+int tmpc_law_get_hop_stats(tmpc_handle *h, int variant, int64_t *stats) {
+    if (const int rc = table_entry(h, "tmpc_law_get_hop_stats", variant)) return rc;
+    if (!stats) { h->err = "tmpc_law_get_hop_stats: NULL argument"; return TMPC_E_INVALID; }
+    std::fill(stats, stats + tmpc::LAW_HOP_STATS, 0);
+    if (h->device < 0 || !h->law || !h->law->dstats) return TMPC_OK;
+    if (const int rc = quiesce(h)) return rc;
+    HIP_TRY(h, hipMemcpy(stats, h->law->dstats + variant * tmpc::LAW_HOP_STATS, tmpc::LAW_HOP_STATS * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return TMPC_OK;
+}
+
+int tmpc_law_clear_hop_stats(tmpc_handle *h, int variant) {
+    if (const int rc = table_entry(h, "tmpc_law_clear_hop_stats", variant)) return rc;
+    if (h->device < 0 || !h->law || !h->law->dstats) return TMPC_OK;
+    if (const int rc = quiesce(h)) return rc;
+    HIP_TRY(h, hipMemset(h->law->dstats + variant * tmpc::LAW_HOP_STATS, 0, tmpc::LAW_HOP_STATS * sizeof(unsigned long long)));
+    return TMPC_OK;
+}
+
+int tmpc_law_find_key(tmpc_handle *h, int variant, uint64_t key, int32_t *id) {
+    if (const int rc = table_entry(h, "tmpc_law_find_key", variant)) return rc;
+    if (!id) { h->err = "tmpc_law_find_key: NULL argument"; return TMPC_E_INVALID; }
+    *id = h->law ? h->law->v[variant].keys.find(key) : -1;
+    return TMPC_OK;
 }
 
 int tmpc_law_get_region(tmpc_handle *h, int variant, int32_t id, uint32_t *words, double *Ky, double *ky, double *S, double *s) {
@@ -683,18 +809,39 @@ int tmpc_get_param_rows(tmpc_handle *h, int variant, double *gp0, double *Ep) {
 int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G, const double *g0,
                      const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order, const int32_t *order,
                      int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries) {
-    const std::string who = "tmpc_qp_law_eval: ";
+    return qp_law_eval("tmpc_qp_law_eval: ", device, nv, nc, np, ny, H, F, G, g0, Ebar, Y, Yp, n_sets, words, n_order, order, B, P, hint, max_tries, out_y, region,
+                       tries, 0, nullptr);
+}
+
+int tmpc_qp_law_eval_hops(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G, const double *g0,
+                          const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order, const int32_t *order,
+                          int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries, int max_hops,
+                          int64_t *stats) {
+    return qp_law_eval("tmpc_qp_law_eval_hops: ", device, nv, nc, np, ny, H, F, G, g0, Ebar, Y, Yp, n_sets, words, n_order, order, B, P, hint, max_tries, out_y,
+                       region, tries, max_hops, stats);
+}
+
+}  // extern "C"
+
+namespace {
+
+int qp_law_eval(const std::string &who, int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
+                const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t n_sets, const uint32_t *words, int64_t n_order,
+                const int32_t *order, int64_t B, const double *P, const int32_t *hint, int max_tries, double *out_y, int32_t *region, int32_t *tries,
+                int max_hops, int64_t *stats) {
     auto refuse = [&](int rc, const std::string &msg) { g_create_error = who + msg; return rc; };
     if (nv < 1 || nv > tmpc::LAW_MAX_NV) return refuse(TMPC_E_INVALID, "nv = " + std::to_string(nv) + " is not in [1, " + std::to_string(tmpc::LAW_MAX_NV) + "]");
     if (nc < 0 || nc > tmpc::LAW_MAX_NC) return refuse(TMPC_E_INVALID, "nc = " + std::to_string(nc) + " is not in [0, 2^20]");
     if (np < 1 || np > tmpc::LAW_MAX_NP) return refuse(TMPC_E_INVALID, "np = " + std::to_string(np) + " is not in [1, " + std::to_string(tmpc::LAW_MAX_NP) + "]");
     if (ny < 1 || ny > tmpc::LAW_MAX_NY) return refuse(TMPC_E_INVALID, "ny = " + std::to_string(ny) + " is not in [1, " + std::to_string(tmpc::LAW_MAX_NY) + "]");
     if (B < 0) return refuse(TMPC_E_INVALID, "B < 0");
+    if (max_hops < 0) return refuse(TMPC_E_INVALID, "max_hops < 0");
     if (n_sets < 0 || n_sets > (1 << 20) || n_order < 0 || n_order > (1 << 20)) return refuse(TMPC_E_INVALID, "n_sets and n_order are in [0, 2^20]");
     if (!H || !F || (nc > 0 && (!G || !g0 || !Ebar)) || !Y || !Yp || (n_sets > 0 && nc > 0 && !words) || (n_order > 0 && !order) || !P || !out_y || !region)
         return refuse(TMPC_E_INVALID, "NULL argument");
     for (int64_t i = 0; i < n_order; ++i)
         if (order[i] < 0 || order[i] >= n_sets) return refuse(TMPC_E_INVALID, "order[" + std::to_string(i) + "] is not a set");
+    if (stats) std::fill(stats, stats + tmpc::LAW_HOP_STATS, 0);
     if (B == 0) return TMPC_OK;
     if (device < 0) return refuse(TMPC_E_DEVICE, "device < 0: the kernel runs on the GPU");
     LawModel m;
@@ -707,9 +854,12 @@ int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny,
     const size_t sS = (snp + 1) * m.nrowp(), sK = (snp + 1) * sny, R = static_cast<size_t>(n_sets), nw = m.nwords();
     std::vector<double> S(std::max<size_t>(R * sS, 1)), K(std::max<size_t>(R * sK, 1), 0.0);
     const uint32_t none = 0u;
+    LawKeys keys;
+    keys.key.assign(R, tmpc::LAW_NO_KEY);
     for (size_t r = 0; r < R; ++r) {
         LawRegion reg;
         if (build_region(m, nw ? words + r * nw : &none, reg)) {
+            keys.key[r] = key_of_words(nw ? words + r * nw : &none, static_cast<int>(nw));
             std::copy(reg.S.begin(), reg.S.end(), S.begin() + r * sS);
             std::copy(reg.K.begin(), reg.K.end(), K.begin() + r * sK);
         } else {
@@ -718,6 +868,8 @@ int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny,
             std::fill(S.begin() + r * sS + snp * m.nrowp(), S.begin() + (r + 1) * sS, -1.0);
         }
     }
+    keys.rebuild();
+    const unsigned long long zeros[tmpc::LAW_HOP_STATS] = {0, 0, 0, 0, 0, 0};
     auto fail = [&](const char *what, hipError_t e) { return refuse(TMPC_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
     if (const hipError_t e = hipSetDevice(device); e != hipSuccess) return fail("hipSetDevice", e);
     int n_cu = 0;
@@ -730,7 +882,9 @@ int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny,
     struct Part { const void *host_in; void *host_out; size_t bytes; size_t off; };
     Part parts[] = {{S.data(), nullptr, R * sS * d, 0}, {K.data(), nullptr, R * sK * d, 0}, {order, nullptr, static_cast<size_t>(n_order) * 4, 0},
                     {P, nullptr, b * snp * d, 0}, {hint, nullptr, hint ? b * 4 : 0, 0}, {nullptr, out_y, b * sny * d, 0}, {nullptr, region, b * 4, 0},
-                    {nullptr, tries, tries ? b * 4 : 0, 0}, {nullptr, nullptr, sizeof(tmpc::LawTable), 0}};
+                    {nullptr, tries, tries ? b * 4 : 0, 0}, {nullptr, nullptr, sizeof(tmpc::LawTable), 0},
+                    {keys.key.data(), nullptr, R * sizeof(unsigned long long), 0}, {keys.slot.data(), nullptr, keys.slot.size() * sizeof(int32_t), 0},
+                    {zeros, stats, sizeof zeros, 0}};
     size_t total = 0;
     for (Part &p : parts) { p.off = total; total += (p.bytes + 255) / 256 * 256; }
     if (hipMalloc(reinterpret_cast<void **>(&own.p), std::max<size_t>(total, 256)) != hipSuccess) {
@@ -747,9 +901,12 @@ int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny,
     tmpc::LawTable t;
     t.nrow = m.nrow(); t.nrowp = m.nrowp(); t.R = static_cast<int>(R); t.n_order = static_cast<int>(n_order);
     t.S = reinterpret_cast<const double *>(at(0)); t.K = reinterpret_cast<const double *>(at(1)); t.order = reinterpret_cast<const int32_t *>(at(2));
+    t.nc = nc; t.key = reinterpret_cast<const unsigned long long *>(at(9)); t.slot = reinterpret_cast<const int32_t *>(at(10));
+    t.n_slot = R ? static_cast<int>(keys.slot.size()) : 0;
     if (const hipError_t e = hipMemcpy(at(8), &t, sizeof t, hipMemcpyHostToDevice); e != hipSuccess) return fail("upload", e);
     a.t = reinterpret_cast<const tmpc::LawTable *>(at(8));
     a.B = B; a.np0 = np; a.P0 = reinterpret_cast<const double *>(at(3)); a.hint = reinterpret_cast<const int32_t *>(at(4)); a.max_tries = max_tries;
+    a.max_hops = max_hops; a.hop_stats = reinterpret_cast<unsigned long long *>(at(11));
     a.ny0 = ny; a.ny1 = 0; a.Y0 = reinterpret_cast<double *>(at(5));
     a.region = reinterpret_cast<int32_t *>(at(6)); a.tries = reinterpret_cast<int32_t *>(at(7));
     if (const hipError_t e = tmpc::launch_law(a, tmpc::law_blocks(B, n_cu), nullptr); e != hipSuccess) return fail("launch", e);
@@ -760,4 +917,4 @@ int tmpc_qp_law_eval(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny,
     return TMPC_OK;
 }
 
-}  // extern "C"
+}  // namespace

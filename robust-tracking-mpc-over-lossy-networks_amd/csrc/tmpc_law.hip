@@ -8,7 +8,9 @@
 // One wavefront per instance, LAW_WAVES instances per workgroup, a fixed grid takes the instances round robin.  Per instance:
 //
 //   1  p is read a lane per entry and checked; it goes to the wave's LDS slice, from where every lane reads it as a broadcast;
-//   2  the candidates: the hint when it is a valid id, then the search order without the hint, at most max_tries of them;
+//   2  the candidates: the hint when it is a valid id, then the search order without the hint, at most max_tries of them; with
+//      max_hops > 0 a failed hint (or first entry of the order) hops to the region across its lowest failing row first, through a hash
+//      of the working sets' keys (tmpc_law_wave.hpp: law_find);
 //   3  per candidate the lanes take the rows 64 at a time -- S is stored [np + 1][nrowp], a row per lane, so that a wave reads
 //      np + 1 runs of 512 contiguous bytes per chunk -- and a ballot rejects the candidate at the first chunk with a failing row;
 //   4  the winner's y = Ky p + ky with the lanes over the rows of y (Ky stored [np + 1][ny] for the same reason), the nominal
@@ -104,8 +106,9 @@ __global__ __launch_bounds__(LAW_THREADS) void law_kernel(const LawArgs a) {
         // ---- 2, 3: the candidates
         const LawTable t = a.t[var];
         const int h = a.hint ? a.hint[b] : -1;
-        int tried = 0;
-        const int win = finite ? law_find(t.S, t.order, t.R, t.n_order, t.nrowp, np, pv, h, a.max_tries, lane, tried) : -1;
+        int tried = 0, chain_tests = 0, chain_end = LAW_HOP_NONE;
+        const int win = finite ? law_find(&t, np, pv, h, a.max_tries, lane, tried, a.max_hops, chain_tests, chain_end) : -1;
+        if (lane == 0 && a.max_hops > 0 && a.hop_stats) law_count_hops(a.hop_stats + var * LAW_HOP_STATS, chain_tests, chain_end);
 
         // ---- 5: a miss
         if (win < 0) {
@@ -186,7 +189,7 @@ unsigned law_blocks(int64_t B, int n_cu) {
 
 hipError_t launch_law(const LawArgs &a, unsigned blocks, hipStream_t stream) {
     if (a.np < 1 || a.np > LAW_MAX_NP || a.ny < 1 || a.ny > LAW_MAX_NY || a.B < 1 || blocks < 1 || a.nvariants < 1 || a.nvariants > 2 || !a.t || !a.region ||
-        a.np0 < 0 || a.np0 > a.np || !a.P0 || (a.np0 < a.np && !a.P1))
+        a.np0 < 0 || a.np0 > a.np || !a.P0 || (a.np0 < a.np && !a.P1) || a.max_hops < 0)
         return hipErrorInvalidValue;
     if (a.x_nom && (a.nx < 1 || a.nx > LAW_MAX_NX || a.nu < 1 || a.N < 1 || a.N * a.nu > LAW_MAX_NV || a.ny0 != a.N * a.nu || a.ny1 != a.nx || !a.A || !a.Bm))
         return hipErrorInvalidValue;

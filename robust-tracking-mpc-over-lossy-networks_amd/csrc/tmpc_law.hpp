@@ -22,6 +22,18 @@ constexpr double LAW_RANK_TOL = 1e-13;   // a working set is refused when a diag
 constexpr int LAW_WAVES = 4;             // instances per workgroup, one per wavefront
 constexpr int LAW_TODO_DONE = 0xFF;      // selector byte of an instance that needs no solve
 
+// The key of a working set is the XOR of law_key_bit(i) over its rows i (include/tmpc.h: splitmix64 of i + 1; the empty set has key 0), so
+// the set across the facet of row i has the key of this one ^ law_key_bit(i), whichever side of it row i is on.
+constexpr unsigned long long law_key_bit(int i) {
+    unsigned long long x = (static_cast<unsigned long long>(i) + 1ull) * 0x9E3779B97F4A7C15ull;
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+constexpr unsigned long long LAW_NO_KEY = ~0ull;        // a region without a working set (a refused set of tmpc_qp_law_eval): no chain leaves it
+constexpr int LAW_HOP_STATS = 6;         // counters per variant: chain hits, chain tests, chains ended by an absent neighbour / the cap / a two-cycle / a parameter-only row
+
 // The regions of one problem variant on the device.  Row i of region r is  sum_q S[r][q][i] p_q + S[r][np][i] >= 0.
 struct LawTable {
     int nrow = 0;            // nc + npar
@@ -32,6 +44,12 @@ struct LawTable {
     const double *K = nullptr;        // [R][np + 1][ny]: y_j = sum_q K[r][q][j] p_q + K[r][np][j]
     const int32_t *order = nullptr;   // [n_order] region ids
     unsigned long long *hits = nullptr;       // [R] or NULL
+    // the hops (LawArgs::max_hops): rows < nc belong to a working set's bit; the key of each region and the open-addressed table of ids
+    // over them (-1: empty; n_slot the power of two >= max(64, 2 R), ids inserted in increasing order at key & (n_slot - 1), linear probing)
+    int nc = 0;
+    const unsigned long long *key = nullptr;  // [R] or NULL: no hops
+    const int32_t *slot = nullptr;            // [n_slot]
+    int n_slot = 0;
 };
 
 // One launch over B instances.  All pointers are device pointers.
@@ -66,6 +84,8 @@ struct LawArgs {
     long long miss_cap;      // rows of the log; the counter goes on counting beyond
     double *miss_p;          // [miss_cap][np]
     uint8_t *miss_var;       // [miss_cap]
+    int max_hops = 0;        // > 0: a failed hint (or order[0]) hops to the neighbour across its lowest failing row, at most so often (tmpc_law_wave.hpp)
+    unsigned long long *hop_stats = nullptr;  // [nvariants][LAW_HOP_STATS] or NULL; touched with max_hops > 0 only
 };
 
 // What the fused closed loop (closed_loop_law, tmpc_fused_law.hip) reads of the law: in device memory, read through the constant
@@ -80,6 +100,8 @@ struct LawLoop {
     long long miss_cap;
     double *miss_p;          // [miss_cap][np]
     uint8_t *miss_var;       // [miss_cap]
+    int max_hops = 0;        // as LawArgs
+    unsigned long long *hop_stats = nullptr;  // [2][LAW_HOP_STATS] or NULL
 };
 
 unsigned law_blocks(int64_t B, int n_cu);

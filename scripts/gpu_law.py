@@ -78,6 +78,24 @@ def measure(label, mpc, X, R, pool, reps, lines):
     _native.law_reorder(h)
     t = timed(h, ev, reps)
     say("law eval, no hints, reordered", t, f"   mean tries {tr.cpu().numpy().mean():.1f}")
+    # the hops (tmpc_law_set_hops): the hint is the region of the state before -- a closed loop's hint where the region changes every step
+    prev = dev(np.roll(region, 1).astype(np.int32))
+    t0 = None
+    for mh in (0, 4, 16, 64):
+        _native.law_set_hops(h, mh)
+        _native.law_hop_stats(h, 0, clear=True)
+        t = timed(h, lambda: ev(prev.data_ptr()), reps)
+        hs = _native.law_hop_stats(h, 0, clear=True)
+        tries = float(tr.cpu().numpy().mean())
+        if mh == 0:
+            t0, tries0 = np.median(t), tries
+            say("law eval, hint of the state before, max_hops 0", t, f"   mean tries {tries:.1f}")
+        else:
+            n = max(1, int(hs[0] + hs[2] + hs[3] + hs[4] + hs[5]))
+            say(f"law eval, hint of the state before, max_hops {mh}", t, f"   mean tries {tries:.1f}; chains: hits {hs[0] / n:.1%}, absent {hs[2] / n:.1%}, cap "
+                f"{hs[3] / n:.1%}, two-cycle {hs[4] / n:.1%}, parameter row {hs[5] / n:.1%}, tests per chain {hs[1] / n:.2f}; per instance "
+                f"{1e3 * (np.median(t) - t0) / B:+.3f} us against max_hops 0 at {tries - tries0:+.2f} tries")
+    _native.law_set_hops(h, 0)
     t_s0 = timed(h, sv, reps)
     say("law solve, 0 % misses", t_s0)
     # take out the regions that answer about 10 % of the batch (the least hit first), then all of them

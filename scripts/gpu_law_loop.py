@@ -8,7 +8,9 @@ device, so that a call uploads nothing.  Each loop is repeated `reps` times afte
           per-step loop around the law's and the solve launches of every step, summed -- the state-machine launches lie outside;
   wall -- the host's clock around the call, everything included (the steps/s figure is B T / median wall).
 Per horizon, cold and warm: the loops that solve every step (fused, per step: the references), then through the table of a pilot sweep
-(its first --pilot trajectories) at max_tries 1, 4, 16 and all and, with all, after tmpc_law_reorder, fused and per step, and through an empty table (the cost of the law phase on a loop that never hits)."""
+(its first --pilot trajectories) at max_tries 1, 4, 16 and all and, with all, after tmpc_law_reorder, fused and per step, and through an empty table (the cost of the law phase on a loop that never hits).
+Before and after the reorder, with every candidate allowed: the search with hops (tmpc_law_set_hops) at max_hops 0, 4, 16 and 64, the four
+settings INTERLEAVED call by call, with the chains' counters of the timed calls."""
 import argparse
 import os
 import sys
@@ -37,21 +39,54 @@ def timed(mpc, reps, **kw):
     return np.asarray(dev), np.asarray(wall), out
 
 
+def timed_hops(mpc, table, reps, hops, **kw):
+    """One call per setting of max_hops in turn, reps + 3 rounds (the first three are warm-up) -> per setting (dev, wall, out, counters of the timed calls)."""
+    h = mpc._handle
+    got = {mh: ([], [], None, np.zeros(6, np.int64)) for mh in hops}
+    for i in range(reps + 3):
+        for mh in hops:
+            table.set_hops(mh)
+            table.hop_stats(clear=True)
+            _native.kernel_ms_total(h, reset=True)
+            t0 = time.perf_counter()
+            out = mpc.run_closed_loop(**kw)
+            dt = time.perf_counter() - t0
+            ms, _ = _native.kernel_ms_total(h, reset=True)
+            if i >= 3:
+                dev, wall, _, st = got[mh]
+                dev.append(ms)
+                wall.append(1e3 * dt)
+                st += np.array(list(table.hop_stats().values()), np.int64)
+                got[mh] = (dev, wall, out, st)
+    table.set_hops(0)
+    return {mh: (np.asarray(d), np.asarray(w_), o, st) for mh, (d, w_, o, st) in got.items()}
+
+
 def measure(N, B, T, reps, lines, n_pilot):
     mpc, w = common.make_mpc("cartpole", N, True, create=True)
     law = mpc.explicit_law()
     base = dict(p_loss=(np.arange(B) % 10) / 10.0, ref=np.where(np.arange(T) < T // 2, 0.5, -0.3), device_rng=(11, 0, w["w_bound"]))
 
-    def say(name, dev, wall, out, ref_dev=None):
+    def say(name, dev, wall, out, ref_dev=None, hop=None):
         steps = B * T
         extra = ""
         if "law_hits" in out:
             extra = f"  hit rate {out['law_hits'].sum() / steps:6.1%}  mean tries {out['law_tries'].sum() / steps:6.2f}"
         if ref_dev is not None:
             extra += f"  outside the reference's spread on the faster side: {bool(dev.max() < ref_dev.min())}"
-        lines.append(f"N = {N:2d} B = {B:4d} T = {T:3d}  {name:44s} dev min {dev.min():9.3f} median {np.median(dev):9.3f} max {dev.max():9.3f} ms   "
+        if hop is not None and hop[1] > 0:
+            calls, hits, chains = len(dev), max(1, int(out["law_hits"].sum())), steps * len(dev)
+            extra += (f"  chain hits {hop[0] / calls / hits:6.1%} of hits, hops per chain hit {(hop[1] - chains) / max(1, hop[0]):5.2f}, chains ended: absent "
+                      f"{hop[2] / chains:6.1%} cap {hop[3] / chains:6.1%} two-cycle {hop[4] / chains:6.1%} parameter row {hop[5] / chains:6.1%}")
+        lines.append(f"N = {N:2d} B = {B:4d} T = {T:3d}  {name:48s} dev min {dev.min():9.3f} median {np.median(dev):9.3f} max {dev.max():9.3f} ms   "
                      f"wall median {np.median(wall):9.3f} ms   {steps / (1e-3 * np.median(wall)):12.0f} MPC steps/s{extra}")
         print(lines[-1], flush=True)
+
+    def hop_rows(tag, what, warm, refs):
+        """The table as it stands at max_hops 0 / 4 / 16 / 64, the four settings interleaved, fused and per step."""
+        for fused in ("on", "off"):
+            for mh, (dev, wall, out, st) in timed_hops(mpc, law, reps, (0, 4, 16, 64), fused=fused, warm_start=warm, law=True, **base).items():
+                say(f"{tag}, {what}, max_hops {mh:2d}, fused {fused}", dev, wall, out, refs[fused], st)
 
     for warm in (False, True):
         tag = "warm" if warm else "cold"
@@ -74,11 +109,13 @@ def measure(N, B, T, reps, lines, n_pilot):
             for fused in ("on", "off"):
                 dev, wall, out = timed(mpc, reps, fused=fused, warm_start=warm, law=mt if mt else True, **base)
                 say(f"{tag}, pilot's table, max_tries {mt if mt else 'all'}, fused {fused}", dev, wall, out, refs[fused])
+        hop_rows(tag, "pilot's table", warm, refs)
         # the search order by the hit counters of the sweeps so far (tmpc_law_reorder): the walk behind a failed hint gets shorter
         law.reorder()
         for fused in ("on", "off"):
             dev, wall, out = timed(mpc, reps, fused=fused, warm_start=warm, law=True, **base)
             say(f"{tag}, pilot's table reordered, all, fused {fused}", dev, wall, out, refs[fused])
+        hop_rows(tag, "reordered", warm, refs)
     mpc._close()
 
 
