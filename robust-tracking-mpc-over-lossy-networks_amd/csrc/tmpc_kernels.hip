@@ -196,6 +196,14 @@ struct Shape {
     static constexpr int NB = (NV_ + 1 + 15) / 16;
     static constexpr int LDG = 16 * NB + 1;
     static constexpr int NTL = NB * (NB + 1) / 2;                 // 16 x 16 tiles of the lower triangle
+    // The G'DG pass of sweep A on 4 x 4 x 4 matrix blocks (wv::gdg_blocks: the 6 ... 9 blocks of the lower triangle in two or three
+    // v_mfma_f64_4x4x4_4b_f64 per k-step, 17 cycles each) instead of one 16 x 16 tile (64 cycles): the cart-pole shapes up to twelve
+    // variables, which were measured.  The dense-only shapes and NV >= 15 multiply tiles as before.
+#ifdef TMPC_NO_MFMA_BLOCKS
+    static constexpr bool MFMA_BLOCKS = false;      // diagnostic builds: every shape multiplies tiles
+#else
+    static constexpr bool MFMA_BLOCKS = NV_ <= 12 && KC_ > 0;
+#endif
     // first row side and number of sides of dense functional slot kd / factored functional slot kc
     static constexpr int dbase(int kd) { return kd < DP_ ? 2 * kd : 2 * DP_ + (kd - DP_); }
     static constexpr int dsides(int kd) { return kd < DP_ ? 2 : 1; }
@@ -286,6 +294,8 @@ __device__ __forceinline__ double fact_dot(const double *Hct, const double *c, i
 // (row NV: t_f); B operand (4 x 16): g_f[16 J + j], j = l % 16 -- the same LDS value, read once.  C/D: lane l holds
 // rows (l / 16) + 4 reg, column l % 16 of a tile.  The tiles go to LDS as full rows of M (mt, stride LDM) and row NV
 // as the vector G't (gdr).
+// Shape::MFMA_BLOCKS: the same product from the 4 x 4 blocks of its lower triangle, four independent blocks per
+// v_mfma_f64_4x4x4_4b_f64 (wv::gdg_blocks, tmpc_wave.hpp): (D, t) are staged as here, and the result lands where the tiles put it.
 typedef double v4d __attribute__((ext_vector_type(4)));
 template <class SH>
 __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const double (&s)[SH::RS], const double (&lam)[SH::RS],
@@ -311,6 +321,11 @@ __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const d
         dtw[2 * (kd * WAVE + lane) + 1] = t;
     });
     wave_lds_fence();
+    static_assert(WaveLds<SH>::RED >= 2 * (SH::NDP + 4), "look-ahead of the MFMA pass stays inside the transposition tile");
+    if constexpr (SH::MFMA_BLOCKS) {
+        wv::gdg_blocks<NV, LDG, SH::LDM>(Gt, nks, dtw, mt, gdr, lane);
+        return;
+    }
     const int c = lane & 15, kq = lane >> 4;
     const double tmask = (c == CT) ? 1.0 : 0.0;
     // Two k-steps in flight: the operands of step ks + 1 are on their way while step ks multiplies (an LDS round trip per
@@ -356,7 +371,6 @@ __device__ __forceinline__ void sweep_a_dense(const double *Gt, int nks, const d
         }
         if (ks < nks) multiply(std::integral_constant<int, 0>{}, D0, t0, g0);
     }
-    static_assert(WaveLds<SH>::RED >= 2 * (SH::NDP + 4), "look-ahead of the MFMA pass stays inside the transposition tile");
     double *mtk = mt + kq * SH::LDM + c;
 #pragma unroll
     for (int I = 0; I < NB; ++I)
@@ -512,10 +526,36 @@ __device__ __forceinline__ void solve_body(
     static_assert(NCS == FC || (SH::SKIPS && NCS == FC - 1), "the slot counts a layout of this shape can have");
 
     // ---- stage the shared model once per workgroup (coalesced, L2-resident source)
-    for (int i = tid; i < (grows + ZERO_ROWS) * LDG; i += blockDim.x) Gt[i] = (i < grows * LDG) ? qp.Gt[i] : 0.0;
-    for (int i = tid; i < KC * NCCP; i += blockDim.x) Hct[i] = qp.Hct[i];
-    for (int i = tid; i < KC * NV; i += blockDim.x) Psi[i] = qp.Psi[i];
-    for (int i = tid; i < NV * NV; i += blockDim.x) { const int r_ = i / NV, c_ = i - r_ * NV; Hs[r_ * SH::LDH + c_] = qp.Hs[i]; Hinv[r_ * SH::LDH + c_] = qp.Hinv[i]; }
+    // (the block form of sweep A's matrix pass reads a ONE in column NV of every functional: wv::gdg_blocks.  No other reader goes past column NV - 1.)
+    // Every thread issues ALL its loads, then stores: one L2 round trip in front of the barrier instead of one per trip of five loops
+    // (eight in the bench shape) -- nothing else runs on the CU meanwhile, and the next launch's workgroup waits for this one to leave.
+    // The thread count is the launch's, WAVE * WPB, so that the trips are counted at compile time.
+    {
+        constexpr int NT = WAVE * WPB;
+        constexpr int TG = ((NDP + ZERO_ROWS) * LDG + NT - 1) / NT, TH = (KC * NCCP + NT - 1) / NT, TP = (KC * NV + NT - 1) / NT, TS = (NV * NV + NT - 1) / NT;
+        const int ng = grows * LDG, nz = (grows + ZERO_ROWS) * LDG;
+        double vg[TG > 0 ? TG : 1], vh[TH > 0 ? TH : 1], vp[TP > 0 ? TP : 1], vs[TS], vi[TS];
+#pragma unroll
+        for (int u = 0; u < TG; ++u) { const int i = tid + u * NT; vg[u] = i < ng ? qp.Gt[i] : 0.0; }
+#pragma unroll
+        for (int u = 0; u < TH; ++u) { const int i = tid + u * NT; vh[u] = i < KC * NCCP ? qp.Hct[i] : 0.0; }
+#pragma unroll
+        for (int u = 0; u < TP; ++u) { const int i = tid + u * NT; vp[u] = i < KC * NV ? qp.Psi[i] : 0.0; }
+#pragma unroll
+        for (int u = 0; u < TS; ++u) { const int i = tid + u * NT; vs[u] = i < NV * NV ? qp.Hs[i] : 0.0; vi[u] = i < NV * NV ? qp.Hinv[i] : 0.0; }
+#pragma unroll
+        for (int u = 0; u < TG; ++u) { const int i = tid + u * NT; if (i < nz) Gt[i] = (SH::MFMA_BLOCKS && i < ng && i % LDG == NV) ? 1.0 : vg[u]; }
+        for (int i = tid + TG * NT; i < nz; i += NT) Gt[i] = i < ng ? qp.Gt[i] : 0.0;      // (more functionals than the shape's slots hold: none)
+#pragma unroll
+        for (int u = 0; u < TH; ++u) { const int i = tid + u * NT; if (i < KC * NCCP) Hct[i] = vh[u]; }
+#pragma unroll
+        for (int u = 0; u < TP; ++u) { const int i = tid + u * NT; if (i < KC * NV) Psi[i] = vp[u]; }
+#pragma unroll
+        for (int u = 0; u < TS; ++u) {
+            const int i = tid + u * NT, r_ = i / NV, c_ = i - r_ * NV;
+            if (i < NV * NV) { Hs[r_ * SH::LDH + c_] = vs[u]; Hinv[r_ * SH::LDH + c_] = vi[u]; }
+        }
+    }
     __syncthreads();
 
     double *red = wbase + wave * WL::TOTAL;       // transposition tile / refinement workspace

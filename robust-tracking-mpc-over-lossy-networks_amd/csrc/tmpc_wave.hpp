@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include <cstdint>
 #include <utility>
 
 namespace tmpc {
@@ -530,6 +531,170 @@ template <int N>
 __device__ __forceinline__ double lanes_backsub_lane(const double (&row)[N], double b, double dinv, int lane) {
     if constexpr (N <= DPP_ROW) return rows16_backsub_lane<N>(row, b, dinv, lane);
     else return rows_backsub_lane<N>(row, b, dinv, lane);
+}
+
+// ---- v_mfma_f64_4x4x4_4b_f64: four INDEPENDENT 4 x 4 x 4 products D_b = A_b B_b + C_b (b = 0 .. 3) per instruction, one double per
+// lane and operand.  Lane maps as probed on the device with index-coded operands (tests/wavecheck/mfmablocks.hip,
+// tests/test_mfma_blocks_gpu.py; they are NOT those of the other data types): with block b = (lane >> 2) & 3 on every operand,
+//   A: lane 16 k + 4 b + i holds A_b[i][k]      B: lane 16 k + 4 b + j holds B_b[k][j]      C / D: lane 16 i + 4 b + j holds D_b[i][j]
+// i.e. `lane & 3` is the row of A and the column of B and D, `lane >> 4` is k on A and B and the row on C / D.  The host model sums
+// k = 0 .. 3 in order by fused multiply-adds starting from C.
+constexpr int mb_block(int lane) { return (lane >> 2) & 3; }
+constexpr int mb_minor(int lane) { return lane & 3; }
+constexpr int mb_major(int lane) { return lane >> 4; }
+__device__ __forceinline__ double mfma_blocks(double a, double b, double c) {
+#ifdef TMPC_HOST_SIM
+    sim::Slot s{};
+    s.d[0] = a;
+    s.d[1] = b;
+    const sim::Slot *all = sim::wave_meet(sim::OP_MFMA, s);
+    const int l = sim::cur_lane(), base = 4 * mb_block(l), i = mb_major(l), j = mb_minor(l);
+    double acc = c;
+    for (int k = 0; k < 4; ++k) acc = std::fma(all[16 * k + base + i].d[0], all[16 * k + base + j].d[1], acc);
+    return acc;
+#else
+    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
+#endif
+}
+
+// The product of sweep A's dense pass on those blocks:
+//          [ G'DG   ]     [ (D.G)' ]
+//          [ (G't)' ]  =  [  t'    ]  G         NV + 1 rows by NV columns, the NV x NV part symmetric
+// needs the 4 x 4 blocks (I, J), J <= I, of its lower triangle only -- six of them for NV = 11, two instructions per k-step, where one
+// v_mfma_f64_16x16x4_f64 computes the sixteen blocks of a whole tile in four times an instruction's time.
+// Gt: the functionals row-major in LDS, [4 nks + 4][LDG]; column NV holds ONE in the rows of the functionals, and the four rows behind
+// the last functional are zero.  dtw: (D, t) of functional f at dtw[2 f], dtw[2 f + 1], with eight more readable doubles behind the last.
+// k-step ks multiplies the functionals 4 ks .. 4 ks + 3: the lane reads f = 4 ks + (lane >> 4).  Its A entry is D_f g_f[row] -- and
+// t_f g_f[NV] = t_f on row NV: the lane picks D or t by the ADDRESS it reads, a multiply and no select --, its B entry g_f[column].
+// Blocks to instructions: see GdgBlocks::slotq.  Two k-steps are in flight -- the operands of step ks + 1 are on their way while step ks
+// multiplies; the look-ahead reads k-step nks at most and never multiplies it -- and even and odd steps accumulate into registers of
+// their own, so that successive matrix instructions do not wait for each other's result.  Four k-steps per trip of the loop: the lane's
+// addresses (one per operand and instruction: the rows and columns of its blocks differ from lane to lane) are bumped once per trip.
+// The result goes to mt ([NV][LDM]) as BOTH triangles from the lower one (equal bit for bit), row NV to gdr[0 .. NV).
+// An LDS address the compiler takes as it is: one 32-bit register, the k-steps of a trip at immediate offsets from it.  (Left to itself it
+// keeps the arrays' common base and adds the array's offset in the workgroup's LDS -- a literal beyond the 64 KiB an immediate reaches --
+// in front of every load: 26 additions per trip of the loop below instead of 6.)
+#ifdef TMPC_HOST_SIM
+typedef const double *lds_cptr;
+__device__ __forceinline__ lds_cptr lds_opaque(const double *p) { return p; }
+#else
+typedef const __attribute__((address_space(3))) double *lds_cptr;
+__device__ __forceinline__ lds_cptr lds_opaque(const double *p) {
+    unsigned a = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_cptr)p));
+    asm("" : "+v"(a));
+    return reinterpret_cast<lds_cptr>(static_cast<uintptr_t>(a));
+}
+#endif
+template <int NV>
+struct GdgBlocks {
+    static constexpr int NBR = (NV + 1 + 3) / 4, NBC = (NV + 3) / 4;             // block rows (NV + 1 rows), block columns
+    static constexpr int first(int I) { return I <= NBC ? I * (I + 1) / 2 : NBC * (NBC + 1) / 2 + (I - NBC) * NBC; }      // index of block (I, 0)
+    static constexpr int NBLK = first(NBR);
+    static constexpr int NI = (NBLK + 3) / 4;                                   // instructions per k-step
+    static constexpr int brow(int q) { int I = 0; while (first(I + 1) <= q) ++I; return I; }
+    static constexpr int bcol(int q) { return q - first(brow(q)); }
+    // block of slot bs of instruction n, row-major in the lower triangle: the LAST instruction holds the last four blocks, so that the
+    // blocks of the last block row -- the only ones with row NV -- share as few instructions as can be; the spare slots are the first of
+    // instruction 0 (q < 0: they repeat block 0 and are not stored)
+    static constexpr int slotq(int n, int bs) { return NBLK - 4 * (NI - n) + bs; }
+    static constexpr int clampq(int q) { return q < 0 ? 0 : q; }
+    static constexpr bool takes_t(int n) { return brow(clampq(slotq(n, 3))) == NV / 4; }
+    static constexpr bool any_plain() { for (int n = 0; n < NI; ++n) if (!takes_t(n)) return true; return false; }
+};
+template <int NV, int LDG, int LDM>
+__device__ __forceinline__ void gdg_blocks(const double *Gt, int nks, const double *dtw, double *mt, double *gdr, int lane) {
+    using GB = GdgBlocks<NV>;
+    constexpr int NI = GB::NI;
+    static_assert(4 * GB::NBR <= LDG, "the rows of the last block row read columns of G that are staged");
+    const int kq = mb_major(lane), bs = mb_block(lane), r = mb_minor(lane);
+    // first row / column of the lane's block in instruction n
+    int r0[NI], c0[NI];
+    static_for_n<NI>([&](auto n_) {
+        constexpr int n = decltype(n_)::value;
+        constexpr int q0 = GB::clampq(GB::slotq(n, 0)), q1 = GB::clampq(GB::slotq(n, 1)), q2 = GB::clampq(GB::slotq(n, 2)), q3 = GB::clampq(GB::slotq(n, 3));
+        r0[n] = 4 * (bs == 0 ? GB::brow(q0) : bs == 1 ? GB::brow(q1) : bs == 2 ? GB::brow(q2) : GB::brow(q3));
+        c0[n] = 4 * (bs == 0 ? GB::bcol(q0) : bs == 1 ? GB::bcol(q1) : bs == 2 ? GB::bcol(q2) : GB::bcol(q3));
+    });
+    double acc[2][NI];
+#pragma unroll
+    for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+        for (int n = 0; n < NI; ++n) acc[h2][n] = 0.0;
+    // the multiplier of the A entry (D, or t on row NV), the A entry's g and the B entry's g: one address each per instruction
+    lds_cptr pd = lds_opaque(dtw + 2 * kq), px[NI], pa[NI], pb[NI];
+#pragma unroll
+    for (int n = 0; n < NI; ++n) {
+        px[n] = GB::takes_t(n) ? lds_opaque(dtw + 2 * kq + (r0[n] + r == NV ? 1 : 0)) : pd;
+        pa[n] = lds_opaque(Gt + kq * LDG + r + r0[n]);
+        pb[n] = lds_opaque(Gt + kq * LDG + r + c0[n]);
+    }
+    struct Ops { double D, x[NI], ga[NI], gb[NI]; };
+    auto fetch = [&](Ops &o, auto u_) {                 // the k-step u steps behind the addresses
+        constexpr int u = decltype(u_)::value;
+        if constexpr (GB::any_plain()) o.D = pd[8 * u];
+#pragma unroll
+        for (int n = 0; n < NI; ++n) {
+            if (GB::takes_t(n)) o.x[n] = px[n][8 * u];
+            o.ga[n] = pa[n][4 * LDG * u];
+            o.gb[n] = pb[n][4 * LDG * u];
+        }
+    };
+    auto bump = [&](auto u_) {
+        constexpr int u = decltype(u_)::value;
+        pd += 8 * u;
+#pragma unroll
+        for (int n = 0; n < NI; ++n) { px[n] += 8 * u; pa[n] += 4 * LDG * u; pb[n] += 4 * LDG * u; }
+    };
+    auto multiply = [&](auto h_, const Ops &o) {
+        constexpr int h2 = decltype(h_)::value;
+        static_for_n<NI>([&](auto n_) {
+            constexpr int n = decltype(n_)::value;
+            const double a = (GB::takes_t(n) ? o.x[n] : o.D) * o.ga[n];
+            acc[h2][n] = mfma_blocks(a, o.gb[n], acc[h2][n]);
+        });
+    };
+    constexpr std::integral_constant<int, 0> c_0{};
+    constexpr std::integral_constant<int, 1> c_1{};
+    constexpr std::integral_constant<int, 2> c_2{};
+    constexpr std::integral_constant<int, 3> c_3{};
+    constexpr std::integral_constant<int, 4> c_4{};
+    {
+        Ops o0, o1;
+        fetch(o0, c_0);
+        int ks = 0;
+        for (; ks + 3 < nks; ks += 4) {
+            fetch(o1, c_1);
+            multiply(c_0, o0);
+            fetch(o0, c_2);
+            multiply(c_1, o1);
+            fetch(o1, c_3);
+            multiply(c_0, o0);
+            bump(c_4);
+            fetch(o0, c_0);                             // (past the end: zero rows, never multiplied)
+            multiply(c_1, o1);
+        }
+        if (ks + 1 < nks) {
+            fetch(o1, c_1);
+            multiply(c_0, o0);
+            fetch(o0, c_2);
+            multiply(c_1, o1);
+            ks += 2;
+        }
+        if (ks < nks) multiply(c_0, o0);
+    }
+    // C / D: the lane holds row `lane >> 4`, column `lane & 3` of its block
+    static_for_n<NI>([&](auto n_) {
+        constexpr int n = decltype(n_)::value;
+        const double v = acc[0][n] + acc[1][n];
+        const int row = r0[n] + kq, col = c0[n] + r;
+        const bool mine = GB::slotq(n, 0) + bs >= 0;        // (not a spare block)
+        if (mine && row < NV && col <= row) {
+            mt[row * LDM + col] = v;
+            if (col < row) mt[col * LDM + row] = v;
+        }
+        if (mine && row == NV && col < NV) gdr[col] = v;
+    });
+    lds_fence();
 }
 
 }  // namespace wv
