@@ -32,7 +32,9 @@ extern "C" {
  * Added without a bump: the regulator QPs (tmpc_regulator_problem, tmpc_create_regulator, tmpc_reg_run) -- new exports; tmpc_problem
  * and every tracking handle behave as before (a regulator handle accepts ref == NULL in the solve calls, see below); the
  * disturbance-set estimation (tmpc_estimate_w, tmpc_order_statistics) -- new exports; tmpc_set_call_overlap, tmpc_debug_lane_counters,
- * tmpc_debug_calls_conflict -- new exports (what tmpc_kernel_ms_total adds up for calls that overlap is defined there) */
+ * tmpc_debug_calls_conflict -- new exports (what tmpc_kernel_ms_total adds up for calls that overlap is defined there);
+ * tmpc_set_call_lanes / tmpc_get_call_lanes, tmpc_debug_lane_counters_n and the policy diagnostics next to them -- new exports
+ * (tmpc_debug_lane_counters now counts by the parity of the lane changes: with two lanes, what it was) */
 #define TMPC_ABI_VERSION 5
 
 /* error codes (function return values) */
@@ -230,15 +232,16 @@ int tmpc_solve_batch(tmpc_handle *h, int64_t B,
  * tmpc_last_kernel_ms().
  *
  * Ordering contract: calls on a handle take effect as if executed in call order.  Independent calls may run concurrently: the
- * handle keeps two launch lanes (a non-blocking stream each, with its own launch scratch), and a call goes to the other lane
- * than the call before it when none of its arrays overlaps -- read after write, write after write or write after read, by byte
- * range: x_k, ref, variant are read; u_nom, x_nom0, xu_ss, x_nom, status, iters written -- an array of the unfinished calls of
- * that call's lane.  A call that does overlap stays behind the call it depends on, and waits for the other lane as well where it
- * depends on both.  The tail of one launch (a launch ends with its slowest instances while most of the card idles) then runs
- * under the head of the next: a server that streams independent batches through one handle needs no second handle.  The
- * second lane is created by the first call that finds unfinished, independent work of the handle to run beside; every other entry
- * point (tmpc_solve_batch, tmpc_mc_run / _replay, tmpc_reg_run, the getters) joins the lanes before it runs.  tmpc_set_call_overlap
- * turns the second lane off.
+ * handle keeps up to TMPC_MAX_LANES launch lanes (a non-blocking stream each, with its own launch scratch; tmpc_set_call_lanes), and a
+ * call goes to the next lane in rotation when none of its arrays overlaps -- read after write, write after write or write after
+ * read, by byte range: x_k, ref, variant are read; u_nom, x_nom0, xu_ss, x_nom, status, iters written -- an array of the
+ * unfinished calls of the handle.  A call that does overlap stays on a lane behind a call it depends on, and that lane waits for the
+ * other lanes as well where it depends on several.  The tail of one launch (a launch ends with its slowest instances while most of
+ * the card idles) then runs under the head of the next ones: a server that streams independent batches through one handle needs no
+ * second handle.  A lane is taken into use by the first call that finds unfinished, independent work on every lane in use to run
+ * beside (the lanes' streams are created by tmpc_create, together, so that they land on different hardware queues);
+ * every other entry point (tmpc_solve_batch, tmpc_mc_run / _replay, tmpc_reg_run, the getters) joins the lanes before it runs.
+ * tmpc_set_call_overlap turns all lanes but the first off.
  * The handle's streams are its own: they are NOT ordered against the stream that produced the inputs or will consume the
  * outputs (e.g. torch's current stream).  The caller synchronises on both sides: the producers of x_k / ref / variant must have
  * completed before this call (torch.cuda.synchronize() or an event wait), and the outputs may be read only after
@@ -687,22 +690,53 @@ int tmpc_mc_get_physics_error(tmpc_handle *h, int64_t B, double *err2_phys);
 #define TMPC_ACTUATOR_SMART      1
 int tmpc_mc_set_actuator(tmpc_handle *h, int kind);
 
-/* Block until everything enqueued on the handle, on either launch lane, has finished. */
+/* Block until everything enqueued on the handle, on every launch lane, has finished. */
 int tmpc_synchronize(tmpc_handle *h);
 
 /*
- * Successive independent tmpc_solve_batch_device calls of the handle on two launch lanes (on != 0, the default; see the
- * ordering contract there) or every call on the one stream the handle is created with (on = 0: calls run one after the
- * other, and a second stream is never created).  Results do not depend on the setting.  Turning it off orders the first
- * lane behind what the second one still holds; turning it on waits for the calls enqueued while it was off.
+ * Successive independent tmpc_solve_batch_device calls of the handle on several launch lanes (on != 0, the default; see the
+ * ordering contract there) or every call on the handle's first stream (on = 0: calls run one after the other, and the
+ * other streams stay idle).  Results do not depend on the setting.  Turning it off orders the first
+ * lane behind what the others still hold; turning it on waits for the calls enqueued while it was off.
  */
 int tmpc_set_call_overlap(tmpc_handle *h, int on);
 /*
- * Diagnostics: calls_per_lane[2] = the tmpc_solve_batch_device calls enqueued on the first / second lane, *cross_lane_waits =
- * those among them that depended on unfinished calls of both lanes and made their lane wait for the other one -- since the
- * handle was created or the counters were last reset (reset != 0 clears them after reading).  Either pointer may be NULL.
+ * The number of launch lanes the independent calls of the handle rotate over while the overlap is on: n = 1 ... TMPC_MAX_LANES
+ * (1: as with the overlap off).  A new handle takes the environment's TMPC_CALL_LANES, else the library's default (DESIGN.md 5.1
+ * "Between launches" has the measurements behind it); two lanes schedule exactly as the two-lane handle did.  A handle with a
+ * variant on the workgroup-per-QP kernel uses at most two, whatever is set here (that kernel's workspace is per lane).  The
+ * ordering contract of tmpc_solve_batch_device holds for every n, and results do not depend on it.  Changing the number waits
+ * for the handle's calls.  tmpc_get_call_lanes: the lanes in use now.
+ */
+#define TMPC_MAX_LANES 4
+int tmpc_set_call_lanes(tmpc_handle *h, int n);
+int tmpc_get_call_lanes(const tmpc_handle *h);
+/*
+ * Diagnostics: calls_per_lane[2] = the tmpc_solve_batch_device calls by the parity of the lane changes since the lanes were last
+ * joined (a call that goes to another lane than the call before it changes the parity) -- with two lanes, the calls enqueued on the
+ * first / second lane, as before; for every lane count, independent calls in rotation alternate between the two entries.
+ * *cross_lane_waits = the calls among them that depended on unfinished calls of several lanes and made their lane wait for the
+ * others -- since the handle was created or the counters were last reset (reset != 0 clears them after reading).  Either
+ * pointer may be NULL.  tmpc_debug_lane_counters_n: the same with calls_per_lane[TMPC_MAX_LANES], one count per lane.
  */
 int tmpc_debug_lane_counters(tmpc_handle *h, int64_t *calls_per_lane, int64_t *cross_lane_waits, int reset);
+int tmpc_debug_lane_counters_n(tmpc_handle *h, int64_t *calls_per_lane, int64_t *cross_lane_waits, int reset);
+/*
+ * Diagnostics (tests/test_elastic_policy.py): the lane policy, and the policy of an elastic launch grid that is not in use yet (DESIGN.md
+ * 5.1 "Between launches"), themselves (csrc/tmpc_hazard.hpp); none of them touches a device, and all work on a host-only handle or without one.
+ * tmpc_debug_elastic_grid: *core = the core workgroups of an elastic launch on n_cu CUs with `lanes` lanes set (a handle with a
+ *   block-kernel variant: at most two), *eligible = whether a launch over B instances with wpb waves per workgroup would be elastic.
+ * tmpc_debug_surplus_yields: the decision of a surplus workgroup that reads `followers`, 0 | 1.
+ * tmpc_debug_plan_lanes: the lanes of a script of n_calls tmpc_solve_batch_device calls none of which finishes, on a fresh handle
+ *   with `lanes` lanes; ptrs = [n_calls][9] pointer arguments as in tmpc_debug_calls_conflict, B = [n_calls].  lane_out[i] = the
+ *   call's lane, waited_out[i] = bit l set: its lane waited for lane l, followers_out[i] = what call i's followers word ends at.
+ * tmpc_debug_busy_union: tmpc_kernel_ms_total's arithmetic on n calls given in call order by lane, start and end time.
+ */
+int tmpc_debug_elastic_grid(const tmpc_handle *h, int32_t n_cu, int32_t lanes, int32_t wpb, int64_t B, int32_t *core, int32_t *eligible);
+int tmpc_debug_surplus_yields(uint32_t followers, int32_t lanes);
+int tmpc_debug_plan_lanes(int32_t nx, int32_t nu, int32_t N, int32_t lanes, int32_t n_calls, const int64_t *B, const void *const *ptrs,
+                          int32_t *lane_out, int32_t *waited_out, int32_t *followers_out);
+double tmpc_debug_busy_union(int32_t n, const int32_t *lane, const double *start, const double *end);
 /*
  * Diagnostics (tests/test_call_hazards.py): the overlap rule itself, no device and no handle involved.  a and b are the nine
  * pointer arguments of two tmpc_solve_batch_device calls over B_a / B_b instances of a problem with nx, nu, N, in the order

@@ -184,6 +184,22 @@ def lib():
         L.tmpc_set_call_overlap.restype = C.c_int
         L.tmpc_debug_lane_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
         L.tmpc_debug_lane_counters.restype = C.c_int
+        if hasattr(L, "tmpc_set_call_lanes"):      # (an older build loaded through TMPC_LIB for an A/B has none of these)
+            L.tmpc_set_call_lanes.argtypes = [C.c_void_p, C.c_int]
+            L.tmpc_set_call_lanes.restype = C.c_int
+            L.tmpc_get_call_lanes.argtypes = [C.c_void_p]
+            L.tmpc_get_call_lanes.restype = C.c_int
+            L.tmpc_debug_lane_counters_n.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+            L.tmpc_debug_lane_counters_n.restype = C.c_int
+            L.tmpc_debug_elastic_grid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            L.tmpc_debug_elastic_grid.restype = C.c_int
+            L.tmpc_debug_surplus_yields.argtypes = [C.c_uint32, C.c_int32]
+            L.tmpc_debug_surplus_yields.restype = C.c_int
+            L.tmpc_debug_plan_lanes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            L.tmpc_debug_plan_lanes.restype = C.c_int
+            L.tmpc_debug_busy_union.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            L.tmpc_debug_busy_union.restype = C.c_double
         L.tmpc_debug_calls_conflict.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p)]
         L.tmpc_debug_calls_conflict.restype = C.c_int
         L.tmpc_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
@@ -451,12 +467,69 @@ def set_call_overlap(h: Handle, on: bool = True):
 
 
 def lane_counters(h: Handle, reset: bool = False):
-    """include/tmpc.h: tmpc_debug_lane_counters -> ((device-pointer calls enqueued on lane 0, on lane 1), calls that had to wait for
-    the other lane), since the handle was created or the counters were last reset."""
+    """include/tmpc.h: tmpc_debug_lane_counters -> ((device-pointer calls by the parity of the lane changes: with two lanes, those enqueued on
+    lane 0, on lane 1), calls that had to wait for another lane), since the handle was created or the counters were last reset."""
     calls, waits = (C.c_int64 * 2)(), C.c_int64()
     if lib().tmpc_debug_lane_counters(h.ptr, calls, C.byref(waits), int(reset)) != 0:
         raise RuntimeError(h.error())
     return (int(calls[0]), int(calls[1])), int(waits.value)
+
+
+MAX_LANES = 4
+
+
+def set_call_lanes(h: Handle, n: int):
+    """include/tmpc.h: tmpc_set_call_lanes -- the launch lanes (1 ... MAX_LANES) the handle's independent calls rotate over."""
+    if lib().tmpc_set_call_lanes(h.ptr, int(n)) != 0:
+        raise RuntimeError(h.error())
+
+
+def get_call_lanes(h: Handle) -> int:
+    """include/tmpc.h: tmpc_get_call_lanes -- the lanes in use now."""
+    return int(lib().tmpc_get_call_lanes(h.ptr))
+
+
+def lane_counters_n(h: Handle, reset: bool = False):
+    """include/tmpc.h: tmpc_debug_lane_counters_n -> ((device-pointer calls enqueued on each of the MAX_LANES lanes), calls that had to
+    wait for another lane)."""
+    calls, waits = (C.c_int64 * MAX_LANES)(), C.c_int64()
+    if lib().tmpc_debug_lane_counters_n(h.ptr, calls, C.byref(waits), int(reset)) != 0:
+        raise RuntimeError(h.error())
+    return tuple(int(c) for c in calls), int(waits.value)
+
+
+def elastic_grid(h: Handle, n_cu: int, lanes: int, wpb: int, B: int):
+    """include/tmpc.h: tmpc_debug_elastic_grid -> (core workgroups, whether a launch over B instances would be elastic).  No device is touched."""
+    core, el = C.c_int32(), C.c_int32()
+    if lib().tmpc_debug_elastic_grid(h.ptr, n_cu, lanes, wpb, int(B), C.byref(core), C.byref(el)) != 0:
+        raise RuntimeError("tmpc_debug_elastic_grid: invalid argument")
+    return int(core.value), bool(el.value)
+
+
+def surplus_yields(followers: int, lanes: int) -> bool:
+    """include/tmpc.h: tmpc_debug_surplus_yields -- the decision of a surplus workgroup of an elastic launch."""
+    return bool(lib().tmpc_debug_surplus_yields(int(followers), int(lanes)))
+
+
+def plan_lanes(nx: int, nu: int, N: int, lanes: int, calls):
+    """include/tmpc.h: tmpc_debug_plan_lanes.  calls: [(B, {argument name (SOLVE_POINTERS): address})] -> (lane, wait mask, followers) per
+    call, for a script none of whose calls finishes.  No device is touched."""
+    n = len(calls)
+    B = (C.c_int64 * max(n, 1))(*[int(b) for b, _ in calls])
+    ptrs = (C.c_void_p * (9 * max(n, 1)))(*[a.get(k) for _, a in calls for k in SOLVE_POINTERS])
+    lane, waited, fol = ((C.c_int32 * max(n, 1))() for _ in range(3))
+    if lib().tmpc_debug_plan_lanes(nx, nu, N, int(lanes), n, B, ptrs, lane, waited, fol) != 0:
+        raise RuntimeError("tmpc_debug_plan_lanes: invalid argument")
+    return [(int(lane[i]), int(waited[i]), int(fol[i])) for i in range(n)]
+
+
+def busy_union(lanes, start, end) -> float:
+    """include/tmpc.h: tmpc_debug_busy_union -- tmpc_kernel_ms_total's arithmetic on calls given in call order."""
+    n = len(lanes)
+    la = (C.c_int32 * max(n, 1))(*[int(x) for x in lanes])
+    s = (C.c_double * max(n, 1))(*[float(x) for x in start])
+    e = (C.c_double * max(n, 1))(*[float(x) for x in end])
+    return float(lib().tmpc_debug_busy_union(n, la, s, e))
 
 
 SOLVE_POINTERS = ("x_k", "ref", "variant", "u_nom", "x_nom0", "xu_ss", "x_nom", "status", "iters")

@@ -345,15 +345,6 @@ int upload_variant(tmpc_handle *h, Variant &v, const tmpc_problem &p) {
     return TMPC_OK;
 }
 
-// Orders the primary lane behind what the secondary lane has been given, without blocking the host: the start of every entry
-// point that runs on the primary lane alone.  Each of them ends with a synchronisation of that lane, which then covers both.
-int join_lanes(tmpc_handle *h) {
-    Lane &second = h->lane[1];
-    if (second.stream && !second.inflight.empty()) HIP_TRY(h, hipStreamWaitEvent(h->stream, second.inflight.back().end, 0));
-    h->cur = 0;
-    return TMPC_OK;
-}
-
 // block-kernel workspace of a lane: one slice per resident workgroup, sized once for the largest variant (a slice is addressed
 // with the launching variant's ncp)
 int ensure_block_ws(tmpc_handle *h, Lane &lane) {
@@ -424,6 +415,9 @@ int create_lane(tmpc_handle *h, Lane &lane) {
     return TMPC_OK;
 }
 
+// Lanes the handle's calls rotate over now
+int lanes_in_use(const tmpc_handle *h) { return h->overlap ? std::min(h->lanes, max_lanes(h)) : 1; }
+
 // Drops the records of the lane's calls that have finished (they finish in order).
 void prune_finished(Lane &lane) {
     while (!lane.inflight.empty()) {
@@ -438,30 +432,47 @@ bool conflicts_with_lane(const Lane &lane, const tmpc::CallRanges &call) {
     return false;
 }
 
-// The lane of a tmpc_solve_batch_device call.  It goes to the other lane than the call before it when it has no RAW, WAW or WAR
-// overlap with the unfinished calls of that call's lane: it may then run beside them, and on its own lane it is ordered behind
-// whatever that lane holds.  Otherwise it stays on the lane of the call it conflicts with, behind it; if unfinished calls
-// of the other lane conflict with it as well, its lane first waits for that lane's latest end event.  The second lane is created
-// by the first call that finds unfinished, independent work to run beside.
+// The lane of a tmpc_solve_batch_device call (tmpc_hazard.hpp: pick_lane_policy).  With no RAW, WAW or WAR overlap with the unfinished
+// calls of the handle it goes to the next lane of the rotation and may run beside what the other lanes hold; on its own lane it is
+// ordered behind whatever that lane holds.  Otherwise it stays on a lane that holds a call it conflicts with, behind it, and that lane
+// first waits for the latest end event of every other lane that holds one.  A lane is created by the first call that finds
+// unfinished, independent work on every lane in use to run beside ("created": taken into use -- its stream exists since tmpc_create).
 int pick_lane(tmpc_handle *h, const tmpc::CallRanges &call, Lane **out) {
     *out = &h->lane[0];
-    if (!h->overlap) return TMPC_OK;
-    for (Lane &l : h->lane) prune_finished(l);
-    Lane &prev = h->lane[h->cur], &other = h->lane[1 - h->cur];
-    if (conflicts_with_lane(prev, call)) {
-        if (other.stream && conflicts_with_lane(other, call)) {
-            HIP_TRY(h, hipStreamWaitEvent(prev.stream, other.inflight.back().end, 0));
-            ++h->lane_waits;
-        }
-        *out = &prev;
-        return TMPC_OK;
+    const int n = lanes_in_use(h);
+    if (n <= 1) return TMPC_OK;
+    tmpc::LaneView view[tmpc::MAX_LANES];
+    for (int l = 0; l < n; ++l) {
+        Lane &lane = h->lane[l];
+        if (!lane.active) continue;
+        prune_finished(lane);
+        view[l].exists = true;
+        view[l].busy = !lane.inflight.empty();
+        view[l].conflicts = conflicts_with_lane(lane, call);
     }
-    if (!other.stream) {
-        if (prev.inflight.empty()) { *out = &prev; return TMPC_OK; }
-        if (const int rc = create_lane(h, other)) return rc;
+    const tmpc::LanePick pick = tmpc::pick_lane_policy(view, n, h->cur);
+    Lane &lane = h->lane[pick.lane];
+    if (pick.create) {
+        if (!lane.stream)                  // (a lane beyond those of tmpc_create: tmpc_set_call_lanes raised the count)
+            if (const int rc = create_lane(h, lane)) return rc;
+        lane.active = true;
     }
-    *out = &other;
+    for (int l = 0; l < n; ++l)
+        if (pick.wait_mask >> l & 1u) HIP_TRY(h, hipStreamWaitEvent(lane.stream, h->lane[l].inflight.back().end, 0));
+    if (pick.wait_mask) ++h->lane_waits;
+    *out = &lane;
     return TMPC_OK;
+}
+
+// Counts a device-pointer call enqueued on `lane` (tmpc_debug_lane_counters[_n]) and makes that lane the current one.  The two-entry
+// counter goes by the parity of the lane changes since the lanes were last joined: with two lanes that is the lane itself, and calls in
+// rotation alternate between its entries for every number of lanes.
+void count_call(tmpc_handle *h, Lane &lane) {
+    const int idx = static_cast<int>(&lane - h->lane);
+    if (idx != h->cur) h->par ^= 1;
+    ++h->par_calls[h->par];
+    ++lane.calls;
+    h->cur = idx;
 }
 
 // Notes a tmpc_solve_batch_device call just enqueued on `lane` as in flight.  Its end event is the call's timing event; when that
@@ -482,9 +493,14 @@ int note_in_flight(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call) {
         HIP_TRY(h, hipEventRecord(end, lane.stream));
     }
     lane.inflight.push_back({call, end});
-    ++lane.calls;
-    h->cur = static_cast<int>(&lane - h->lane);
+    count_call(h, lane);
     return TMPC_OK;
+}
+
+// The environment's default of a new handle: TMPC_CALL_LANES (1 ... 4).  Read once, here.
+void read_lane_settings(tmpc_handle *h) {
+    h->lanes = DEFAULT_CALL_LANES;
+    if (const char *e = std::getenv("TMPC_CALL_LANES")) h->lanes = std::min(std::max(std::atoi(e), 1), tmpc::MAX_LANES);
 }
 
 // Uploads the condensed variant(s) of a new handle to HIP device `device` (stream, work counters, timing events, kernel layouts),
@@ -500,6 +516,7 @@ int setup_handle(tmpc_handle *h, const tmpc_problem &p, int device) {
             if (rc == TMPC_E_UNSUPPORTED) h->err.clear();
             else if (rc) return rc;
         }
+        read_lane_settings(h);
         return TMPC_OK;
     }
     hipDeviceProp_t prop;
@@ -511,6 +528,7 @@ int setup_handle(tmpc_handle *h, const tmpc_problem &p, int device) {
     }
     h->n_cu = prop.multiProcessorCount;
     if (const int rc = create_lane(h, h->lane[0])) return rc;
+    h->lane[0].active = true;
     h->stream = h->lane[0].stream;
     for (int i = 0; i < 256; ++i) {       // timing events are created up front, not in the solve path
         hipEvent_t a = nullptr, b = nullptr;
@@ -520,6 +538,15 @@ int setup_handle(tmpc_handle *h, const tmpc_problem &p, int device) {
     }
     for (int k = 0; k < h->nvariants; ++k)
         if (const int rc = upload_variant(h, h->v[k], p)) return rc;
+    read_lane_settings(h);
+    // The streams of the other lanes are created here, one after the other, and not by the first call that needs one: the runtime binds a
+    // stream to one of the process's few hardware queues (four by default) when it is created, to the one with the fewest streams, and two
+    // lanes of a handle on one queue run one after the other -- the launches of one lane then wait behind WHOLE launches of the other.
+    // Created together, the lanes of a handle land on different queues; created whenever a burst first needed them, between the streams of
+    // other handles, they did not (the headline of `bench.py --full` at 0.93 of the two-lane handle's, measured).  A lane is still taken
+    // into use (Lane::active) only by the first call that finds work to run beside.
+    for (int l = 1; l < std::min(h->lanes, max_lanes(h)); ++l)
+        if (const int rc = create_lane(h, h->lane[l])) return rc;
     return TMPC_OK;
 }
 
@@ -602,20 +629,37 @@ namespace tmpc_host {
 
 thread_local std::string g_create_error;
 
-// Waits for everything enqueued on the handle, on either lane.
+// Waits for everything enqueued on the handle, on every lane.
 hipError_t sync_lanes(tmpc_handle *h) {
-    hipError_t e = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
-    Lane &second = h->lane[1];
-    if (e == hipSuccess && second.stream) e = hipStreamSynchronize(second.stream);
+    hipError_t e = hipSuccess;
+    for (Lane &l : h->lane)
+        if (e == hipSuccess && l.stream) e = hipStreamSynchronize(l.stream);
     if (e == hipSuccess)
         for (Lane &l : h->lane) l.inflight.clear();
     return e;
 }
 
+// Orders the primary lane behind what the other lanes have been given, without blocking the host: the start of every entry
+// point that runs on the primary lane alone.  Each of them ends with a synchronisation of that lane, which then covers all.
+int join_lanes(tmpc_handle *h) {
+    for (int l = 1; l < tmpc::MAX_LANES; ++l) {
+        Lane &other = h->lane[l];
+        if (other.stream && !other.inflight.empty()) HIP_TRY(h, hipStreamWaitEvent(h->stream, other.inflight.back().end, 0));
+    }
+    h->cur = h->par = 0;
+    return TMPC_OK;
+}
+
+int max_lanes(const tmpc_handle *h) {
+    for (int k = 0; k < h->nvariants; ++k)
+        if (use_block(h, h->v[k])) return 2;
+    return tmpc::MAX_LANES;
+}
+
 // The lane choice and the in-flight record of tmpc_solve_batch_device, for the other entry points that follow its ordering contract
 // (tmpc_sens.cpp)
 int pick_call_lane(tmpc_handle *h, const tmpc::CallRanges &call, Lane **out) { return pick_lane(h, call, out); }
-int note_call(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call) { return h->overlap ? note_in_flight(h, lane, call) : (++lane.calls, TMPC_OK); }
+int note_call(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call) { return lanes_in_use(h) > 1 ? note_in_flight(h, lane, call) : (count_call(h, lane), TMPC_OK); }
 
 bool use_block(const tmpc_handle *h, const Variant &v) { return h->kernel_path == TMPC_PATH_BLOCK ? v.tiles != 0 : !v.wave_ok; }
 
@@ -824,7 +868,7 @@ int tmpc_solve_batch_device(tmpc_handle *h, int64_t B, const double *x_k, const 
     Lane *lane = nullptr;
     if (const int rc = pick_lane(h, call, &lane)) return rc;
     if (const int rc = enqueue(h, *lane, {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, x_nom, status, iters})) return rc;
-    return h->overlap ? note_in_flight(h, *lane, call) : (++lane->calls, TMPC_OK);
+    return lanes_in_use(h) > 1 ? note_in_flight(h, *lane, call) : (count_call(h, *lane), TMPC_OK);
 }
 
 int tmpc_solve_batch(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant,
@@ -877,6 +921,12 @@ int tmpc_set_kernel_path(tmpc_handle *h, int path) {
     for (int k = 0; k < h->nvariants; ++k) {
         if (path == TMPC_PATH_WAVE && !h->v[k].wave_ok && h->device >= 0) { h->err = "tmpc_set_kernel_path: no wave-per-QP shape covers this problem"; return TMPC_E_UNSUPPORTED; }
         if (path == TMPC_PATH_BLOCK && h->v[k].tiles == 0 && h->device >= 0) { h->err = "tmpc_set_kernel_path: the block kernel needs nv <= 128"; return TMPC_E_UNSUPPORTED; }
+    }
+    if (h->device >= 0 && path != h->kernel_path) {
+        // (a handle with a variant on the block kernel rotates over two lanes: the records of the others must not be left behind)
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, sync_lanes(h));
+        h->cur = h->par = 0;
     }
     h->kernel_path = path;
     return TMPC_OK;
@@ -957,11 +1007,88 @@ int tmpc_set_call_overlap(tmpc_handle *h, int on) {
 
 int tmpc_debug_lane_counters(tmpc_handle *h, int64_t *calls_per_lane, int64_t *cross_lane_waits, int reset) {
     if (!h) return TMPC_E_INVALID;
+    // (count_call: by the parity of the lane changes -- the two lanes of a two-lane handle; calls in rotation alternate for any lane count)
     if (calls_per_lane)
-        for (int k = 0; k < 2; ++k) calls_per_lane[k] = h->lane[k].calls;
+        for (int k = 0; k < 2; ++k) calls_per_lane[k] = h->par_calls[k];
     if (cross_lane_waits) *cross_lane_waits = h->lane_waits;
-    if (reset) { h->lane[0].calls = h->lane[1].calls = 0; h->lane_waits = 0; }
+    if (reset) {
+        for (tmpc_host::Lane &l : h->lane) l.calls = 0;
+        h->par_calls[0] = h->par_calls[1] = 0;
+        h->lane_waits = 0;
+    }
     return TMPC_OK;
+}
+
+int tmpc_debug_lane_counters_n(tmpc_handle *h, int64_t *calls_per_lane, int64_t *cross_lane_waits, int reset) {
+    if (!h) return TMPC_E_INVALID;
+    if (calls_per_lane)
+        for (int l = 0; l < tmpc::MAX_LANES; ++l) calls_per_lane[l] = h->lane[l].calls;
+    return tmpc_debug_lane_counters(h, nullptr, cross_lane_waits, reset);
+}
+
+int tmpc_set_call_lanes(tmpc_handle *h, int n) {
+    if (!h || session_bars(h, "tmpc_set_call_lanes")) return TMPC_E_INVALID;
+    if (n < 1 || n > tmpc::MAX_LANES) { h->err = "tmpc_set_call_lanes: 1 ... TMPC_MAX_LANES lanes"; return TMPC_E_INVALID; }
+    if (h->device >= 0 && n != h->lanes) {
+        // the records of the lanes that leave the rotation would no longer be looked at: the lanes start empty
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, sync_lanes(h));
+        h->cur = h->par = 0;
+    }
+    h->lanes = n;
+    return TMPC_OK;
+}
+
+int tmpc_get_call_lanes(const tmpc_handle *h) { return h ? (h->overlap ? std::min(h->lanes, max_lanes(h)) : 1) : TMPC_E_INVALID; }
+
+int tmpc_debug_elastic_grid(const tmpc_handle *h, int32_t n_cu, int32_t lanes, int32_t wpb, int64_t B, int32_t *core, int32_t *eligible) {
+    if (!h || n_cu <= 0 || lanes < 1 || lanes > tmpc::MAX_LANES || wpb <= 0) return TMPC_E_INVALID;
+    const bool block_variant = max_lanes(h) < tmpc::MAX_LANES;
+    const int l = std::min<int>(lanes, max_lanes(h));
+    if (core) *core = tmpc::elastic_core(n_cu, l);
+    if (eligible) *eligible = tmpc::elastic_eligible(B, n_cu, wpb, block_variant) && tmpc::elastic_core(n_cu, l) < n_cu ? 1 : 0;
+    return TMPC_OK;
+}
+
+int tmpc_debug_surplus_yields(uint32_t followers, int32_t lanes) { return tmpc::surplus_yields(followers, lanes) ? 1 : 0; }
+
+int tmpc_debug_plan_lanes(int32_t nx, int32_t nu, int32_t N, int32_t lanes, int32_t n_calls, const int64_t *B, const void *const *ptrs,
+                          int32_t *lane_out, int32_t *waited_out, int32_t *followers_out) {
+    if (!B || !ptrs || !lane_out || nx <= 0 || nu <= 0 || N <= 0 || n_calls < 0 || lanes < 1 || lanes > tmpc::MAX_LANES) return TMPC_E_INVALID;
+    // no call of the script finishes: every lane keeps all it was given
+    std::vector<tmpc::CallRanges> calls;
+    std::vector<int> held[tmpc::MAX_LANES];
+    std::vector<int32_t> fol(static_cast<size_t>(n_calls), 0);
+    bool exists[tmpc::MAX_LANES] = {true, false, false, false};
+    int cur = 0;
+    for (int i = 0; i < n_calls; ++i) {
+        const void *const *a = ptrs + static_cast<size_t>(i) * 9;
+        calls.push_back(tmpc::solve_call_ranges(B[i], nx, nu, N, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]));
+        tmpc::LaneView view[tmpc::MAX_LANES];
+        for (int l = 0; l < lanes; ++l) {
+            view[l].exists = exists[l];
+            view[l].busy = !held[l].empty();
+            for (int j : held[l]) view[l].conflicts = view[l].conflicts || tmpc::calls_conflict(calls[j], calls[i]);
+        }
+        const tmpc::LanePick pick = tmpc::pick_lane_policy(view, lanes, cur);
+        exists[pick.lane] = true;
+        const unsigned beside = tmpc::follower_lanes(pick, view, lanes);
+        for (int l = 0; l < lanes; ++l)
+            if (beside >> l & 1u)
+                for (int j : held[l]) ++fol[j];
+        held[pick.lane].push_back(i);
+        cur = pick.lane;
+        lane_out[i] = pick.lane;
+        if (waited_out) waited_out[i] = static_cast<int32_t>(pick.wait_mask);
+    }
+    if (followers_out) std::copy(fol.begin(), fol.end(), followers_out);
+    return TMPC_OK;
+}
+
+double tmpc_debug_busy_union(int32_t n, const int32_t *lane, const double *start, const double *end) {
+    if (n < 0 || !lane || !start || !end) return -1.0;
+    return tmpc::busy_union(static_cast<size_t>(n), [&](size_t i, double *ms) { *ms = end[i] - start[i]; return true; },
+                            [&](size_t j, size_t i, double *ms) { *ms = end[i] - end[j]; return true; }, [&](size_t i) { return lane[i]; });
 }
 
 int tmpc_debug_calls_conflict(int32_t nx, int32_t nu, int32_t N, int64_t B_a, const void *const *a, int64_t B_b, const void *const *b) {
@@ -983,23 +1110,15 @@ int tmpc_kernel_ms_total(tmpc_handle *h, float *total_ms, int32_t *launches, int
     if (!h) return TMPC_E_INVALID;
     if (h->device < 0) { h->err = "host-only handle"; return TMPC_E_DEVICE; }
     HIP_TRY(h, sync_lanes(h));
-    // A call adds the time by which it extended the handle's busy period: from the later of its own start and the end of the
-    // busy period so far (`busy`: the call that ended last) to its own end.  Calls of one lane follow each other, so only a
-    // call on the other lane than `busy` can have started before that end.
-    float sum = 0.f;
-    size_t busy = 0;
-    for (size_t i = 0; i < h->pool_used; ++i) {
-        float ms = 0.f;
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->pool[i].first, h->pool[i].second));
-        if (i > 0 && h->pool_lane[i] != h->pool_lane[busy]) {
-            float past = 0.f;
-            HIP_TRY(h, hipEventElapsedTime(&past, h->pool[busy].second, h->pool[i].second));
-            if (past <= 0.f) continue;          // ended inside the busy period: extends nothing
-            ms = std::min(ms, past);
-        }
-        busy = i;
-        sum += ms;
-    }
+    // (tmpc_hazard.hpp: busy_union -- any number of lanes)
+    hipError_t bad = hipSuccess;
+    bool ok = true;
+    const float sum = static_cast<float>(tmpc::busy_union(
+        h->pool_used,
+        [&](size_t i, double *ms) { float t = 0.f; bad = hipEventElapsedTime(&t, h->pool[i].first, h->pool[i].second); *ms = t; return bad == hipSuccess; },
+        [&](size_t j, size_t i, double *ms) { float t = 0.f; bad = hipEventElapsedTime(&t, h->pool[j].second, h->pool[i].second); *ms = t; return bad == hipSuccess; },
+        [&](size_t i) { return h->pool_lane[i]; }, &ok));
+    if (!ok) HIP_TRY(h, bad);
     if (total_ms) *total_ms = sum;
     if (launches) *launches = static_cast<int32_t>(h->pool_used);
     if (reset) h->pool_used = 0;

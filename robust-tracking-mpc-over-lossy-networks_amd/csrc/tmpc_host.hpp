@@ -109,9 +109,14 @@ struct LoopRecords {
     int64_t law_B = 0;           // 0: the last loop did not go through the law
 };
 
+// What a new handle starts with where the environment says nothing (TMPC_CALL_LANES): DESIGN.md 5.1 "Between launches" has the
+// measurements behind the choice
+constexpr int DEFAULT_CALL_LANES = 3;
+
 // One launch lane of a device handle: a non-blocking stream and everything a solve launch on it mutates, so that launches on
 // different lanes may overlap while the launches of one lane stay ordered.  Lane 0 (the primary lane) exists from tmpc_create on
-// and takes every entry point; lane 1 is created by the first tmpc_solve_batch_device call that can run beside an unfinished one.
+// and takes every entry point; the others (tmpc::MAX_LANES in all) get their streams at tmpc_create too and are taken into use by the first
+// tmpc_solve_batch_device call that finds every lane in use holding unfinished work it can run beside.
 struct Lane {
     hipStream_t stream = nullptr;
     tmpc::WorkCounter wc;        // work counters of the wave / block kernel's launches (tmpc_device.hpp)
@@ -129,6 +134,7 @@ struct Lane {
     std::vector<hipEvent_t> spare;
     size_t spare_next = 0;
     int64_t calls = 0;           // tmpc_solve_batch_device calls enqueued here (tmpc_debug_lane_counters)
+    bool active = false;         // taken into use by the lane choice (the stream of a lane exists from tmpc_create on, see setup_handle)
 };
 
 // The stepped closed loop of a handle (tmpc_mc_open .. tmpc_mc_close): the records of tmpc_mc_run, whose arrays live in the loop
@@ -207,11 +213,14 @@ struct tmpc_handle {
     int reg_tube = 0;
     std::vector<double> hA, hB, hK, hKanc, hQ, hR;   // host copies for the closed-loop entry points
     int kernel_path = TMPC_PATH_AUTO;
-    tmpc_host::Lane lane[2];
+    tmpc_host::Lane lane[tmpc::MAX_LANES];
     hipStream_t stream = nullptr;        // = lane[0].stream: everything but an overlapped tmpc_solve_batch_device call runs on it
     int overlap = 1;             // tmpc_set_call_overlap
+    int lanes = 2;               // lanes the calls rotate over with the overlap on (tmpc_set_call_lanes, TMPC_CALL_LANES)
     int cur = 0;                 // lane of the latest solve call
-    int64_t lane_waits = 0;      // calls that had to wait for the other lane (tmpc_debug_lane_counters)
+    int par = 0;                 // parity of the lane changes since the lanes were last joined; with two lanes, = cur
+    int64_t par_calls[2] = {0, 0};       // calls by that parity (tmpc_debug_lane_counters)
+    int64_t lane_waits = 0;      // calls that had to wait for another lane (tmpc_debug_lane_counters)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     // event pairs of the calls since the last tmpc_kernel_ms_total(reset), and the lane each ran on: per-call device time
@@ -266,6 +275,10 @@ int prepare_wave_scratch(tmpc_handle *h, Lane &lane, int64_t B, int nvar);
 int enqueue(tmpc_handle *h, Lane &lane, const tmpc::BatchIO &io, int32_t *const *ws = nullptr, bool variants_valid = false);
 void release_session(tmpc_handle *h);
 int begin_loop(tmpc_handle *h, int64_t B);
+// orders the primary lane behind what the other lanes hold, without blocking the host (every entry point that runs on the primary lane alone starts so)
+int join_lanes(tmpc_handle *h);
+// lanes a handle may use: tmpc::MAX_LANES where every variant runs on the wave kernel, two where one has the block kernel's workspace per lane
+int max_lanes(const tmpc_handle *h);
 bool session_bars(tmpc_handle *h, const char *who);
 int pick_call_lane(tmpc_handle *h, const tmpc::CallRanges &call, Lane **out);
 int note_call(tmpc_handle *h, Lane &lane, const tmpc::CallRanges &call);

@@ -98,7 +98,7 @@ struct LawState {
     tmpc::LawTable *dtab = nullptr;          // the two tables' descriptions as the kernel reads them, rewritten whenever a table changes
     int max_hops = 0;            // tmpc_law_set_hops
     unsigned long long *dstats = nullptr;    // [2][LAW_HOP_STATS] the hops' counters per variant, allocated with dtab
-    DeviceBuffer todo[2];        // the selector bytes of a tmpc_law_solve call, one buffer per launch lane
+    DeviceBuffer todo[tmpc::MAX_LANES];   // the selector bytes of a tmpc_law_solve call, one buffer per launch lane
     DeviceBuffer stage;          // the host-pointer entries' device copies
 };
 
@@ -433,7 +433,7 @@ int quiesce(tmpc_handle *h) {
     if (h->device < 0) return TMPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, sync_lanes(h));
-    h->cur = 0;
+    h->cur = h->par = 0;
     return TMPC_OK;
 }
 
@@ -551,8 +551,7 @@ int call_host(tmpc_handle *h, const char *who, const LawCall &c) {
     if (const int rc = check_call(h, who, c); rc || c.B == 0) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     // the primary lane behind what the secondary lane holds
-    if (Lane &second = h->lane[1]; second.stream && !second.inflight.empty()) HIP_TRY(h, hipStreamWaitEvent(h->stream, second.inflight.back().end, 0));
-    h->cur = 0;
+    if (const int rc = join_lanes(h)) return rc;
     if (const int rc = ensure_state(h, who)) return rc;
     const size_t b = static_cast<size_t>(c.B), nx = h->nx, nu = h->nu, N = h->N, d = sizeof(double);
     struct Part { const void *host_in; void *host_out; size_t bytes; size_t off; };

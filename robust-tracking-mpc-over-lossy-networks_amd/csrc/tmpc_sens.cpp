@@ -18,7 +18,7 @@ struct SensModel {
 // What a handle owns for its sensitivity calls (created by the first one)
 struct SensState {
     SensModel m[2];
-    DeviceBuffer ws[2];          // the kernel's right-hand-side blocks, one slice per workgroup; one buffer per launch lane
+    DeviceBuffer ws[tmpc::MAX_LANES];     // the kernel's right-hand-side blocks, one slice per workgroup; one buffer per launch lane
     DeviceBuffer stage;          // the host-pointer entries' device copies
 };
 
@@ -338,10 +338,7 @@ int enqueue_sens(tmpc_handle *h, Lane &lane, const char *who, const SensCall &c)
 
 // The primary lane behind what the secondary lane holds (every entry point that runs on the primary lane alone starts so)
 int primary_behind_secondary(tmpc_handle *h) {
-    Lane &second = h->lane[1];
-    if (second.stream && !second.inflight.empty()) HIP_TRY(h, hipStreamWaitEvent(h->stream, second.inflight.back().end, 0));
-    h->cur = 0;
-    return TMPC_OK;
+    return join_lanes(h);
 }
 
 // What a sensitivity call reads and writes, by byte range: the ordering contract of tmpc_solve_batch_device covers these calls too
