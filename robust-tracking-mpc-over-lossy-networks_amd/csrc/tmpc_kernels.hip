@@ -488,6 +488,15 @@ __device__ __forceinline__ LawRecord law_record(const LawLoop *p) {
 }
 #endif
 
+// Kernels that keep the SELECT forms of the triangular solves (tmpc_wave.hpp: lanes_factor<N, SELECT>): a register-allocation fact
+// of the compiler in use, not a property of the shape.  closed_loop_law<11,1,0,5,4,0,8> -- the explicit-law loop of the bench
+// shape -- needs all 256 vector registers of Occupancy 2 with the select forms; with the masked ones its allocation spills 2 of them
+// into a 12-byte private segment.  tests/test_code_objects.py holds every instantiation to private segment 0, so an entry that a
+// later change makes necessary shows there; one that has become unnecessary shows only by deleting it and reading the notes
+// (scripts/code_object_notes.py).  The explicit-law loop of the bench shape therefore runs the parent's code for these solves.
+template <int FUSED, int NV, int DP, int DS, int KC, int CP, int CS, int WPB>
+constexpr bool keeps_select_forms = FUSED == 3 && NV == 11 && DP == 1 && DS == 0 && KC == 5 && CP == 4 && CS == 0 && WPB == 8;
+
 // The body of both kernels below (inlined into each: one persistent workgroup per CU, a wave per work item)
 // NCS: the factored slots in use, a compile-time count (TMPC_SOLVE_BODY below picks the instantiation)
 template <int NV, int DP, int DS, int KC, int CP, int CS, int WPB, int FUSED, int NCS>
@@ -501,6 +510,9 @@ __device__ __forceinline__ void solve_body(
     using SH = Shape<NV, DP, DS, KC, CP, CS, tile_rows(NV, WPB)>;
     using WL = WaveLds<SH>;
     constexpr int RS = SH::RS, FD = SH::FD, FC = SH::FC, NDP = SH::NDP, NCCP = SH::NCCP, KT = SH::KT, WCAP = SH::WCAP, LDG = SH::LDG;
+    // (the four calls of lanes_factor / lanes_backsub_lane below stand in wave-uniform control flow -- `spd` comes from a
+    // readfirstlane, the refinement's exits from wave_max --: the masked forms need all 64 lanes active)
+    constexpr bool SELF = keeps_select_forms<FUSED, NV, DP, DS, KC, CP, CS, WPB>;
 #ifdef TMPC_HOST_SIM
     double *smem = sim::lds<double>();
 #else
@@ -1115,9 +1127,9 @@ __device__ __forceinline__ void solve_body(
                             wave_lds_fence();
                             double bb = rhs_i;
                             mdinv = 1.0;
-                            spd = lanes_factor<NV>(mrow, bb, mdinv, lane);
+                            spd = lanes_factor<NV, SELF>(mrow, bb, mdinv, lane);
                             if (spd) {
-                                const double xl = lanes_backsub_lane<NV>(mrow, bb, mdinv, lane);
+                                const double xl = lanes_backsub_lane<NV, SELF>(mrow, bb, mdinv, lane);
                                 if (lane < NV) {
                                     dzav[lane] = xl;
                                     // the factor waits in LDS for the corrector's solve: 2 NV registers less through sweep B
@@ -1243,7 +1255,7 @@ __device__ __forceinline__ void solve_body(
                         const double mdinv = Mf[li * SH::LDM + NV];
                         double bb = (lane < NV) ? rhs_i + v2 - smu * v3 : 0.0;
                         lanes_forward<NV>(mrow, bb, lane);
-                        const double xl = lanes_backsub_lane<NV>(mrow, bb, mdinv, lane);
+                        const double xl = lanes_backsub_lane<NV, SELF>(mrow, bb, mdinv, lane);
                         if (lane < NV) dzv[lane] = xl;
                     }
                     wave_lds_fence();
@@ -1468,7 +1480,7 @@ __device__ __forceinline__ void solve_body(
                         }
                         {
                             double bdummy = 0.0;
-                            if (!lanes_factor<MC>(srow, bdummy, sdinv, lane)) return false;
+                            if (!lanes_factor<MC, SELF>(srow, bdummy, sdinv, lane)) return false;
                         }
                         STAMP(12);
                         // proximal Newton steps on the KKT system of the working set (at most twelve -- nearly parallel working rows need them --; they stop once a step
@@ -1502,7 +1514,7 @@ __device__ __forceinline__ void solve_body(
                                 bb = gz - hw[Widx[lane]] - gt;
                             }
                             lanes_forward<MC>(srow, bb, lane);
-                            const double dyl = lanes_backsub_lane<MC>(srow, bb, sdinv, lane);
+                            const double dyl = lanes_backsub_lane<MC, SELF>(srow, bb, sdinv, lane);
                             if (lane < m) { dyv[lane] = dyl; yv[lane] += dyl; }
                             wave_lds_fence();
                             // zp -= t1 + T dy  (lane j -> entry j)

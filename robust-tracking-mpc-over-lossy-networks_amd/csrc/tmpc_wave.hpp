@@ -302,8 +302,10 @@ __device__ __forceinline__ void pin(double &v) {
 // while the remaining updates of step k issue.  Order of the other DPP reads: an update of step k reads a register written in
 // step k-1, with at least the pivot broadcast and the multiplier's instructions in between.  The inputs of step 0 come from
 // LDS loads (guarded by s_waitcnt) and, b, from the caller through pin().
+// (this form, with a select per use of the triangular structure, defines the values: it is what the host execution model and
+// the -DTMPC_NO_DPP_FMAC builds run; the product runs rows16_factor_masked below)
 template <int N>
-__device__ __forceinline__ bool rows16_factor(double (&row)[N], double &b, double &dinv, int lane) {
+__device__ __forceinline__ bool rows16_factor_select(double (&row)[N], double &b, double &dinv, int lane) {
     static_assert(N <= 16, "one matrix row per lane of a 16-lane DPP row");
     const int l16 = lane & 15;
     bool ok = true;
@@ -354,7 +356,7 @@ __device__ __forceinline__ void rows16_forward(const double (&row)[N], double &b
     });
 }
 template <int N>
-__device__ __forceinline__ double rows16_backsub_lane(const double (&row)[N], double b, double dinv, int lane) {
+__device__ __forceinline__ double rows16_backsub_lane_select(const double (&row)[N], double b, double dinv, int lane) {
     const int l16 = lane & 15;
     double xl = 0.0;
     static_for_n<N>([&](auto r_) {
@@ -365,6 +367,173 @@ __device__ __forceinline__ double rows16_backsub_lane(const double (&row)[N], do
         b = fma(-row[i], xi, b);
     });
     return xl;
+}
+
+// ---- the factorisation and the back substitution without the selects.  `l16 > k`, `l16 == k` and `l16 <= i` are lane patterns
+// known at compile time: instead of a compare and two v_cndmask_b32 per 64-bit select, the few instructions that belong to a
+// pattern run with EXEC set to it (two s_mov_b32 of a literal; the scalar unit, not the vector pipe the wave shares).  The values
+// are those of the select forms above, on every lane and in every 16-lane row:
+//   - a multiplier that the select form sets to zero IS zero here too (the updates multiply by it under full EXEC: an infinity
+//     in an excluded lane still makes a NaN, and -0 + 0 still gives +0) -- only HOW the zero gets there changes;
+//   - the back substitution masks the update itself, which the select form applies to every lane, because the lanes it
+//     excludes hold values that nothing reads afterwards (lane i is done once step i has taken its x_i = b_i / d_i).
+// All 64 lanes must be active at the call (the DPP broadcasts of the select forms need that as well): every statement restores
+// EXEC to -1, so that nothing the compiler places between two statements runs under a pattern.
+// A DPP read of a lane that EXEC disables does not deliver its value: the factorisation keeps its DPP instructions outside the
+// masked stretches, the back substitution's pattern includes the lane it broadcasts.  A scalar write of EXEC needs no wait
+// state in front of a DPP instruction (the five wait states are for a VECTOR write of EXEC).
+// (-DTMPC_DEBUG_EXEC: diagnostic builds trap where a masked routine is entered with a lane switched off -- a caller under a divergent
+// branch would otherwise get its idle lanes switched on by the restore)
+__device__ __forceinline__ void expect_full_exec() {
+#if defined(TMPC_DEBUG_EXEC) && !defined(TMPC_HOST_SIM)
+    if (__builtin_amdgcn_read_exec() != ~0ull) __builtin_trap();
+#endif
+}
+constexpr unsigned lanes4x16(unsigned m16) { return (m16 & 0xFFFFu) * 0x10001u; }      // the same 16-lane pattern in all four rows, per EXEC half
+constexpr unsigned m16_gt(int k) { return (0xFFFFu << (k + 1)) & 0xFFFFu; }
+constexpr unsigned m16_eq(int k) { return 1u << k; }
+constexpr unsigned m16_le(int i) { return (2u << i) - 1u; }
+
+// step K of the factorisation, everything that depends on the lane's place:  lanes above K: f = rk * pinv, rk = f, nf = -f;
+// lane K: dinv = pinv, nf = -0.  Lanes below K keep the -0 they got as lane K of their own step: nf is ONE register through
+// all steps (step 0 writes every lane of it).
+template <int K>
+__device__ __forceinline__ void factor_scale(double &nf, double &rk, double &dinv, double pinv, int l16) {
+#if defined(TMPC_HOST_SIM) || defined(TMPC_NO_DPP_FMAC)
+    if (l16 > K) {
+        const double f = rk * pinv;
+        nf = -f;
+        rk = f;
+    }
+    if (l16 == K) {
+        dinv = pinv;
+        nf = -0.0;
+    }
+#else
+    (void)l16;
+    constexpr int GT = static_cast<int>(lanes4x16(m16_gt(K))), EQ = static_cast<int>(lanes4x16(m16_eq(K)));
+    if constexpr (K == 0)
+        asm volatile("s_mov_b32 exec_lo, %4\n\ts_mov_b32 exec_hi, %4\n\t"
+                     "v_mul_f64 %0, -%1, %3\n\tv_mul_f64 %1, %1, %3\n\t"
+                     "s_mov_b32 exec_lo, %5\n\ts_mov_b32 exec_hi, %5\n\t"
+                     "v_mov_b64 %2, %3\n\tv_lshlrev_b64 %0, 63, 1\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "=&v"(nf), "+v"(rk), "+v"(dinv) : "v"(pinv), "n"(GT), "n"(EQ));
+    else if constexpr (K < 15)
+        asm volatile("s_mov_b32 exec_lo, %4\n\ts_mov_b32 exec_hi, %4\n\t"
+                     "v_mul_f64 %0, -%1, %3\n\tv_mul_f64 %1, %1, %3\n\t"
+                     "s_mov_b32 exec_lo, %5\n\ts_mov_b32 exec_hi, %5\n\t"
+                     "v_mov_b64 %2, %3\n\tv_lshlrev_b64 %0, 63, 1\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(nf), "+v"(rk), "+v"(dinv) : "v"(pinv), "n"(GT), "n"(EQ));
+    else      // (no lane above 15)
+        asm volatile("s_mov_b32 exec_lo, %3\n\ts_mov_b32 exec_hi, %3\n\t"
+                     "v_mov_b64 %1, %2\n\tv_lshlrev_b64 %0, 63, 1\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(nf), "+v"(dinv) : "v"(pinv), "n"(EQ));
+#endif
+}
+// step I of the back substitution on the lanes up to I:  x = b * dinv (lane I's is x_I and stays: the later steps run on fewer
+// lanes), then b -= r * (x of lane I).  The fused DPP multiply-add takes the negation as a source modifier; the lanes above I,
+// whose b nothing reads any more, sit the step out.  Lane I's own b is spent by the update, which is why x is taken first.
+template <int I>
+__device__ __forceinline__ void backsub_step(double &b, double &x, double dinv, double r, int l16) {
+#if defined(TMPC_HOST_SIM) || defined(TMPC_NO_DPP_FMAC)
+    if (l16 <= I) x = b * dinv;
+    const double xi = row_bcast_d<I>(x);
+    if (l16 <= I) b = fma(xi, -r, b);
+#else
+    (void)l16;
+    constexpr int LE = static_cast<int>(lanes4x16(m16_le(I)));
+    if constexpr (I > 0)
+        asm volatile("s_mov_b32 exec_lo, %4\n\ts_mov_b32 exec_hi, %4\n\t"
+                     "v_mul_f64 %1, %0, %2\n\t"
+                     "s_nop 1\n\t"
+                     "v_fmac_f64_dpp %0, %1, -%3 row_newbcast:%5 row_mask:0xf bank_mask:0xf\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(b), "+v"(x) : "v"(dinv), "v"(r), "n"(LE), "n"(I));
+    else      // (nothing below lane 0 to update)
+        asm volatile("s_mov_b32 exec_lo, %3\n\ts_mov_b32 exec_hi, %3\n\t"
+                     "v_mul_f64 %0, %1, %2\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(x) : "v"(b), "v"(dinv), "n"(LE));
+#endif
+}
+
+// rows16_factor_select with factor_scale at the head of every step: the same software pipeline (the next pivot's reciprocal under
+// the updates), the same order of the DPP reads -- factor_scale's vector instructions now stand, volatile, between the last write
+// of step k - 1 and the first DPP read of step k, where the select form had the multiplier's -- and one register less (pinv_k need
+// not outlive the step: dinv takes it at the head).
+template <int N>
+__device__ __forceinline__ bool rows16_factor_masked(double (&row)[N], double &b, double &dinv, int lane) {
+    static_assert(N <= 16, "one matrix row per lane of a 16-lane DPP row");
+    const int l16 = lane & 15;
+    bool ok = true;
+    expect_full_exec();
+    pin(b);
+    // (row[0] may come straight from the caller's vector instructions -- the working-set matrix of the refinement is built by
+    // selects --, and with the multiplier's selects gone nothing of this routine is left to stand in between: two wait states)
+    double pkk = row_bcast_ordered<0, 2>(row[0]);
+    double pinv = fast_rcp(pkk);
+    double nf = -0.0;
+    static_for_n<N>([&](auto k_) {
+        constexpr int k = decltype(k_)::value;
+        ok = ok && (pkk > 0.0);
+        factor_scale<k>(nf, row[k], dinv, pinv, l16);
+        constexpr int NU = N - 1 - k;
+        static_for_n<(NU < 3 ? NU : 3)>([&](auto j_) {
+            constexpr int j = k + 1 + decltype(j_)::value;
+            fmac_bcast<k, 0>(row[j], row[j], nf);
+        });
+        if constexpr (NU < 3) fmac_bcast<k, 0>(b, b, nf);
+        if constexpr (k + 1 < N) {
+            pkk = row_bcast_ordered<k + 1, (NU == 1 ? 2 : 0)>(row[k + 1]);
+            pinv = fast_rcp(pkk);
+        }
+        if constexpr (NU >= 3) {
+            static_for_n<NU - 3>([&](auto j_) {
+                constexpr int j = k + 4 + decltype(j_)::value;
+                fmac_bcast<k, 0>(row[j], row[j], nf);
+            });
+            fmac_bcast<k, 0>(b, b, nf);
+        }
+    });
+    return __builtin_amdgcn_readfirstlane(static_cast<int>(ok)) != 0;
+}
+// One chain as in the select form -- product, broadcast, update --, two vector instructions a step instead of six.  Lanes beyond
+// N return 0 as there.
+template <int N>
+__device__ __forceinline__ double rows16_backsub_lane_masked(const double (&row)[N], double b, double dinv, int lane) {
+    static_assert(N <= 16, "one matrix row per lane of a 16-lane DPP row");
+    const int l16 = lane & 15;
+    double xl = 0.0;
+    expect_full_exec();
+    static_for_n<N>([&](auto r_) {
+        constexpr int i = N - 1 - decltype(r_)::value;
+        backsub_step<i>(b, xl, dinv, row[i], l16);
+    });
+    return xl;
+}
+// (the forward substitution keeps its selects: its zero multipliers reach values that ARE read afterwards, so the update
+// cannot be masked, and a masked copy of the multiplier costs the vector pipe what the select does)
+// SELECT: the caller asks for the select forms (a kernel at the 256-register limit whose allocation the volatile statements of the
+// masked forms tip into a spill: tmpc_kernels.hip names it)
+// (-DTMPC_SELECT_FORMS: the select forms throughout, everything else as shipped -- csrc/Makefile builds lib/libtmpc_hip_select.so
+// that way, the reference of tests/test_select_free_end_to_end_gpu.py)
+#if defined(TMPC_HOST_SIM) || defined(TMPC_NO_DPP_FMAC) || defined(TMPC_SELECT_FORMS)
+constexpr bool MASKED_FORMS = false;
+#else
+constexpr bool MASKED_FORMS = true;
+#endif
+template <int N, bool SELECT = false>
+__device__ __forceinline__ bool rows16_factor(double (&row)[N], double &b, double &dinv, int lane) {
+    if constexpr (MASKED_FORMS && !SELECT) return rows16_factor_masked<N>(row, b, dinv, lane);
+    else return rows16_factor_select<N>(row, b, dinv, lane);
+}
+template <int N, bool SELECT = false>
+__device__ __forceinline__ double rows16_backsub_lane(const double (&row)[N], double b, double dinv, int lane) {
+    if constexpr (MASKED_FORMS && !SELECT) return rows16_backsub_lane_masked<N>(row, b, dinv, lane);
+    else return rows16_backsub_lane_select<N>(row, b, dinv, lane);
 }
 // ---- 16 < N <= 32: TWO matrix rows per lane -- lane i of every 16-lane row holds rows i (`ra`) and i + 16 (`rb`) -- so that every
 // pivot row sits on a lane of the SAME 16-lane row as the rows it updates and the DPP forms above apply: an update is one
@@ -517,9 +686,9 @@ constexpr int DPP_ROW = 0;
 #else
 constexpr int DPP_ROW = 16;
 #endif
-template <int N>
+template <int N, bool SELECT = false>
 __device__ __forceinline__ bool lanes_factor(double (&row)[N], double &b, double &dinv, int lane) {
-    if constexpr (N <= DPP_ROW) return rows16_factor<N>(row, b, dinv, lane);
+    if constexpr (N <= DPP_ROW) return rows16_factor<N, SELECT>(row, b, dinv, lane);
     else return rows_factor<N>(row, b, dinv, lane);
 }
 template <int N>
@@ -527,9 +696,9 @@ __device__ __forceinline__ void lanes_forward(const double (&row)[N], double &b,
     if constexpr (N <= DPP_ROW) rows16_forward<N>(row, b, lane);
     else rows_forward<N>(row, b, lane);
 }
-template <int N>
+template <int N, bool SELECT = false>
 __device__ __forceinline__ double lanes_backsub_lane(const double (&row)[N], double b, double dinv, int lane) {
-    if constexpr (N <= DPP_ROW) return rows16_backsub_lane<N>(row, b, dinv, lane);
+    if constexpr (N <= DPP_ROW) return rows16_backsub_lane<N, SELECT>(row, b, dinv, lane);
     else return rows_backsub_lane<N>(row, b, dinv, lane);
 }
 
