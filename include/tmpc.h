@@ -943,6 +943,33 @@ int tmpc_estimate_w_models(int device, int32_t nx, int32_t nu, const double *A, 
  *   F nv*2nx = [F1 F2], Ebar nc*2nx = [E 0], Y ny*nv and Yp ny*2nx (y = Y z + Yp [x_k | ref]), Rec nv*(ny + 2nx): z = Rec [y | x_k | ref],
  *   the map back from a solve's outputs (theta by least squares from xu_ss).  Refusals as above.
  * Added without an ABI bump: new exports, nothing else changed.
+ *
+ * Gradients with respect to the weights Q, R, P, T of tmpc_problem, summed over the batch (K, K_anc and all sets held fixed; the four
+ * count as independent symmetric parameters of the QP -- a caller who ties P to (Q, R) chains through their own Riccati code).  With
+ * v = Y' ybar_b the reverse mode solves [H G_A'; G_A 0] [a_b; q_b] = [v; 0] on the working set; for a loss l(y)
+ *   dl = -a' dH z - a' dF p   =>   Hbar = -1/2 sum_b (a_b z_b' + z_b a_b'),   Fbar = -sum_b a_b p_b'
+ * (dH symmetric), and H, F are linear in the weights: H = 2 sum L'W L, F1 = 2 sum L'W Dx, F2 = 2 sum L'W Dr over the error signals
+ * e = L z + Dx x_k + Dr ref priced with W, so  Wbar = sym(2 sum (L Hbar L' + L F1bar Dx' + L F2bar Dr')).  SKIPPED instances add nothing.
+ * The sums over b run in a fixed order (chunks of 256 instances, then the chunks in order; no atomics): two calls give equal bytes.
+ *
+ * tmpc_sens_vjp_weights(h, B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, ybar, pbar, Qbar, Rbar, Pbar, Tbar, flag, n_active):
+ *   HOST pointers.  pbar, flag, n_active: the bytes tmpc_sens_vjp writes for the same inputs.  Qbar nx*nx, Rbar nu*nu, Pbar nx*nx,
+ *   Tbar nx*nx: symmetric, any of the four may be NULL; on an extended handle the contributions of both variants are added.
+ * tmpc_sens_vjp_weights_device: the per-instance arrays (x_k .. n_active) are DEVICE pointers under the ordering contract of
+ *   tmpc_sens_vjp_device (same ranges read and written; the call counts in tmpc_debug_lane_counters).  Qbar, Rbar, Pbar, Tbar are HOST
+ *   pointers: the call returns once they are in place, after it has synchronised ITS OWN launch lane (the map from Hbar, Fbar to the
+ *   weights is a few MFLOP on an nv x (nv + 2 nx) block and runs on the host).  pbar, flag, n_active are complete then as well.
+ *   Workspace per lane: 2 B nv + ceil(B / 256) nv (nv + 2 nx) doubles.
+ * Refusals: those of tmpc_sens_vjp / tmpc_sens_vjp_device.
+ * tmpc_sens_weight_map(h, variant, Hbar, Fbar, Qbar, Rbar, Pbar, Tbar): the map alone, on the host (works on a host-only handle):
+ *   Hbar nv*nv, Fbar nv*2nx = [F1bar F2bar] in; symmetric matrices out, any may be NULL.  Under a terminal equality the terminal error
+ *   x_N - x_bar is zero, so Pbar = 0.  Refused: NULL handle, Hbar or Fbar, a variant out of range (TMPC_E_INVALID); a regulator handle, a
+ *   variant that keeps unpriced auxiliaries (TMPC_E_UNSUPPORTED).
+ * tmpc_qp_sensitivity_data(device, nv, nc, np, ny, H, F, G, g0, Ebar, Y, Yp, B, P, Z, status, act_tol, ybar, pbar, Hbar, Fbar, adj, flag,
+ *   n_active): the handle-free entry on raw condensed data, beside tmpc_qp_sensitivity (same limits and refusals; HOST pointers):
+ *   pbar [B][np] (or NULL) as tmpc_qp_sensitivity(mode = VJP) writes it, Hbar nv*nv (symmetric), Fbar nv*np, adj [B][nv] (or NULL) the a_b.
+ *   The a_b behind Hbar, Fbar and adj take one step of refinement on the constraint rows, a = a0 - W_A' M^-1 (G_A a0) with a0 the a_b behind
+ *   pbar (the exact a_b has G_A a_b = 0; with |A| = nv it is zero); pbar is that of tmpc_sens_vjp, untouched.
  */
 #define TMPC_SENS_SKIPPED   0x1
 #define TMPC_SENS_DEPENDENT 0x2
@@ -963,6 +990,17 @@ int tmpc_sens_vjp_device(tmpc_handle *h, int64_t B, const double *x_k, const dou
                          const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, const double *ybar, double *pbar,
                          int32_t *flag, int32_t *n_active);
 int tmpc_sens_get_model(tmpc_handle *h, int variant, double *F, double *Ebar, double *Y, double *Yp, double *Rec);
+int tmpc_sens_vjp_weights(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                          const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, const double *ybar, double *pbar,
+                          double *Qbar, double *Rbar, double *Pbar, double *Tbar, int32_t *flag, int32_t *n_active);
+int tmpc_sens_vjp_weights_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                                 const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, const double *ybar, double *pbar,
+                                 double *Qbar, double *Rbar, double *Pbar, double *Tbar, int32_t *flag, int32_t *n_active);
+int tmpc_sens_weight_map(tmpc_handle *h, int variant, const double *Hbar, const double *Fbar, double *Qbar, double *Rbar, double *Pbar, double *Tbar);
+int tmpc_qp_sensitivity_data(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
+                             const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t B, const double *P, const double *Z,
+                             const int32_t *status, double act_tol, const double *ybar, double *pbar, double *Hbar, double *Fbar, double *adj,
+                             int32_t *flag, int32_t *n_active);
 int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
                         const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t B, const double *P, const double *Z,
                         const int32_t *status, double act_tol, int mode, const double *ybar, double *out, int32_t *flag, int32_t *n_active,

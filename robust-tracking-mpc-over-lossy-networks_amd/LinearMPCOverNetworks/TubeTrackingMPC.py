@@ -348,6 +348,28 @@ class TubeTrackingMPC(TubeRegulatorMPC):
     def get_ancillary_controller_gain(self):
         return self._K if self._K_ancillary is None else self._K_ancillary
 
+    def set_cost_weights(self, Q=None, R=None, P=None, T=None):
+        """Replaces the given weights of the QP -- stage weights Q, R, terminal weight P, offset weight T (None: kept) -- and re-creates
+        the device problem from the sets already loaded.  The gains K and K_anc and every set (Z, Xc, Uc, Xf, ...) are UNTOUCHED: they
+        were computed with the weights of the constructor and stay valid constraints, but P is no longer tied to (Q, R) by a Riccati
+        equation unless the caller keeps it so.  The old handle goes with what it owned: its law tables, its sensitivity model, its
+        kernel-path setting.  A refusal of tmpc_create (a weight that makes H indefinite) is raised with the library's message, and the
+        controller keeps its previous weights and handle."""
+        from . import _native
+        old = (self._Q, self._R, self._P, self._Tout)
+        sym = lambda W, like: like if W is None else np.ascontiguousarray(0.5 * (np.asarray(W, dtype=np.float64).reshape(like.shape)
+                                                                                 + np.asarray(W, dtype=np.float64).reshape(like.shape).T))
+        self._Q, self._R, self._P, self._Tout = sym(Q, self._Q), sym(R, self._R), sym(P, self._P), sym(T, self._Tout)
+        if self._handle is None:
+            return
+        try:
+            new = _native.create(self._problem_dict(), self._device)
+        except Exception:
+            self._Q, self._R, self._P, self._Tout = old
+            raise
+        self._close()
+        self._handle = new
+
     def get_steady_state_controller_gain(self):
         return self._K
 

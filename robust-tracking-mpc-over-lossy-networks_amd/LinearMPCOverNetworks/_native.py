@@ -225,6 +225,16 @@ def lib():
             getattr(L, name).restype = C.c_int
         L.tmpc_sens_get_model.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.tmpc_sens_get_model.restype = C.c_int
+        if hasattr(L, "tmpc_sens_vjp_weights"):     # (an older build loaded through TMPC_LIB for an A/B has none of these)
+            vjpw = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_double] + [C.c_void_p] * 8
+            for name in ("tmpc_sens_vjp_weights", "tmpc_sens_vjp_weights_device"):
+                getattr(L, name).argtypes = vjpw
+                getattr(L, name).restype = C.c_int
+            L.tmpc_sens_weight_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+            L.tmpc_sens_weight_map.restype = C.c_int
+            L.tmpc_qp_sensitivity_data.argtypes = ([C.c_int] + [C.c_int32] * 4 + [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_double]
+                                                   + [C.c_void_p] * 7)
+            L.tmpc_qp_sensitivity_data.restype = C.c_int
         L.tmpc_qp_sensitivity.argtypes = ([C.c_int] + [C.c_int32] * 4 + [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_double, C.c_int]
                                           + [C.c_void_p] * 5)
         L.tmpc_qp_sensitivity.restype = C.c_int
@@ -1478,6 +1488,75 @@ def qp_sensitivity(H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol: float =
                                    out["flag"].ctypes.data, out["n_active"].ctypes.data, out["active"].ctypes.data if nc else None)
     if rc != 0:
         _sens_fail("tmpc_qp_sensitivity", rc, lib().tmpc_last_error(None).decode())
+    return out
+
+
+# ---- gradients with respect to the weights Q, R, P, T (include/tmpc.h: tmpc_sens_vjp_weights*, tmpc_sens_weight_map, tmpc_qp_sensitivity_data)
+def _weight_outputs(h: Handle) -> dict:
+    return dict(Qbar=np.empty((h.nx, h.nx)), Rbar=np.empty((h.nu, h.nu)), Pbar=np.empty((h.nx, h.nx)), Tbar=np.empty((h.nx, h.nx)))
+
+
+def sens_vjp_weights(h: Handle, x, ref, sol: dict, ybar, variant=None, act_tol: float = 0.0) -> dict:
+    """Host-pointer entry (tmpc_sens_vjp_weights): the vector-Jacobian products of tmpc_sens_vjp and the gradients of the same scalar with
+    respect to the four weights, summed over the batch -> pbar (B, 2nx), Qbar, Rbar, Pbar, Tbar (symmetric), flag, n_active."""
+    B, x, ref, var, u, x0, ss, st = _sens_inputs(h, x, ref, variant, sol)
+    ny = h.N * h.nu + 2 * h.nx + h.nu
+    ybar = np.ascontiguousarray(np.asarray(ybar, dtype=np.float64).reshape(B, ny))
+    out = dict(pbar=np.empty((B, 2 * h.nx)), flag=np.empty(B, np.int32), n_active=np.empty(B, np.int32), **_weight_outputs(h))
+    rc = lib().tmpc_sens_vjp_weights(h.ptr, B, x.ctypes.data, ref.ctypes.data, _ptr(var), u.ctypes.data, x0.ctypes.data, ss.ctypes.data, _ptr(st),
+                                     float(act_tol), ybar.ctypes.data, out["pbar"].ctypes.data, out["Qbar"].ctypes.data, out["Rbar"].ctypes.data,
+                                     out["Pbar"].ctypes.data, out["Tbar"].ctypes.data, out["flag"].ctypes.data, out["n_active"].ctypes.data)
+    if rc != 0:
+        _sens_fail("tmpc_sens_vjp_weights", rc, h.error())
+    return out
+
+
+def sens_vjp_weights_device(h: Handle, B: int, x_ptr, r_ptr, var_ptr, u_ptr, x0_ptr, ss_ptr, st_ptr, act_tol, ybar_ptr, pbar_ptr, flag_ptr, nact_ptr) -> dict:
+    """Device-pointer entry (tmpc_sens_vjp_weights_device): raw addresses for the per-instance arrays; the four gradients are numpy arrays
+    on the host.  Returns them once they are in place: the call has synchronised its own launch lane, pbar / flag / n_active are complete."""
+    out = _weight_outputs(h)
+    rc = lib().tmpc_sens_vjp_weights_device(h.ptr, int(B), x_ptr, r_ptr, var_ptr, u_ptr, x0_ptr, ss_ptr, st_ptr, float(act_tol), ybar_ptr, pbar_ptr,
+                                            out["Qbar"].ctypes.data, out["Rbar"].ctypes.data, out["Pbar"].ctypes.data, out["Tbar"].ctypes.data,
+                                            flag_ptr, nact_ptr)
+    if rc != 0:
+        _sens_fail("tmpc_sens_vjp_weights_device", rc, h.error())
+    return out
+
+
+def sens_weight_map(h: Handle, Hbar, Fbar, variant: int = 0) -> dict:
+    """include/tmpc.h: tmpc_sens_weight_map -- the adjoint of the condensing's cost assembly on the host (works on a host-only handle):
+    Hbar (nv, nv), Fbar (nv, 2nx) -> Qbar, Rbar, Pbar, Tbar (symmetric)."""
+    nv = get_dims(h, variant)[0]
+    Hbar = _contiguous(Hbar).reshape(nv, nv)
+    Fbar = _contiguous(Fbar).reshape(nv, 2 * h.nx)
+    out = _weight_outputs(h)
+    rc = lib().tmpc_sens_weight_map(h.ptr, int(variant), Hbar.ctypes.data, Fbar.ctypes.data, *[out[k].ctypes.data for k in ("Qbar", "Rbar", "Pbar", "Tbar")])
+    if rc != 0:
+        _sens_fail("tmpc_sens_weight_map", rc, h.error())
+    return out
+
+
+def qp_sensitivity_data(H, F, G, g0, Ebar, Y, Yp, P, Z, ybar, status=None, act_tol: float = 0.0, device: int = 0) -> dict:
+    """include/tmpc.h: tmpc_qp_sensitivity_data -- the reverse mode on raw condensed data with the gradients with respect to H and F, summed
+    over the batch; arguments and result as LinearMPCOverNetworks.sensitivity.qp_sensitivity_data, its numpy twin:
+    -> pbar (B, np), Hbar (nv, nv), Fbar (nv, np), adj (B, nv), flag, n_active."""
+    H, F, G, g0, Ebar, Y, Yp = (_contiguous(a) for a in (H, F, G, g0, Ebar, Y, Yp))
+    nv, npar = F.shape
+    nc, ny = g0.shape[0], Y.shape[0]
+    P = _contiguous(P).reshape(-1, npar)
+    Z = _contiguous(Z).reshape(-1, nv)
+    B = P.shape[0]
+    st = None if status is None else np.ascontiguousarray(np.asarray(status, dtype=np.int32).reshape(B))
+    yb = _contiguous(ybar).reshape(B, ny)
+    out = dict(pbar=np.empty((B, npar)), Hbar=np.empty((nv, nv)), Fbar=np.empty((nv, npar)), adj=np.empty((B, nv)), flag=np.empty(B, np.int32),
+               n_active=np.empty(B, np.int32))
+    rc = lib().tmpc_qp_sensitivity_data(int(device), nv, nc, npar, ny, H.ctypes.data, F.ctypes.data, G.ctypes.data if nc else None,
+                                        g0.ctypes.data if nc else None, Ebar.ctypes.data if nc else None, Y.ctypes.data, Yp.ctypes.data, B,
+                                        P.ctypes.data, Z.ctypes.data, _ptr(st), float(act_tol), yb.ctypes.data, out["pbar"].ctypes.data,
+                                        out["Hbar"].ctypes.data, out["Fbar"].ctypes.data, out["adj"].ctypes.data, out["flag"].ctypes.data,
+                                        out["n_active"].ctypes.data)
+    if rc != 0:
+        _sens_fail("tmpc_qp_sensitivity_data", rc, lib().tmpc_last_error(None).decode())
     return out
 
 

@@ -70,6 +70,7 @@ def qp_sensitivity(H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol: float =
     n_active = np.zeros(B, np.int32)
     active = np.zeros((B, (nc + 31) // 32), np.uint32)
     lams = [None] * B
+    adj = np.zeros((B, nv))           # (reverse mode) a_b of  [H G_A'; G_A 0] [a; q] = [Y' ybar_b; 0];  zeros where SKIPPED
     cache = {}
     for b in range(B):
         p, z = P[b], Z[b]
@@ -102,6 +103,9 @@ def qp_sensitivity(H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol: float =
             q = Li.T @ (Li @ (WA @ v))
             x = Hinv @ v - WA.T @ q
             out[b] = Yp.T @ ybar[b] - F.T @ x + EA.T @ q
+            # (the plain formula.  The kernel's adj output takes one more step, a refinement on the constraint rows,
+            # a = x - W_A' M^-1 (G_A x): the exact a has G_A a = 0.  The twin stays the less accurate of the two.)
+            adj[b] = x
         else:
             D = -(Li.T @ (Li @ (WA @ F + EA)))
             dz = -HinvF - WA.T @ D
@@ -111,7 +115,21 @@ def qp_sensitivity(H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol: float =
         for i in kept:
             active[b, i >> 5] |= np.uint32(1 << (i & 31))
         lams[b] = lam
-    return dict(out=out, flag=flag, n_active=n_active, active=active, lam=lams)
+    return dict(out=out, flag=flag, n_active=n_active, active=active, lam=lams, **(dict(adj=adj) if vjp else {}))
+
+
+def qp_sensitivity_data(H, F, G, g0, Ebar, Y, Yp, P, Z, ybar, status=None, act_tol: float = 0.0) -> dict:
+    """The numpy twin of tmpc_qp_sensitivity_data: the reverse mode of `qp_sensitivity` (same working set, same factorisation) and, from
+    its a_b, the gradients of the scalar behind ybar with respect to the QP's data, summed over the batch:
+        Hbar = -1/2 sum_b (a_b z_b' + z_b a_b'),   Fbar = -sum_b a_b p_b'      (SKIPPED instances add nothing)
+    -> dict(pbar (B, np), adj (B, nv), Hbar (nv, nv) symmetric, Fbar (nv, np), flag, n_active)."""
+    r = qp_sensitivity(H, F, G, g0, Ebar, Y, Yp, P, Z, status=status, act_tol=act_tol, mode="vjp", ybar=ybar)
+    nv, npar = np.shape(F)
+    live = (r["flag"] & SKIPPED) == 0
+    a = r["adj"][live]
+    C = a.T @ np.asarray(Z, dtype=np.float64).reshape(-1, nv)[live]
+    return dict(pbar=r["out"], adj=r["adj"], Hbar=-0.5 * (C + C.T), Fbar=-(a.T @ np.asarray(P, dtype=np.float64).reshape(-1, npar)[live]),
+                flag=r["flag"], n_active=r["n_active"])
 
 
 def decode_active(active, nc=None):
@@ -175,6 +193,40 @@ def handle_sensitivity(mpc_or_handle, x, ref, sol: dict, variant=None, act_tol: 
         out[idx], flag[idx], n_active[idx] = r["out"], r["flag"], r["n_active"]
         active[idx, :r["active"].shape[1]] = r["active"]
     return dict(out=out, flag=flag, n_active=n_active, active=active)
+
+
+def handle_weight_gradients(mpc_or_handle, x, ref, sol: dict, ybar, variant=None, act_tol: float = 0.0) -> dict:
+    """The twin of tmpc_sens_vjp_weights on a handle's problem (device or host-only): `qp_sensitivity_data` per problem variant on the
+    tmpc_get_condensed / tmpc_sens_get_model data, each variant's (Hbar, Fbar) through `_native.sens_weight_map`, the contributions added.
+    K, K_anc and the sets are held fixed; Q, R, P, T count as independent symmetric parameters.
+    -> dict(pbar (B, 2nx), Qbar, Rbar, Pbar, Tbar, flag, n_active)."""
+    from . import _native
+    h = getattr(mpc_or_handle, "_handle", mpc_or_handle)
+    x = np.asarray(x, dtype=np.float64).reshape(-1, h.nx)
+    B = x.shape[0]
+    ref = np.broadcast_to(np.asarray(ref, dtype=np.float64).reshape(-1, h.nx), (B, h.nx))
+    var = np.zeros(B, np.uint8) if variant is None else np.broadcast_to(np.asarray(variant, dtype=np.uint8).reshape(-1), (B,))
+    ny = h.N * h.nu + 2 * h.nx + h.nu
+    ybar = np.asarray(ybar, dtype=np.float64).reshape(B, ny)
+    out = dict(pbar=np.full((B, 2 * h.nx), np.nan), flag=np.full(B, SKIPPED, np.int32), n_active=np.zeros(B, np.int32),
+               Qbar=np.zeros((h.nx, h.nx)), Rbar=np.zeros((h.nu, h.nu)), Pbar=np.zeros((h.nx, h.nx)), Tbar=np.zeros((h.nx, h.nx)))
+    status = sol.get("status")
+    for k in range(h.nvariants if variant is not None else 1):
+        idx = np.flatnonzero(var == k)
+        if not len(idx):
+            continue
+        m = condensed_model(h, k)
+        good = np.isfinite(sol["u_nom"][idx].reshape(len(idx), -1)).all(axis=1) & np.isfinite(sol["x_nom0"][idx]).all(axis=1) \
+            & np.isfinite(sol["xu_ss"][idx]).all(axis=1)
+        Z = z_from_outputs(m, x[idx], ref[idx], np.nan_to_num(sol["u_nom"][idx]), np.nan_to_num(sol["x_nom0"][idx]), np.nan_to_num(sol["xu_ss"][idx]))
+        Z[~good] = np.nan
+        r = qp_sensitivity_data(m["H"], m["F"], m["G"], m["g0"], m["Ebar"], m["Y"], m["Yp"], np.c_[x[idx], ref[idx]], Z, ybar[idx],
+                                status=None if status is None else np.asarray(status)[idx], act_tol=act_tol)
+        out["pbar"][idx], out["flag"][idx], out["n_active"][idx] = r["pbar"], r["flag"], r["n_active"]
+        w = _native.sens_weight_map(h, r["Hbar"], r["Fbar"], k)
+        for key in ("Qbar", "Rbar", "Pbar", "Tbar"):
+            out[key] += w[key]
+    return out
 
 
 def _dims(h, k):

@@ -386,18 +386,19 @@ std::string condense(const tmpc_problem &p, int variant, Condensed &out) {
 
     // ---- cost (TubeTrackingMPC.py:136,143,144):  sum ||e||^2_W  with e = L z + Dx x + Dr r
     c.H = Mat(nv, nv); c.F1 = Mat(nv, nx); c.F2 = Mat(nv, nx);
-    auto add_cost = [&](const Aff &e, const Mat &W) {
+    auto add_cost = [&](const Aff &e, const Mat &W, int w, bool keep = true) {
         const Mat LtW = mul(tr(e.L), W);
         axpy(c.H, mul(LtW, e.L), 2.0);
         axpy(c.F1, mul(LtW, e.Dx), 2.0);
         axpy(c.F2, mul(LtW, e.Dr), 2.0);
+        if (keep) c.cost.push_back({w, e.L, e.Dx, e.Dr});       // (for tmpc_sens_weight_map, the adjoint of these three sums)
     };
     for (int i = 0; i < N; ++i) {
-        add_cost(sub(x[i], xbar), Q);
-        add_cost(sub(u[i], ubar), R);
+        add_cost(sub(x[i], xbar), Q, 0);
+        add_cost(sub(u[i], ubar), R, 1);
     }
-    add_cost(sub(x[N], xbar), P);
-    add_cost(sub(xbar, rsig), T);
+    add_cost(sub(x[N], xbar), P, 2, !term_eq);       // (x_N == x_bar: the error is zero but for the rounding of the elimination)
+    add_cost(sub(xbar, rsig), T, 3);
     for (int i = 0; i < nv; ++i)
         for (int j = 0; j < i; ++j) { const double a = 0.5 * (c.H(i, j) + c.H(j, i)); c.H(i, j) = c.H(j, i) = a; }
     if (aux) {

@@ -44,6 +44,14 @@ struct Condensed {
     // unscaled:  min 1/2 z'Hz + (F1 x + F2 r)'z  s.t. G z <= g0 + E x ;  0 <= gp0 + Ep x
     Mat H, F1, F2, G, E, Ep, Mth;
     std::vector<double> g0, gp0;
+    // The error signals of the cost as condense() priced them: e = L z + Dx x_k + Dr ref with the weight `w` (0 Q, 1 R, 2 P, 3 T), so
+    // that  H = 2 sum L'W L,  F1 = 2 sum L'W Dx,  F2 = 2 sum L'W Dr.  tmpc_sens_weight_map is the adjoint of that sum.  Left out: the
+    // terminal error x_N - x_bar under a terminal equality, which the eliminated equality makes zero.  Empty for a regulator.
+    struct CostSignal {
+        int w;
+        Mat L, Dx, Dr;
+    };
+    std::vector<CostSignal> cost;
     // scaled: z = Dv .* zs, rows divided by rn (unit row norm after column scaling)
     std::vector<double> Dv;
     Mat Hs, Hinv, Gs, Es, F1s, F2s;

@@ -20,6 +20,7 @@ struct SensState {
     SensModel m[2];
     DeviceBuffer ws[tmpc::MAX_LANES];     // the kernel's right-hand-side blocks, one slice per workgroup; one buffer per launch lane
     DeviceBuffer stage;          // the host-pointer entries' device copies
+    DeviceBuffer wg[tmpc::MAX_LANES];     // tmpc_sens_vjp_weights*: adj | zrec | the partial tiles | Hbar, Fbar per variant; one buffer per launch lane
 };
 
 void release_sens(tmpc_handle *h) {
@@ -28,6 +29,7 @@ void release_sens(tmpc_handle *h) {
     for (SensModel &m : s->m)
         if (m.block) (void)hipFree(m.block);
     for (DeviceBuffer &b : s->ws) b.release();
+    for (DeviceBuffer &b : s->wg) b.release();
     s->stage.release();
     delete s;
     h->sens = nullptr;
@@ -271,7 +273,15 @@ struct SensCall {
     double *out;
     int32_t *flag, *n_active;
     uint32_t *active;
+    // tmpc_sens_vjp_weights*: the reduction over the batch runs behind each variant's launch, its results land here ([Hbar | Fbar] per variant)
+    std::vector<double> *wgrad = nullptr;
 };
+
+// Workgroups of the reduction's first kernel: one wave per tile and chunk, as many as there are or a few per compute unit
+unsigned wgrad_blocks(int64_t B, int n_cu, int nv, int np) {
+    const int64_t work = static_cast<int64_t>(tmpc::sens_wgrad_chunks(B)) * ((nv + 15) / 16) * ((nv + np + 15) / 16);
+    return static_cast<unsigned>(std::clamp<int64_t>(work, 1, 32 * static_cast<int64_t>(std::max(n_cu, 1))));
+}
 
 int nwords_of(const tmpc_handle *h) {
     int nc = 0;
@@ -316,6 +326,25 @@ int enqueue_sens(tmpc_handle *h, Lane &lane, const char *who, const SensCall &c)
         if (c.mode == tmpc::SENS_MODE_JACOBIAN) ws = std::max(ws, static_cast<size_t>(sens_blocks(c.B, h->n_cu, a.nv, a.np)) * 2 * a.nv * a.np * sizeof(double));
     }
     if (ws) HIP_TRY(h, wsbuf.reserve(ws, lane.stream));      // (a buffer that grows waits for its lane alone, the only one whose launches use it)
+    // the weight gradients' workspace: adj | zrec | partial tiles, used by one variant after the other, and [Hbar | Fbar] of each
+    DeviceBuffer &wgbuf = s.wg[&lane - h->lane];
+    size_t wg_part = 0, wg_res[2] = {0, 0}, wg_total = 0;
+    if (c.wgrad) {
+        size_t nvmax = 0, tile = 0;
+        for (int k = 0; k < nvar; ++k) {
+            const size_t nv = s.m[k].a.nv, N = nv + s.m[k].a.np;
+            nvmax = std::max(nvmax, nv);
+            tile = std::max(tile, nv * N);
+        }
+        const size_t vec = (static_cast<size_t>(c.B) * nvmax + 31) / 32 * 32;
+        wg_part = 2 * vec;
+        wg_total = wg_part + (tmpc::sens_wgrad_chunks(c.B) * tile + 31) / 32 * 32;
+        for (int k = 0; k < nvar; ++k) {
+            wg_res[k] = wg_total;
+            wg_total += (static_cast<size_t>(s.m[k].a.nv) * (s.m[k].a.nv + s.m[k].a.np) + 31) / 32 * 32;
+        }
+        HIP_TRY(h, wgbuf.reserve(wg_total * sizeof(double), lane.stream));
+    }
     const int nx = h->nx, nu = h->nu, N = h->N;
     if (const int rc = begin_timed_launch(h, lane)) return rc;       // (tmpc_last_kernel_ms reads the pair)
     for (int k = 0; k < nvar; ++k) {
@@ -329,10 +358,28 @@ int enqueue_sens(tmpc_handle *h, Lane &lane, const char *who, const SensCall &c)
         a.mode = c.mode; a.ybar = c.ybar; a.out = c.out; a.flag = c.flag; a.n_active = c.n_active; a.active = c.active;
         a.nwords = nwords_of(h);
         a.ws = c.mode == tmpc::SENS_MODE_JACOBIAN ? wsbuf.as<double>() : nullptr;
+        if (c.wgrad) {
+            a.adj = wgbuf.as<double>();
+            a.zrec = a.adj + wg_part / 2;
+        }
         HIP_TRY(h, tmpc::launch_sens(a, sens_blocks(c.B, h->n_cu, a.nv, a.np), lane.stream));
+        if (c.wgrad) {
+            tmpc::SensWgradArgs g{};
+            g.nv = a.nv; g.np = a.np; g.B = a.B; g.adj = a.adj; g.zrec = a.zrec; g.np0 = a.np0; g.P0 = a.P0; g.P1 = a.P1; g.flag = a.flag;
+            g.variant = a.variant; g.my_variant = k; g.nvariants = a.nvariants;
+            g.part = wgbuf.as<double>() + wg_part;
+            g.Hbar = wgbuf.as<double>() + wg_res[k];
+            g.Fbar = g.Hbar + static_cast<size_t>(a.nv) * a.nv;
+            HIP_TRY(h, tmpc::launch_sens_wgrad(g, wgrad_blocks(c.B, h->n_cu, a.nv, a.np), lane.stream));
+        }
     }
     HIP_TRY(h, hipEventRecord(h->ev1, lane.stream));
     h->timed = true;
+    for (int k = 0; c.wgrad && k < nvar; ++k) {
+        const size_t n = static_cast<size_t>(s.m[k].a.nv) * (s.m[k].a.nv + s.m[k].a.np);
+        c.wgrad[k].resize(n);
+        HIP_TRY(h, hipMemcpyAsync(c.wgrad[k].data(), wgbuf.as<double>() + wg_res[k], n * sizeof(double), hipMemcpyDeviceToHost, lane.stream));
+    }
     return TMPC_OK;
 }
 
@@ -378,7 +425,9 @@ int call_device(tmpc_handle *h, const char *who, const SensCall &c) {
     Lane *lane = nullptr;
     if (const int rc = pick_call_lane(h, call, &lane)) return rc;
     if (const int rc = enqueue_sens(h, *lane, who, c)) return rc;
-    return note_call(h, *lane, call);
+    if (const int rc = note_call(h, *lane, call)) return rc;
+    if (c.wgrad) HIP_TRY(h, hipStreamSynchronize(lane->stream));      // (the reduction's results are in host memory: the call's own lane alone)
+    return TMPC_OK;
 }
 
 int call_host(tmpc_handle *h, const char *who, const SensCall &c) {
@@ -419,6 +468,57 @@ int call_host(tmpc_handle *h, const char *who, const SensCall &c) {
 
 }  // namespace
 
+// The adjoint of the cost assembly of condense() for variant k:  M[w] += 2 sum over the error signals priced with weight w of
+// (L Hbar L' + L F1bar Dx' + L F2bar Dr'),  Fbar = [F1bar F2bar] ([nv][2 nx]).  M: Q [nx][nx], R [nu][nu], P [nx][nx], T [nx][nx].
+void weight_map_add(const tmpc_handle *h, int k, const double *Hbar, const double *Fbar, std::vector<double> (&M)[4]) {
+    const tmpc::Condensed &c = h->v[k].c;
+    const int nx = c.nx, nv = c.nv;
+    for (const tmpc::Condensed::CostSignal &e : c.cost) {
+        const int d = e.L.r;
+        std::vector<double> LH(static_cast<size_t>(d) * nv, 0.0), LF(static_cast<size_t>(d) * 2 * nx, 0.0);
+        for (int i = 0; i < d; ++i)
+            for (int t = 0; t < nv; ++t) {
+                const double l = e.L(i, t);
+                if (l == 0.0) continue;
+                for (int j = 0; j < nv; ++j) LH[static_cast<size_t>(i) * nv + j] += l * Hbar[static_cast<size_t>(t) * nv + j];
+                for (int j = 0; j < 2 * nx; ++j) LF[static_cast<size_t>(i) * 2 * nx + j] += l * Fbar[static_cast<size_t>(t) * 2 * nx + j];
+            }
+        std::vector<double> &m = M[e.w];
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) {
+                double s = 0.0;
+                for (int t = 0; t < nv; ++t) s += LH[static_cast<size_t>(i) * nv + t] * e.L(j, t);
+                for (int t = 0; t < nx; ++t) s += LF[static_cast<size_t>(i) * 2 * nx + t] * e.Dx(j, t) + LF[static_cast<size_t>(i) * 2 * nx + nx + t] * e.Dr(j, t);
+                m[static_cast<size_t>(i) * d + j] += 2.0 * s;
+            }
+    }
+}
+
+// The symmetric parts of M to the caller's matrices (any may be NULL): Wbar(i, j) and Wbar(j, i) are one number
+void write_weights(const tmpc_handle *h, const std::vector<double> (&M)[4], double *const (&out)[4]) {
+    const int dims[4] = {h->nx, h->nu, h->nx, h->nx};
+    for (int w = 0; w < 4; ++w) {
+        if (!out[w]) continue;
+        const size_t d = dims[w];
+        for (size_t i = 0; i < d; ++i)
+            for (size_t j = 0; j <= i; ++j) out[w][i * d + j] = out[w][j * d + i] = 0.5 * (M[w][i * d + j] + M[w][j * d + i]);
+    }
+}
+
+// tmpc_sens_vjp_weights[_device]: the VJP call with the reduction behind it, then the map to the weights on the host
+int weights_call(tmpc_handle *h, const char *who, bool device, SensCall c, double *const (&out)[4]) {
+    std::vector<double> res[2];
+    c.wgrad = res;
+    if (const int rc = device ? call_device(h, who, c) : call_host(h, who, c)) return rc;
+    const int dims[4] = {h->nx, h->nu, h->nx, h->nx};
+    std::vector<double> M[4];
+    for (int w = 0; w < 4; ++w) M[w].assign(static_cast<size_t>(dims[w]) * dims[w], 0.0);
+    for (int k = 0; k < (c.variant ? h->nvariants : 1); ++k)
+        if (!res[k].empty()) weight_map_add(h, k, res[k].data(), res[k].data() + static_cast<size_t>(h->v[k].c.nv) * h->v[k].c.nv, M);
+    write_weights(h, M, out);
+    return TMPC_OK;
+}
+
 // The region signatures of a solved batch for tmpc_law_learn: the sensitivity kernel in its one-column mode with a zero ybar (HOST pointers)
 int tmpc_host::sens_signatures(tmpc_handle *h, const char *who, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
                                const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, int32_t *flag, int32_t *n_active, uint32_t *active) {
@@ -453,6 +553,37 @@ int tmpc_sens_vjp_device(tmpc_handle *h, int64_t B, const double *x_k, const dou
     return call_device(h, "tmpc_sens_vjp_device", {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, tmpc::SENS_MODE_VJP, ybar, pbar, flag, n_active, nullptr});
 }
 
+int tmpc_sens_vjp_weights(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                          const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, const double *ybar, double *pbar,
+                          double *Qbar, double *Rbar, double *Pbar, double *Tbar, int32_t *flag, int32_t *n_active) {
+    return weights_call(h, "tmpc_sens_vjp_weights", false, {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, tmpc::SENS_MODE_VJP, ybar, pbar, flag, n_active, nullptr},
+                        {Qbar, Rbar, Pbar, Tbar});
+}
+
+int tmpc_sens_vjp_weights_device(tmpc_handle *h, int64_t B, const double *x_k, const double *ref, const uint8_t *variant, const double *u_nom,
+                                 const double *x_nom0, const double *xu_ss, const int32_t *status, double act_tol, const double *ybar, double *pbar,
+                                 double *Qbar, double *Rbar, double *Pbar, double *Tbar, int32_t *flag, int32_t *n_active) {
+    return weights_call(h, "tmpc_sens_vjp_weights_device", true, {B, x_k, ref, variant, u_nom, x_nom0, xu_ss, status, act_tol, tmpc::SENS_MODE_VJP, ybar, pbar, flag, n_active, nullptr},
+                        {Qbar, Rbar, Pbar, Tbar});
+}
+
+int tmpc_sens_weight_map(tmpc_handle *h, int variant, const double *Hbar, const double *Fbar, double *Qbar, double *Rbar, double *Pbar, double *Tbar) {
+    if (!h) return TMPC_E_INVALID;
+    if (variant < 0 || variant >= h->nvariants) { h->err = "tmpc_sens_weight_map: variant out of range"; return TMPC_E_INVALID; }
+    if (!Hbar || !Fbar) { h->err = "tmpc_sens_weight_map: NULL argument"; return TMPC_E_INVALID; }
+    if (h->regulator) { h->err = "tmpc_sens_weight_map: a regulator handle is not supported (tracking handles only)"; return TMPC_E_UNSUPPORTED; }
+    if (h->v[variant].c.off_aux >= 0) {
+        h->err = "tmpc_sens_weight_map: variant " + std::to_string(variant) + " keeps the unpriced auxiliaries of the literal terminal row, which the outputs do not determine (give HTP / hTP)";
+        return TMPC_E_UNSUPPORTED;
+    }
+    const int dims[4] = {h->nx, h->nu, h->nx, h->nx};
+    std::vector<double> M[4];
+    for (int w = 0; w < 4; ++w) M[w].assign(static_cast<size_t>(dims[w]) * dims[w], 0.0);
+    weight_map_add(h, variant, Hbar, Fbar, M);
+    write_weights(h, M, {Qbar, Rbar, Pbar, Tbar});
+    return TMPC_OK;
+}
+
 int tmpc_sens_get_model(tmpc_handle *h, int variant, double *F, double *Ebar, double *Y, double *Yp, double *Rec) {
     if (!h) return TMPC_E_INVALID;
     if (variant < 0 || variant >= h->nvariants) { h->err = "tmpc_sens_get_model: variant out of range"; return TMPC_E_INVALID; }
@@ -466,11 +597,16 @@ int tmpc_sens_get_model(tmpc_handle *h, int variant, double *F, double *Ebar, do
     return TMPC_OK;
 }
 
-int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
-                        const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t B, const double *P, const double *Z,
-                        const int32_t *status, double act_tol, int mode, const double *ybar, double *out, int32_t *flag, int32_t *n_active,
-                        uint32_t *active) {
-    const std::string who = "tmpc_qp_sensitivity: ";
+}  // extern "C"
+
+namespace {
+
+// tmpc_qp_sensitivity, and tmpc_qp_sensitivity_data (`data`: VJP mode, out may be NULL, with the reduction to Hbar and Fbar behind it)
+int qp_sens(const char *name, bool data, int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
+            const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t B, const double *P, const double *Z,
+            const int32_t *status, double act_tol, int mode, const double *ybar, double *out, int32_t *flag, int32_t *n_active,
+            uint32_t *active, double *Hbar, double *Fbar, double *adj) {
+    const std::string who = std::string(name) + ": ";
     auto refuse = [&](int rc, const std::string &msg) { g_create_error = who + msg; return rc; };
     if (nv < 1 || nv > tmpc::SENS_MAX_NV) return refuse(TMPC_E_INVALID, "nv = " + std::to_string(nv) + " is not in [1, " + std::to_string(tmpc::SENS_MAX_NV) + "]");
     if (nc < 0 || nc > tmpc::SENS_MAX_NC) return refuse(TMPC_E_INVALID, "nc = " + std::to_string(nc) + " is not in [0, 2^20]");
@@ -478,9 +614,13 @@ int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t 
     if (ny < 1 || ny > tmpc::SENS_MAX_NY) return refuse(TMPC_E_INVALID, "ny = " + std::to_string(ny) + " is not in [1, " + std::to_string(tmpc::SENS_MAX_NY) + "]");
     if (B < 0) return refuse(TMPC_E_INVALID, "B < 0");
     if (mode != TMPC_SENS_JACOBIAN && mode != TMPC_SENS_VJP) return refuse(TMPC_E_INVALID, "mode is TMPC_SENS_JACOBIAN or TMPC_SENS_VJP");
-    if (!H || !F || (nc > 0 && (!G || !g0 || !Ebar)) || !Y || !Yp || !P || !Z || !out || !flag || !n_active || (mode == TMPC_SENS_VJP && !ybar))
+    if (!H || !F || (nc > 0 && (!G || !g0 || !Ebar)) || !Y || !Yp || !P || !Z || (!data && !out) || !flag || !n_active || (mode == TMPC_SENS_VJP && !ybar) ||
+        (data && (!Hbar || !Fbar)))
         return refuse(TMPC_E_INVALID, "NULL argument");
-    if (B == 0) return TMPC_OK;
+    if (B == 0) {
+        if (data) { std::fill(Hbar, Hbar + static_cast<size_t>(nv) * nv, 0.0); std::fill(Fbar, Fbar + static_cast<size_t>(nv) * np, 0.0); }
+        return TMPC_OK;
+    }
     if (device < 0) return refuse(TMPC_E_DEVICE, "device < 0: the kernel runs on the GPU");
     auto fail = [&](const char *what, hipError_t e) { return refuse(TMPC_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
     if (const hipError_t e = hipSetDevice(device); e != hipSuccess) return fail("hipSetDevice", e);
@@ -505,7 +645,10 @@ int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t 
     Part parts[] = {{P, nullptr, b * np * d, 0}, {Z, nullptr, b * nv * d, 0}, {ybar, nullptr, mode == TMPC_SENS_VJP ? b * ny * d : 0, 0},
                     {status, nullptr, status ? b * 4 : 0, 0}, {nullptr, out, b * nout * d, 0}, {nullptr, flag, b * 4, 0}, {nullptr, n_active, b * 4, 0},
                     {nullptr, active, active ? b * nw * 4 : 0, 0},
-                    {nullptr, nullptr, mode == TMPC_SENS_JACOBIAN ? static_cast<size_t>(blocks) * 2 * nv * np * d : 0, 0}};
+                    {nullptr, nullptr, mode == TMPC_SENS_JACOBIAN ? static_cast<size_t>(blocks) * 2 * nv * np * d : 0, 0},
+                    {nullptr, adj, data ? b * nv * d : 0, 0}, {nullptr, nullptr, data ? b * nv * d : 0, 0},
+                    {nullptr, nullptr, data ? tmpc::sens_wgrad_chunks(B) * nv * (static_cast<size_t>(nv) + np) * d : 0, 0},
+                    {nullptr, Hbar, data ? static_cast<size_t>(nv) * nv * d : 0, 0}, {nullptr, Fbar, data ? static_cast<size_t>(nv) * np * d : 0, 0}};
     size_t total = 0;
     for (Part &p : parts) { p.off = total; total += (p.bytes + 255) / 256 * 256; }
     if (hipMalloc(reinterpret_cast<void **>(&own.batch), total) != hipSuccess) {
@@ -529,12 +672,40 @@ int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t 
     a.out = reinterpret_cast<double *>(at(4)); a.flag = reinterpret_cast<int32_t *>(at(5)); a.n_active = reinterpret_cast<int32_t *>(at(6));
     a.active = reinterpret_cast<uint32_t *>(at(7)); a.nwords = static_cast<int>(nw);
     a.ws = reinterpret_cast<double *>(at(8));
+    a.adj = reinterpret_cast<double *>(at(9)); a.zrec = reinterpret_cast<double *>(at(10));
     if (const hipError_t e = tmpc::launch_sens(a, blocks, nullptr); e != hipSuccess) return fail("launch", e);
+    if (data) {
+        tmpc::SensWgradArgs g{};
+        g.nv = nv; g.np = np; g.B = B; g.adj = a.adj; g.zrec = a.zrec; g.np0 = np; g.P0 = a.P0; g.P1 = nullptr; g.flag = a.flag;
+        g.variant = nullptr; g.my_variant = 0; g.nvariants = 1;
+        g.part = reinterpret_cast<double *>(at(11)); g.Hbar = reinterpret_cast<double *>(at(12)); g.Fbar = reinterpret_cast<double *>(at(13));
+        if (const hipError_t e = tmpc::launch_sens_wgrad(g, wgrad_blocks(B, n_cu, nv, np), nullptr); e != hipSuccess) return fail("launch", e);
+    }
     if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess) return fail("hipDeviceSynchronize", e);
     for (const Part &p : parts)
         if (p.host_out && p.bytes)
             if (const hipError_t e = hipMemcpy(p.host_out, own.batch + p.off, p.bytes, hipMemcpyDeviceToHost); e != hipSuccess) return fail("copy-out", e);
     return TMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tmpc_qp_sensitivity(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
+                        const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t B, const double *P, const double *Z,
+                        const int32_t *status, double act_tol, int mode, const double *ybar, double *out, int32_t *flag, int32_t *n_active,
+                        uint32_t *active) {
+    return qp_sens("tmpc_qp_sensitivity", false, device, nv, nc, np, ny, H, F, G, g0, Ebar, Y, Yp, B, P, Z, status, act_tol, mode, ybar, out, flag, n_active, active,
+                   nullptr, nullptr, nullptr);
+}
+
+int tmpc_qp_sensitivity_data(int device, int32_t nv, int32_t nc, int32_t np, int32_t ny, const double *H, const double *F, const double *G,
+                             const double *g0, const double *Ebar, const double *Y, const double *Yp, int64_t B, const double *P, const double *Z,
+                             const int32_t *status, double act_tol, const double *ybar, double *pbar, double *Hbar, double *Fbar, double *adj,
+                             int32_t *flag, int32_t *n_active) {
+    return qp_sens("tmpc_qp_sensitivity_data", true, device, nv, nc, np, ny, H, F, G, g0, Ebar, Y, Yp, B, P, Z, status, act_tol, TMPC_SENS_VJP, ybar, pbar, flag, n_active,
+                   nullptr, Hbar, Fbar, adj);
 }
 
 }  // extern "C"

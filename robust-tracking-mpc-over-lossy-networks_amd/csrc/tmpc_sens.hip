@@ -131,6 +131,10 @@ __global__ __launch_bounds__(SENS_MAX_THREADS, 4) void sens_kernel(const SensArg
         if (sbad[0]) {
             for (size_t i = tid; i < nout; i += nt) out[i] = nan;
             for (int w = tid; act && w < a.nwords; w += nt) act[w] = 0u;
+            for (int c = tid; c < nv; c += nt) {             // (nothing of this instance enters the sums of sens_wgrad)
+                if (a.adj) a.adj[static_cast<size_t>(b) * nv + c] = 0.0;
+                if (a.zrec) a.zrec[static_cast<size_t>(b) * nv + c] = 0.0;
+            }
             if (tid == 0) { a.flag[b] = TMPC_SENS_SKIPPED; a.n_active[b] = 0; }
             __syncthreads();
             continue;
@@ -344,6 +348,7 @@ __global__ __launch_bounds__(SENS_MAX_THREADS, 4) void sens_kernel(const SensArg
                 for (int j = 0; j < nv; ++j) s += Hr[j] * vv[j];
                 for (int j = 0; j < k; ++j) s -= a.W[static_cast<size_t>(alist[j]) * nv + c] * lam[j];
                 bv[c] = s;
+                if (a.zrec) a.zrec[static_cast<size_t>(b) * nv + c] = zv[c];
             }
             __syncthreads();
             for (int q = tid; q < np; q += nt) {
@@ -352,6 +357,35 @@ __global__ __launch_bounds__(SENS_MAX_THREADS, 4) void sens_kernel(const SensArg
                 for (int c = 0; c < nv; ++c) s -= a.F[static_cast<size_t>(c) * np + q] * bv[c];
                 for (int j = 0; j < k; ++j) s += a.Ebar[static_cast<size_t>(alist[j]) * np + q] * lam[j];
                 out[q] = s;
+            }
+            if (a.adj) {
+                // a_b for the weight gradients: bv after one step of refinement on the constraint rows.  The exact a has G_A a = 0;
+                // bv is the rounded difference of two terms, and what it leaves in G_A bv is taken out through the same factor,
+                // a = bv - W_A' M^-1 (G_A bv).  (With |A| = nv the exact a is zero and bv is rounding alone.)  pbar above used bv and is untouched.
+                if (tid < k) {
+                    const double *Gr = a.G + static_cast<size_t>(alist[tid]) * nv;
+                    double s = 0.0;
+                    for (int c = 0; c < nv; ++c) s += Gr[c] * bv[c];
+                    tv[tid] = s;
+                }
+                __syncthreads();
+                if (tid < k) {
+                    double s = 0.0;
+                    for (int t = 0; t <= tid; ++t) s += Li[tid * ld + t] * tv[t];
+                    av[tid] = s;
+                }
+                __syncthreads();
+                if (tid < k) {
+                    double s = 0.0;
+                    for (int t = tid; t < k; ++t) s += Li[t * ld + tid] * av[t];
+                    mv[tid] = s;
+                }
+                __syncthreads();
+                for (int c = tid; c < nv; c += nt) {
+                    double s = bv[c];
+                    for (int j = 0; j < k; ++j) s -= a.W[static_cast<size_t>(alist[j]) * nv + c] * mv[j];
+                    a.adj[static_cast<size_t>(b) * nv + c] = s;
+                }
             }
         }
         for (int w = tid; act && w < a.nwords; w += nt) {
@@ -362,6 +396,65 @@ __global__ __launch_bounds__(SENS_MAX_THREADS, 4) void sens_kernel(const SensArg
         }
         if (tid == 0) { a.flag[b] = flag; a.n_active[b] = k; }
         __syncthreads();                  // (LDS and the workspace slice go to the next instance)
+    }
+}
+
+// The batch reduction of the weight gradients, first kernel (tmpc_sens.hpp: SensWgradArgs): C = A' Z with A = adj [B][nv] and
+// Z = [zrec | p] [B][nv + np], the inner dimension the batch.  A wave per 16 x 16 tile of C and chunk of SENS_WG_CHUNK instances, the
+// operand layout of sens_gemm_mfma: lane l holds adj[b0 + 4 s + l / 16][i0 + l % 16] and Z[b0 + 4 s + l / 16][j0 + l % 16], so the sixteen
+// lanes of a quarter read sixteen consecutive doubles of one row.  Rows past nv, columns past nv + np, instances past B, of another
+// variant or SKIPPED are zeros in the loads; nothing outside C is stored.  One partial tile per (chunk, tile) in `part`: no atomics.
+__global__ __launch_bounds__(64) void sens_wgrad_partial_kernel(const SensWgradArgs a) {
+    const int nv = a.nv, np = a.np, N = nv + np, lane = threadIdx.x & 63;
+    const int tj = (N + 15) / 16, ntile = ((nv + 15) / 16) * tj;
+    const int64_t nwork = static_cast<int64_t>((a.B + SENS_WG_CHUNK - 1) / SENS_WG_CHUNK) * ntile;
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int64_t chunk = w / ntile, b0 = chunk * SENS_WG_CHUNK;
+        const int t = static_cast<int>(w - chunk * ntile);
+        const int i0 = (t / tj) * 16, j0 = (t - (t / tj) * tj) * 16;
+        const int ar = i0 + (lane & 15), bc = j0 + (lane & 15), kk = lane >> 4;
+        const int steps = static_cast<int>(a.B - b0 < SENS_WG_CHUNK ? a.B - b0 : SENS_WG_CHUNK);      // (uniform)
+        sens_v4d acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+        for (int s0 = 0; s0 < steps; s0 += 4) {
+            const int64_t b = b0 + s0 + kk;
+            bool live = s0 + kk < steps;
+            if (live) {
+                const int var = a.variant ? a.variant[b] : 0;
+                live = (var >= a.nvariants ? a.my_variant == 0 : var == a.my_variant) && !(a.flag[b] & TMPC_SENS_SKIPPED);
+            }
+            double av = 0.0, zv = 0.0;
+            if (live && ar < nv) av = a.adj[b * nv + ar];
+            if (live && bc < N) {
+                const int q = bc - nv;
+                zv = q < 0 ? a.zrec[b * nv + bc] : q < a.np0 ? a.P0[b * a.np0 + q] : a.P1[b * (np - a.np0) + (q - a.np0)];
+            }
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, zv, acc, 0, 0, 0);
+        }
+        double *part = a.part + static_cast<size_t>(chunk) * nv * N;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int row = i0 + (lane >> 4) + 4 * reg, col = j0 + (lane & 15);
+            if (row < nv && col < N) part[static_cast<size_t>(row) * N + col] = acc[reg];
+        }
+    }
+}
+
+// Second kernel: a thread per entry of C adds its partials in chunk order.  Hbar(i, j) takes the sums of C(i, j) and C(j, i), whose
+// sum is the same number in either order: Hbar is symmetric to the bit.
+__global__ __launch_bounds__(SENS_MAX_THREADS) void sens_wgrad_sum_kernel(const SensWgradArgs a) {
+    const int nv = a.nv, np = a.np, N = nv + np;
+    const size_t nchunk = static_cast<size_t>((a.B + SENS_WG_CHUNK - 1) / SENS_WG_CHUNK), tile = static_cast<size_t>(nv) * N;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < nv * N; idx += gridDim.x * blockDim.x) {
+        const int i = idx / N, j = idx - i * N;
+        double s = 0.0, st = 0.0;
+        for (size_t c = 0; c < nchunk; ++c) s += a.part[c * tile + idx];
+        if (j < nv) {
+            for (size_t c = 0; c < nchunk; ++c) st += a.part[c * tile + static_cast<size_t>(j) * N + i];
+            a.Hbar[i * nv + j] = -0.5 * (s + st);
+        } else {
+            a.Fbar[i * np + (j - nv)] = -s;
+        }
     }
 }
 
@@ -379,6 +472,15 @@ hipError_t launch_sens(const SensArgs &a, unsigned blocks, hipStream_t stream) {
         blocks < 1 || !a.out || !a.flag || !a.n_active || (a.mode == SENS_MODE_JACOBIAN && !a.ws) || (a.mode == SENS_MODE_VJP && !a.ybar))
         return hipErrorInvalidValue;
     return launch_grid(sens_kernel, blocks, static_cast<unsigned>(sens_threads(a.nv)), sens_lds_bytes(a.nv, a.np), stream, a);
+}
+
+hipError_t launch_sens_wgrad(const SensWgradArgs &a, unsigned blocks, hipStream_t stream) {
+    if (a.nv < 1 || a.nv > SENS_MAX_NV || a.np < 1 || a.np > SENS_MAX_NP || a.np0 < 0 || a.np0 > a.np || a.B < 1 || blocks < 1 || !a.adj || !a.zrec || !a.P0 ||
+        (a.np0 < a.np && !a.P1) || !a.flag || !a.part || !a.Hbar || !a.Fbar)
+        return hipErrorInvalidValue;
+    if (const hipError_t e = launch_grid(sens_wgrad_partial_kernel, blocks, 64u, 0, stream, a); e != hipSuccess) return e;
+    const unsigned entries = static_cast<unsigned>(a.nv * (a.nv + a.np));
+    return launch_grid(sens_wgrad_sum_kernel, (entries + SENS_MAX_THREADS - 1) / SENS_MAX_THREADS, static_cast<unsigned>(SENS_MAX_THREADS), 0, stream, a);
 }
 
 }  // namespace tmpc

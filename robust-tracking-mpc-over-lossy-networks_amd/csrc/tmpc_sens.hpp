@@ -56,7 +56,31 @@ struct SensArgs {
     uint32_t *active;        // [B][nwords] or NULL
     int nwords;
     double *ws;              // [blocks][2 nv np]  right-hand-side blocks of the Jacobian (NULL for the VJP)
+    // ---- VJP mode, optional (NULL: not written): what the gradient with respect to H and F is made of (sens_wgrad below)
+    double *adj = nullptr;   // [B][nv]  a_b = H^-1 v - W_A' q, the solution of [H G_A'; G_A 0] [a; q] = [v; 0], v = Y' ybar_b; zeros where SKIPPED
+    double *zrec = nullptr;  // [B][nv]  the z_b the kernel worked on (rebuilt through Rec for a handle); zeros where SKIPPED
 };
+
+// The reduction over the batch behind the gradients with respect to H and F:  C [nv][nv + np] = sum_b a_b (x) [z_b | p_b]  over the
+// instances of `my_variant` that are not SKIPPED, then  Hbar = -1/2 (C_H + C_H'),  Fbar = -C_F.  B is cut into chunks of
+// SENS_WG_CHUNK instances -- a constant, so that the order of the sums depends on nothing but B: a wave per 16 x 16 tile and chunk
+// writes its partial tile to `part` (v_mfma_f64_16x16x4_f64, four instances a step), a second kernel adds the partials in chunk order.
+constexpr int SENS_WG_CHUNK = 256;
+struct SensWgradArgs {
+    int nv, np;
+    int64_t B;
+    const double *adj, *zrec;        // [B][nv] as sens_kernel wrote them
+    int np0;                         // p as in SensArgs
+    const double *P0, *P1;
+    const int32_t *flag;             // [B] as sens_kernel wrote it
+    const uint8_t *variant;          // or NULL
+    int my_variant, nvariants;
+    double *part;                    // [ceil(B / SENS_WG_CHUNK)][nv][nv + np]
+    double *Hbar, *Fbar;             // [nv][nv], [nv][np]
+};
+inline size_t sens_wgrad_chunks(int64_t B) { return static_cast<size_t>((B + SENS_WG_CHUNK - 1) / SENS_WG_CHUNK); }
+// `blocks`: workgroups of the first kernel (one wave each; they take the tile-chunk pairs round robin, the result does not depend on it)
+hipError_t launch_sens_wgrad(const SensWgradArgs &a, unsigned blocks, hipStream_t stream);
 
 // LDS of a workgroup in bytes, and its size in threads (one wave up to nv = 32, four beyond)
 size_t sens_lds_bytes(int nv, int np);
