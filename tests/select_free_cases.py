@@ -8,15 +8,7 @@ import subprocess
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WAVESIM = os.path.join(ROOT, "tests", "wavesim")
-CSRC = os.path.join(ROOT, "robust-tracking-mpc-over-lossy-networks_amd", "csrc")
-CXX = "/opt/rocm/lib/llvm/bin/clang++"
 L = 64
-FLAGS = {"plain": ["-O2"],
-         "asan": ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
-         "msan": ["-O1", "-fsanitize=memory", "-fsanitize-memory-track-origins"]}
-SAN_ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
-           "MSAN_OPTIONS": "halt_on_error=1"}
 KEYS = ("frows", "dinv", "x", "x2", "ok")
 
 
@@ -91,27 +83,6 @@ def infinity_problems(n, seed=2):
         b1[w, 16 * w + l] = np.inf
         b2[2 + w, 16 * (w + 1) + l] = -np.inf if w else np.inf
     return rows, b1, b2
-
-
-def toolchain_has(kind, out_dir):
-    """whether the host compiler builds and links a trivial program with this kind's flags (the sanitizer runtimes are optional parts
-    of a toolchain) -- asked BEFORE the test program is built, so that a failure of the real build is a failure"""
-    src = os.path.join(out_dir, f"probe_{kind}.cpp")
-    with open(src, "w") as f:
-        f.write("int main() { return 0; }\n")
-    try:
-        return subprocess.run([CXX, "-std=c++20", *FLAGS[kind], src, "-o", os.path.join(out_dir, f"probe_{kind}")],
-                              capture_output=True, text=True).returncode == 0
-    except OSError:
-        return False
-
-
-def build(kind, out_dir):
-    exe = os.path.join(out_dir, f"selectfree_{kind}")
-    cmd = [CXX, "-std=c++20", "-g", "-DTMPC_HOST_SIM", "-I", WAVESIM, "-I", CSRC, "-Wno-unused-function", "-Wno-unknown-attributes",
-           "-Wno-psabi", *FLAGS[kind], os.path.join(WAVESIM, "selectfree_main.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return exe
 
 
 def run(exe, n, rows, b1, b2, work_dir, tag, env=None):

@@ -314,22 +314,12 @@ def test_refusals_of_the_handle_free_entry(hip_lib):
 # ------------------------------------------------------------------ 5: the kernel's source on the host execution model
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """Needs the host clang++ of tests/wavesim/Makefile with its x86-64 sanitizer runtimes: where a trivial program does not build with
-    them the tests skip; a driver that does not build where the toolchain is sound FAILS them.  Stand-alone programs: nothing is loaded
-    into Python under a sanitizer."""
-    import subprocess
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "wavesim"))
+    import hostsim
     import law_case
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([law_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{law_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    return law_case, law_case.build_all()
+    return law_case, hostsim.binaries_or_skip(tmp_path_factory, "lawsim")
 
 
 @pytest.mark.parametrize("build", ["lawsim_asan", "lawsim_msan"])
@@ -338,7 +328,7 @@ def test_kernel_source_on_the_host_model(binaries, build, shape):
     """csrc/tmpc_law.hip compiled for the CPU under ASan + UBSan and under MSan, outputs uninitialised, exact-size blocks: the clipped family
     with B in {1, 65} (one wave and four waves taking turns), hints valid, absent and out of range, max_tries 0, 1 and 2 -- region, tries and
     the hit counters equal the twin's, y the closed form."""
-    from test_plant_models import CLEAN_MARKERS, SAN_ENV
+    import hostsim
     law_case, bins = binaries
     nv, nc, npar = shape
     for B in (1, 65):
@@ -349,9 +339,8 @@ def test_kernel_source_on_the_host_model(binaries, build, shape):
         order = np.random.default_rng(B).permutation(9)
         hint = np.array([(-1, 2, 9, 0)[b % 4] for b in range(B)], np.int32)
         for mt, hn in ((0, None), (0, hint), (1, hint), (2, None)):
-            out = law_case.run(bins[build], table, c["P"], hint=hn, order=order, max_tries=mt, env=SAN_ENV)
-            for mk in CLEAN_MARKERS:
-                assert mk not in out["stderr"], out["stderr"][-4000:]
+            out = law_case.run(bins[build], table, c["P"], hint=hn, order=order, max_tries=mt, env=hostsim.SAN_ENV)
+            hostsim.assert_clean(out["stderr"])
             region, tries, y = E.locate(table, c["P"], hint=hn, order=order, max_tries=mt)
             assert np.array_equal(out["region"], region) and np.array_equal(out["tries"], tries), (shape, B, mt)
             hit = region >= 0

@@ -19,9 +19,6 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "wav
 ATOL_U = 1e-8          # tests/test_hip_parity.py
 S = np.load(os.path.join(common.GOLDEN, "cartpole_N10_states.npy"))
 CONTINUATION_STATE = 587          # tests/test_residual_scale_gpu.py: the fixture state whose first hand-over is not certified
-SAN_ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
-           "MSAN_OPTIONS": "halt_on_error=1"}
-CLEAN_MARKERS = ("ERROR: AddressSanitizer", "runtime error:", "WARNING: MemorySanitizer", "ERROR: LeakSanitizer")
 
 
 def _cases():
@@ -52,11 +49,12 @@ def test_layout_the_handle_reports(hip_lib, monkeypatch):
     assert factoring(10, extended=True) == ([(92, 412, 5), (102, 854, 4)], [504, 956])
 
 
-def test_packed_and_unpacked_layouts_on_the_host_model_under_memory_sanitizer(oracle_lib, monkeypatch):
+def test_packed_and_unpacked_layouts_on_the_host_model_under_memory_sanitizer(oracle_lib, monkeypatch, tmp_path_factory):
     """The stand-alone MemorySanitizer build of the kernel source (tests/wavesim/Makefile: wavesim_msan; registers, LDS and outputs start
     out poisoned), both layouts, the cases in four processes each."""
+    import hostsim
     import run_case
-    binary = run_case.build_all()["wavesim_msan"]
+    binary = hostsim.binaries_or_skip(tmp_path_factory, "wavesim", ["msan"], extra=run_case.EXTRA)["wavesim_msan"]
     mpc, _ = common.make_mpc("cartpole", 10, True, create=False)
     d = mpc._problem_dict()
     X, R = _cases()
@@ -74,10 +72,9 @@ def test_packed_and_unpacked_layouts_on_the_host_model_under_memory_sanitizer(or
             _native.destroy(h)
         # (run_case.run lays its own host-only handle out under the same environment)
         with ThreadPoolExecutor(len(parts)) as ex:
-            outs = list(ex.map(lambda ii: run_case.run(binary, d, X[ii], R[ii], env=SAN_ENV), parts))
+            outs = list(ex.map(lambda ii: run_case.run(binary, d, X[ii], R[ii], env=hostsim.SAN_ENV), parts))
         for ii, o in zip(parts, outs):
-            for m in CLEAN_MARKERS:
-                assert m not in o["stderr"], (packed, o["stderr"][-4000:])
+            hostsim.assert_clean(o["stderr"])
             assert np.array_equal(o["status"], ref["status"][ii]), (packed, o["status"], ref["status"][ii])
             good = ok[ii]
             err = np.max(np.abs(o["u_nom"][good] - ref["u_nom"][ii][good]))

@@ -399,29 +399,18 @@ def test_a_loop_puts_the_handles_hops_back(hip_lib, handles):
 # ------------------------------------------------------------------ the kernels' source on the host execution model
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """As tests/test_explicit_law.py: needs the host clang++ of tests/wavesim with its x86-64 sanitizer runtimes; where a trivial program does
-    not build with them the tests skip, a driver that does not build where the toolchain is sound FAILS them.  Stand-alone programs: nothing
-    is loaded into Python under a sanitizer."""
-    import subprocess
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "wavesim"))
+    import hostsim
     import law_hop_case
     import law_loop_hop_case
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([law_hop_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{law_hop_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    return law_hop_case, law_loop_hop_case, {**law_hop_case.build_all(), **law_loop_hop_case.build_all()}
+    return law_hop_case, law_loop_hop_case, {**hostsim.binaries_or_skip(tmp_path_factory, "lawhop"), **hostsim.binaries_or_skip(tmp_path_factory, "lawloophop")}
 
 
 def _clean(out):
-    from test_plant_models import CLEAN_MARKERS
-    for mk in CLEAN_MARKERS:
-        assert mk not in out["stderr"], out["stderr"][-4000:]
+    import hostsim
+    hostsim.assert_clean(out["stderr"])
 
 
 @pytest.mark.parametrize("build", ["lawhop_asan", "lawhop_msan"])
@@ -430,7 +419,7 @@ def test_kernel_source_with_hops_on_the_host_model(binaries, build, shape):
     """csrc/tmpc_law.hip compiled for the CPU under ASan + UBSan and under MSan: the clipped family with B in {1, 65}, the table the paths
     from a common start (tests/law_hop_cases.py: hop_table) and a refused set, hints valid, absent and out of range: region, tries, the
     hit counters and the chains' six counters equal the twin's, y the closed form."""
-    from test_plant_models import SAN_ENV
+    import hostsim
     law_hop_case, _, bins = binaries
     nv, nc, npar = shape
     for B in (1, 65):
@@ -443,7 +432,7 @@ def test_kernel_source_with_hops_on_the_host_model(binaries, build, shape):
         order = np.random.default_rng(B).permutation(R)
         hint = np.array([(start, -1, R, R - 1)[b % 4] for b in range(B)], np.int32)
         for mh, mt, hn in ((200, 0, hint), (1, 0, hint), (200, 2, hint), (3, 0, None), (0, 0, hint)):
-            out = law_hop_case.run(bins[build], table, c["P"], hint=hn, order=order, max_tries=mt, max_hops=mh, nc=nc, env=SAN_ENV)
+            out = law_hop_case.run(bins[build], table, c["P"], hint=hn, order=order, max_tries=mt, max_hops=mh, nc=nc, env=hostsim.SAN_ENV)
             _clean(out)
             st = np.zeros(6, np.int64)
             region, tries, y = E.locate(table, c["P"], hint=hn, order=order, max_tries=mt, max_hops=mh, nc=nc, stats=st)
@@ -470,7 +459,7 @@ def _fabricated(nrow=70, npar=3, ny=2):
 
 @pytest.mark.parametrize("build", ["lawhop_asan", "lawhop_msan"])
 def test_two_cycle_and_parameter_row_on_the_host_model(binaries, build):
-    from test_plant_models import SAN_ENV
+    import hostsim
     law_hop_case, _, bins = binaries
     table = _fabricated()
     for B in (1, 65):
@@ -478,7 +467,7 @@ def test_two_cycle_and_parameter_row_on_the_host_model(binaries, build):
         hint = np.array([(0, 2, 1, 4, -1)[b % 5] for b in range(B)], np.int32)
         for order in (np.array([4, 0, 1, 2, 3]), np.array([1, 3])):
             for mh, mt in ((8, 0), (8, 2), (1, 0)):
-                out = law_hop_case.run(bins[build], table, P, hint=hint, order=order, max_tries=mt, max_hops=mh, nc=66, env=SAN_ENV)
+                out = law_hop_case.run(bins[build], table, P, hint=hint, order=order, max_tries=mt, max_hops=mh, nc=66, env=hostsim.SAN_ENV)
                 _clean(out)
                 st = np.zeros(6, np.int64)
                 region, tries, y = E.locate(table, P, hint=hint, order=order, max_tries=mt, max_hops=mh, nc=66, stats=st)
@@ -504,7 +493,7 @@ def test_fused_kernel_source_with_hops_on_the_host_model(binaries, sim_tables, b
     """csrc/tmpc_kernels.hip with FUSED = 3 compiled for the CPU under ASan + UBSan and under MSan (bench shape, B in {1, 9}, T = 3), the
     "three" table of tests/test_law_loop.py with max_hops = 4: region, tries, hits, the per-region counters, the six counters and the miss
     count equal the host twin's (montecarlo.LawPackets(max_hops=4) on the same table, the oracle behind it)."""
-    from test_plant_models import SAN_ENV
+    import hostsim
     _, law_loop_hop_case, bins = binaries
     mpc, w, orc, shape, tables = sim_tables
     table = tables["three"]
@@ -518,7 +507,7 @@ def test_fused_kernel_source_with_hops_on_the_host_model(binaries, sim_tables, b
             host = montecarlo.run_remote_tube_mpc(twin, w["A"], w["B"], K, Kp, N, mpc._Z, sc["p_loss"], sc["ref"], sc["th_u"], sc["ga_u"], sc["w"])
             res = twin.result()
             out = law_loop_hop_case.run(bins[build], mpc._problem_dict(), K, Kp, mpc._Z, sc["p_loss"], sc["ref"], sc["th_u"], sc["ga_u"], sc["w"], table, shape,
-                                        max_tries=max_tries, miss_capacity=B * T, warm=(B == 9), env=SAN_ENV, max_hops=4, nc=nc)
+                                        max_tries=max_tries, miss_capacity=B * T, warm=(B == 9), env=hostsim.SAN_ENV, max_hops=4, nc=nc)
             _clean(out)
             assert np.array_equal(out["region"], res["law_region"]) and np.array_equal(out["hits"], res["law_hits"]), (B, max_tries)
             assert np.array_equal(out["tries"], res["law_tries"]), (B, max_tries, out["tries"], res["law_tries"])

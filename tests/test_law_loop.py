@@ -181,23 +181,13 @@ def test_fused_law_kernels_keep_the_register_budget(hip_lib):
 # ------------------------------------------------------------------ the fused kernel's source on the host execution model
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """As tests/test_explicit_law.py: needs the host clang++ of tests/wavesim with its x86-64 sanitizer runtimes; where a trivial program does
-    not build with them the tests skip, a driver that does not build where the toolchain is sound FAILS them.  Stand-alone programs: nothing
-    is loaded into Python under a sanitizer."""
-    import subprocess
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests", "wavesim"))
+    import hostsim
     import law_loop_case
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([law_loop_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{law_loop_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    return law_loop_case, law_loop_case.build_all()
+    return law_loop_case, hostsim.binaries_or_skip(tmp_path_factory, "lawloop")
 
 
 @pytest.fixture(scope="module")
@@ -232,7 +222,7 @@ def test_fused_kernel_source_on_the_host_model(binaries, sim_tables, build, whic
     """csrc/tmpc_kernels.hip with FUSED = 3 compiled for the CPU under ASan + UBSan and under MSan (bench shape, B in {1, 9}, T = 3): region,
     tries, hits, the per-region counters and the miss log equal the host twin's (montecarlo.LawPackets on the same tables, the oracle behind
     it); the logged states, which two solvers produced, to TOL_U0."""
-    from test_plant_models import CLEAN_MARKERS, SAN_ENV
+    import hostsim
     law_loop_case, bins = binaries
     mpc, w, orc, shape, tables = sim_tables
     table = tables[which]
@@ -245,9 +235,8 @@ def test_fused_kernel_source_on_the_host_model(binaries, sim_tables, build, whic
             host = montecarlo.run_remote_tube_mpc(twin, w["A"], w["B"], K, Kp, N, mpc._Z, sc["p_loss"], sc["ref"], sc["th_u"], sc["ga_u"], sc["w"])
             res = twin.result()
             out = law_loop_case.run(bins[build], mpc._problem_dict(), K, Kp, mpc._Z, sc["p_loss"], sc["ref"], sc["th_u"], sc["ga_u"], sc["w"], table, shape,
-                                    max_tries=max_tries, miss_capacity=B * T - 1, warm=(B == 9), env=SAN_ENV)
-            for mk in CLEAN_MARKERS:
-                assert mk not in out["stderr"], out["stderr"][-4000:]
+                                    max_tries=max_tries, miss_capacity=B * T - 1, warm=(B == 9), env=hostsim.SAN_ENV)
+            hostsim.assert_clean(out["stderr"])
             assert np.array_equal(out["region"], res["law_region"]) and np.array_equal(out["hits"], res["law_hits"]), (which, B, max_tries)
             assert np.array_equal(out["tries"], res["law_tries"]), (which, B, max_tries, out["tries"], res["law_tries"])
             want = np.array([twin.region_hits[0].get(r, 0) for r in range(len(table))], np.uint64)

@@ -1,5 +1,5 @@
 """wv::gdg_blocks (csrc/tmpc_wave.hpp) on the host execution model, no GPU: tests/wavesim/mfmablocks_main.cpp as a stand-alone program under
-AddressSanitizer + UndefinedBehaviorSanitizer (plain where the host toolchain lacks their runtime), against numpy in float64 -- the shapes of
+AddressSanitizer + UndefinedBehaviorSanitizer (skipped where the host toolchain lacks their runtime), against numpy in float64 -- the shapes of
 tests/test_mfma_blocks_gpu.py and NV = 22 (21 blocks, six instructions per k-step, two of them with row NV), which no kernel shape takes yet."""
 import os
 import subprocess
@@ -9,22 +9,15 @@ import pytest
 
 import test_mfma_blocks_gpu as dev
 
+import hostsim  # noqa: E402  (tests/wavesim: test_mfma_blocks_gpu puts it on sys.path)
+
 SHAPES = dev.SHAPES + [(22, 2), (22, 5)]
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-SAN_ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1"}
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    d = tmp_path_factory.mktemp("mfmablocks_host")
-    exe = str(d / "mfmablocks_sim")
-    base = [dev.CXX, "-std=c++20", "-O1", "-g", "-DTMPC_HOST_SIM", "-I", dev.WAVESIM, "-I", dev.CSRC, "-Wno-unused-function",
-            "-Wno-unknown-attributes", "-Wno-psabi", os.path.join(dev.WAVESIM, "mfmablocks_main.cpp"), "-o", exe]
-    try:
-        subprocess.run(base + SAN, check=True, capture_output=True, text=True)
-    except (subprocess.CalledProcessError, OSError):
-        subprocess.run(base, check=True, capture_output=True, text=True)
-    return exe, d
+    exe = hostsim.binaries_or_skip(tmp_path_factory, "mfmablocks", ["asan"])["mfmablocks_asan"]
+    return exe, tmp_path_factory.mktemp("mfmablocks_host")
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=[f"nv{nv}-nks{nks}" for nv, nks in SHAPES])
@@ -35,10 +28,9 @@ def test_gdg_on_the_host_model(program, shape):
     P, ldm = G.shape[0], (nv + 1) | 1
     inp, outp = str(d / f"in_{nv}_{nks}.bin"), str(d / f"out_{nv}_{nks}.bin")
     np.concatenate([np.concatenate([G[p].ravel(), D[p], t[p]]) for p in range(P)]).tofile(inp)
-    res = subprocess.run([exe, str(nv), str(nks), str(P), inp, outp], capture_output=True, text=True, timeout=300, env=dict(os.environ, **SAN_ENV))
+    res = subprocess.run([exe, str(nv), str(nks), str(P), inp, outp], capture_output=True, text=True, timeout=300, env=dict(os.environ, **hostsim.SAN_ENV))
     assert res.returncode == 0, res.stderr[-4000:]
-    for m in ("ERROR: AddressSanitizer", "runtime error:", "ERROR: LeakSanitizer"):
-        assert m not in res.stderr, res.stderr[-4000:]
+    hostsim.assert_clean(res.stderr)
     host = np.fromfile(outp, dtype=np.float64).reshape(P, -1)
     mf, gdr = host[:, :nv * ldm].reshape(P, nv, ldm), host[:, nv * ldm:]
     M = np.einsum("pfi,pf,pfj->pij", G, D, G)

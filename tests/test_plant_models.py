@@ -4,7 +4,6 @@ its numpy twins, the host loop on a family of plants with the CPU oracle as the 
 with a plant per trajectory on the host execution model of tests/wavesim under ASan + UBSan and under MSan
 (tests/wavesim/plantsim_main.cpp, through launch_west_rollout itself)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -19,11 +18,9 @@ from oracle.oracle import Oracle
 from test_stepped_loop_api import E_DEVICE, E_INVALID
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "wavesim"))
+import hostsim  # noqa: E402
 import plant_case  # noqa: E402
 
-SAN_ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
-           "MSAN_OPTIONS": "halt_on_error=1"}
-CLEAN_MARKERS = ("ERROR: AddressSanitizer", "runtime error:", "WARNING: MemorySanitizer", "ERROR: LeakSanitizer")
 P = workloads.CARTPOLE_PARAMS
 NOMINAL = np.array([P["M"], P["m"], P["b"], P["I"], P["g"], P["l"], 0.02])
 LINEAR, CARTPOLE = 0, 1            # include/tmpc.h: TMPC_PLANT_*
@@ -258,23 +255,9 @@ def test_w_estimate_twin_with_a_plant_per_trajectory():
 # ------------------------------------------------------------------------------------------------ the kernels' source on the host model
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """Needs the host clang++ of tests/wavesim/Makefile with its x86-64 sanitizer runtimes: where a trivial program does not build with
-    them the tests skip; a driver that does not build where the toolchain is sound FAILS them."""
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([plant_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{plant_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    return plant_case.build_all()
-
-
-def assert_clean(stderr):
-    for m in CLEAN_MARKERS:
-        assert m not in stderr, stderr[-4000:]
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
+    return hostsim.binaries_or_skip(tmp_path_factory, "plantsim")
 
 
 @pytest.mark.parametrize("build", ["plantsim_asan", "plantsim_msan"])
@@ -287,8 +270,8 @@ def test_rollout_with_a_plant_per_trajectory_on_the_host_model(binaries, build):
     x0 = montecarlo.draw_initial_states_philox(n, *montecarlo.W_REFERENCE_X0_BOX, seed=456, first=3)
     tw = montecarlo.estimate_disturbance_box_host(A, B, K, x0, T, par=fam)
     for kw in (dict(x0=x0), dict(box=montecarlo.W_REFERENCE_X0_BOX, n_traj=n, seed=456, first=3)):
-        out = plant_case.run_rollout(binaries[build], A - B @ K, K, np.full(7, np.nan), fam.models, T, env=SAN_ENV, **kw)
-        assert_clean(out["stderr"])
+        out = plant_case.run_rollout(binaries[build], A - B @ K, K, np.full(7, np.nan), fam.models, T, env=hostsim.SAN_ENV, **kw)
+        hostsim.assert_clean(out["stderr"])
         assert np.array_equal(out["x0_used"], x0)
         np.testing.assert_allclose(out["samples"], tw["samples"], atol=1e-12, rtol=0)
         np.testing.assert_allclose(out["min"], tw["min"], atol=1e-12, rtol=0)

@@ -18,6 +18,8 @@ import pytest
 import select_free_cases as sf
 from test_wave_primitives_gpu import Harness
 
+import hostsim  # noqa: E402  (tests/wavesim: test_wave_primitives_gpu puts it on sys.path)
+
 pytestmark = pytest.mark.gpu
 
 SIZES = [8, 11, 12, 16]
@@ -26,8 +28,7 @@ SIZES = [8, 11, 12, 16]
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """the plain host-model binary, built once"""
-    d = str(tmp_path_factory.mktemp("selectfree_gpu"))
-    return d, sf.build("plain", d)
+    return str(tmp_path_factory.mktemp("selectfree_gpu")), hostsim.build("selectfree", ["plain"])["selectfree"]
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,6 @@ this model is tests/test_select_free_gpu.py.
 
 Also here: the opcode classifier of scripts/asm_phase_mix.py on literal lines of compiler output."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -18,31 +17,23 @@ import pytest
 
 import select_free_cases as sf
 
+sys.path.insert(0, os.path.join(sf.ROOT, "tests", "wavesim"))
+import hostsim  # noqa: E402
+
 SIZES = [1, 2, 8, 11, 12, 16]
+KINDS = ("plain", "asan", "msan")
 
 
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("selectfree"))
-    out = {}
-    for kind in sf.FLAGS:
-        if kind != "plain" and not sf.toolchain_has(kind, d):
-            out[kind] = None       # the host toolchain lacks this sanitizer's runtime (a trivial program does not link)
-            continue
-        try:
-            out[kind] = sf.build(kind, d)          # (the toolchain can: a failure now is the test program's)
-        except subprocess.CalledProcessError as e:
-            raise AssertionError(f"selectfree_main.cpp does not build ({kind}):\n{e.stderr[-4000:]}") from e
-    return d, out
+    return str(tmp_path_factory.mktemp("selectfree")), hostsim.binaries_or_skip(tmp_path_factory, "selectfree", KINDS, per_variant=True)
 
 
 def _both(programs, kind, n, rows, b1, b2, tag):
     d, exes = programs
-    if exes[kind] is None:
-        pytest.skip(f"the host toolchain has no {kind} runtime")
-    rc, err, forms = sf.run(exes[kind], n, rows, b1, b2, d, f"{kind}_{n}_{tag}", env=sf.SAN_ENV)
-    for m in ("ERROR: AddressSanitizer", "runtime error:", "WARNING: MemorySanitizer", "ERROR: LeakSanitizer"):
-        assert m not in err, err[-4000:]
+    exe = exes[hostsim.names("selectfree", [kind])[0]]          # (skips where the host toolchain has no runtime of this kind)
+    rc, err, forms = sf.run(exe, n, rows, b1, b2, d, f"{kind}_{n}_{tag}", env=hostsim.SAN_ENV)
+    hostsim.assert_clean(err)
     assert rc in (0, 1), (rc, err[-2000:])
     for key in sf.KEYS:
         assert np.array_equal(sf.bits(forms["masked"][key]), sf.bits(forms["select"][key])), (kind, n, tag, key)
@@ -50,7 +41,7 @@ def _both(programs, kind, n, rows, b1, b2, tag):
     return forms["masked"]
 
 
-@pytest.mark.parametrize("kind", list(sf.FLAGS))
+@pytest.mark.parametrize("kind", list(KINDS))
 @pytest.mark.parametrize("n", SIZES)
 def test_masked_forms_equal_the_select_forms_on_spd_matrices(programs, kind, n):
     rows, b1, b2 = sf.random_problems(n)
@@ -63,7 +54,7 @@ def test_masked_forms_equal_the_select_forms_on_spd_matrices(programs, kind, n):
     assert np.all(o["x"][:, ~live] == 0.0) and np.all(o["dinv"][:, ~live] == 1.0)
 
 
-@pytest.mark.parametrize("kind", list(sf.FLAGS))
+@pytest.mark.parametrize("kind", list(KINDS))
 @pytest.mark.parametrize("n", SIZES)
 def test_a_pivot_that_is_not_positive_gives_the_same_flag_and_outputs(programs, kind, n):
     steps, (rows, b1, b2) = sf.bad_pivot_problems(n)
@@ -72,7 +63,7 @@ def test_a_pivot_that_is_not_positive_gives_the_same_flag_and_outputs(programs, 
     assert np.all(o["dinv"][:, (np.arange(sf.L) % 16) >= n] == 1.0)
 
 
-@pytest.mark.parametrize("kind", list(sf.FLAGS))
+@pytest.mark.parametrize("kind", list(KINDS))
 @pytest.mark.parametrize("n", SIZES)
 def test_an_infinity_in_an_excluded_lane_still_meets_its_zero_multiplier(programs, kind, n):
     rows, b1, b2 = sf.infinity_problems(n)

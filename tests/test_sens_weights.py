@@ -388,7 +388,7 @@ def test_refusals_of_the_handle_free_entry(hip_lib):
 # ------------------------------------------------------------------ 5: the kernels' source on the host execution model
 def run_wgradsim(binary, c, ybar, status=None, env=None):
     """tests/wavesim/wgradsim_main.cpp on a planted case; the instance-independent products as tests/wavesim/sens_case.py forms them."""
-    from plant_case import _run
+    from hostsim import run_files
     H, F, G, g0, Ebar, Y, Yp, P, Z = (np.asarray(c[k], dtype=np.float64) for k in ARGS)
     nv, npar = F.shape
     nc, ny, B = g0.shape[0], Y.shape[0], P.shape[0]
@@ -397,7 +397,7 @@ def run_wgradsim(binary, c, ybar, status=None, env=None):
     st = np.zeros(B, np.int32) if status is None else np.asarray(status, dtype=np.int32)
     payload = [np.array([nv, nc, npar, ny, B], dtype=np.int64), np.array([1e-7]), H, Hinv, F, Hinv @ F, G, G @ Hinv, g0, Ebar, Y, Yp, P, Z, st,
                np.asarray(ybar, dtype=np.float64).reshape(B, ny)]
-    raw, err = _run(binary, "run", payload, env)
+    raw, err = run_files(binary, "run", payload, env)
     sizes = [B * npar, B * nv, nv * nv, nv * npar]
     o = np.frombuffer(raw, dtype=np.float64, count=sum(sizes))
     cut = np.cumsum([0] + sizes)
@@ -409,21 +409,11 @@ def run_wgradsim(binary, c, ybar, status=None, env=None):
 
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """As tests/test_sensitivity.py::binaries: stand-alone programs under the sanitizers; skips where their runtimes are missing."""
-    import subprocess
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "wavesim"))
-    import plant_case
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([plant_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{plant_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    subprocess.run(["make", "-j2", "-s", "-f", "wgrad.mk", "-C", plant_case.HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(plant_case.BIN, t) for t in ("wgradsim_asan", "wgradsim_msan")}
+    import hostsim
+    return hostsim.binaries_or_skip(tmp_path_factory, "wgradsim")
 
 
 @pytest.mark.parametrize("build", ["wgradsim_asan", "wgradsim_msan"])
@@ -431,7 +421,7 @@ def binaries(tmp_path_factory):
 def test_kernel_source_on_the_host_model(binaries, build, nv):
     """csrc/tmpc_sens.hip's reverse mode with adj / zrec set, and the reduction, under ASan + UBSan and under MSan: outputs and workspace
     uninitialised, exact-size blocks, B on both sides of the chunk boundaries; one batch with a SKIPPED instance."""
-    from test_plant_models import CLEAN_MARKERS, SAN_ENV
+    import hostsim
     for B in (1, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 1):
         # (a working set of half the variables at B = 1; two rows in the long batches, whose subject is the reduction: an instance
         # costs the host model three rendezvous of every thread per working row)
@@ -443,9 +433,8 @@ def test_kernel_source_on_the_host_model(binaries, build, nv):
             c["P"][CHUNK, 0] = np.nan       # the one instance of the second chunk
             status = np.zeros(B, np.int32)
             status[3] = 2
-        out = run_wgradsim(binaries[build], c, ybar, status=status, env=SAN_ENV)
-        for m in CLEAN_MARKERS:
-            assert m not in out["stderr"], out["stderr"][-4000:]
+        out = run_wgradsim(binaries[build], c, ybar, status=status, env=hostsim.SAN_ENV)
+        hostsim.assert_clean(out["stderr"])
         twin = S.qp_sensitivity_data(*[c[k] for k in ARGS], ybar, status=status)
         assert np.array_equal(out["flag"], twin["flag"]) and np.array_equal(out["n_active"], twin["n_active"]), (nv, B)
         if status is not None:

@@ -321,22 +321,12 @@ def test_model_getter_on_a_host_only_handle(hip_lib, handles):
 # ------------------------------------------------------------------ 6: the kernel's source on the host execution model
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """Needs the host clang++ of tests/wavesim/Makefile with its x86-64 sanitizer runtimes: where a trivial program does not build with
-    them the tests skip; a driver that does not build where the toolchain is sound FAILS them.  Stand-alone programs: nothing is loaded
-    into Python under a sanitizer."""
-    import subprocess
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "wavesim"))
+    import hostsim
     import sens_case
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([sens_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{sens_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    return sens_case, sens_case.build_all()
+    return sens_case, hostsim.binaries_or_skip(tmp_path_factory, "senssim")
 
 
 @pytest.mark.parametrize("build", ["senssim_asan", "senssim_msan"])
@@ -344,7 +334,7 @@ def binaries(tmp_path_factory):
 def test_kernel_source_on_the_host_model(binaries, build, nv):
     """csrc/tmpc_sens.hip compiled for the CPU under ASan + UBSan and under MSan, outputs and workspace uninitialised, exact-size blocks:
     planted cases in both modes (64 and 256 threads, rows across the chunk boundary at nv = 128), the flags, against the twin."""
-    from test_plant_models import CLEAN_MARKERS, SAN_ENV
+    import hostsim
     sens_case, bins = binaries
     nA, nc = (nv // 2 + 1, 65 if nv < 128 else 600) if nv > 1 else (1, 3)
     cases = [(sr.planted_case(80 + nv, nv, nA, nc, 8, 3), None)]
@@ -359,9 +349,8 @@ def test_kernel_source_on_the_host_model(binaries, build, nv):
         a = [c[k] for k in ("H", "F", "G", "g0", "Ebar", "Y", "Yp", "P", "Z")]
         ybar = np.random.default_rng(1).standard_normal((c["P"].shape[0], c["ny"]))
         for mode in ("jacobian", "vjp"):
-            out = sens_case.run(bins[build], *a, status=status, mode=mode, ybar=ybar, env=SAN_ENV)
-            for m in CLEAN_MARKERS:
-                assert m not in out["stderr"], out["stderr"][-4000:]
+            out = sens_case.run(bins[build], *a, status=status, mode=mode, ybar=ybar, env=hostsim.SAN_ENV)
+            hostsim.assert_clean(out["stderr"])
             twin = S.qp_sensitivity(*a, status=status, mode=mode, ybar=ybar)
             assert np.array_equal(out["flag"], twin["flag"]) and np.array_equal(out["n_active"], twin["n_active"]) and np.array_equal(out["active"], twin["active"])
             ok = twin["flag"] != S.SKIPPED

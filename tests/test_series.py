@@ -6,7 +6,6 @@ and under MSan against the numpy twin."""
 import ctypes as C
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,10 +15,10 @@ import common
 import regulator_problems as rp
 from LinearMPCOverNetworks import _native, montecarlo, workloads
 from LinearMPCOverNetworks.polytope_lite import Polytope
-from test_plant_models import CLEAN_MARKERS, SAN_ENV
 from test_stepped_loop_api import E_DEVICE, E_INVALID
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "wavesim"))
+import hostsim  # noqa: E402
 import series_case  # noqa: E402
 
 FLAGS = ("lost_up", "lost_down", "adopted", "tube", "not_optimal", "overrun")
@@ -308,18 +307,9 @@ def test_setter_and_getters_on_host_only_handles(host_handle):
 # ------------------------------------------------------------------------------------------------ 4: the kernel's source on the host model
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """Needs the host clang++ of tests/wavesim/Makefile with its x86-64 sanitizer runtimes: where a trivial program does not build with
-    them the tests skip; a driver that does not build where the toolchain is sound FAILS them."""
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([series_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{series_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    return series_case.build_all()
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
+    return hostsim.binaries_or_skip(tmp_path_factory, "seriessim")
 
 
 def _assert_equals_twin(out, e, word, group, q, G):
@@ -341,8 +331,7 @@ def test_reduction_kernel_on_the_host_model(binaries, build):
     e, word, group, G = series_case.edge_record()
     q16 = series_case.QUANTILES + tuple(np.linspace(0.01, 0.99, 11))
     for grp, ng, q in ((group, G, q16), (None, 1, ()), (group, G, series_case.QUANTILES[:1])):
-        out = series_case.run_stats(binaries[build], e, word, grp, q, ng, env=SAN_ENV)
-        for m in CLEAN_MARKERS:
-            assert m not in out["stderr"], out["stderr"][-4000:]
+        out = series_case.run_stats(binaries[build], e, word, grp, q, ng, env=hostsim.SAN_ENV)
+        hostsim.assert_clean(out["stderr"])
         ref = _assert_equals_twin(out, e, word, grp, q, ng)
     assert ref["n_alive"][0].tolist() == list(series_case.SIZES) + [0] and np.isnan(ref["e_q"][:, [0, G - 1]]).all()

@@ -4,7 +4,6 @@ execution model of tests/wavesim under ASan + UBSan and under MSan (tests/wavesi
 against the numpy twin montecarlo.PlantFamily.__call__."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,10 +12,11 @@ import pytest
 import common
 from LinearMPCOverNetworks import _native, montecarlo, workloads
 from LinearMPCOverNetworks.RegulatorMPC import RegulatorMPC
-from test_plant_models import CLEAN_MARKERS, NOMINAL, SAN_ENV
+from test_plant_models import NOMINAL
 from test_stepped_loop_api import E_DEVICE, E_INVALID
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "wavesim"))
+import hostsim  # noqa: E402
 import plantstep_case  # noqa: E402
 
 LINEAR, CARTPOLE = 0, 1            # include/tmpc.h: TMPC_PLANT_*
@@ -182,23 +182,9 @@ def test_plant_step_refusals_come_before_the_device(hip_lib):
 # ------------------------------------------------------------------------------------------------ the kernels' source on the host model
 @pytest.fixture(scope="module")
 def binaries(tmp_path_factory):
-    """Needs the host clang++ of tests/wavesim/Makefile with its x86-64 sanitizer runtimes: where a trivial program does not build with
-    them the tests skip; a driver that does not build where the toolchain is sound FAILS them."""
-    d = tmp_path_factory.mktemp("probe")
-    (d / "t.cpp").write_text("int main() { return 0; }\n")
-    for flags in ("-fsanitize=address,undefined", "-fsanitize=memory"):
-        try:
-            ok = subprocess.run([plantstep_case.CXX, flags, str(d / "t.cpp"), "-o", str(d / "t")], capture_output=True).returncode == 0
-        except OSError:
-            ok = False
-        if not ok:
-            pytest.skip(f"{plantstep_case.CXX} {flags}: no such compiler or sanitizer runtime on this host")
-    return plantstep_case.build_all()
-
-
-def assert_clean(stderr):
-    for m in CLEAN_MARKERS:
-        assert m not in stderr, stderr[-4000:]
+    """The host-model programs under the sanitizers (tests/wavesim/hostsim.py: a host without their runtimes skips, a program that does not
+    build fails).  Stand-alone programs: nothing is loaded into Python under a sanitizer."""
+    return hostsim.binaries_or_skip(tmp_path_factory, "plantstep")
 
 
 def cartpole_inputs(nb, seed):
@@ -222,8 +208,8 @@ def test_cartpole_kernel_on_the_host_model(binaries, build, nb):
     _, _, wp = montecarlo.draw_realisations_philox(nb, t + 1, w_bound, seed=seed, first=first)
     w_arr = np.random.default_rng(2).uniform(-1e-2, 1e-2, (nb, 4))
     for kw, w in ((dict(), None), (dict(w=w_arr), w_arr), (dict(philox=(t, seed, first, w_bound)), wp[:, t])):
-        out = plantstep_case.run_step(binaries[build], fam, x, u, hold=hold, env=SAN_ENV, **kw)
-        assert_clean(out["stderr"])
+        out = plantstep_case.run_step(binaries[build], fam, x, u, hold=hold, env=hostsim.SAN_ENV, **kw)
+        hostsim.assert_clean(out["stderr"])
         exp = want if w is None else want + w
         exp[held] = x[held]
         np.testing.assert_allclose(out["x_plus"], exp, atol=CARTPOLE_ATOL, rtol=0)
@@ -234,8 +220,8 @@ def test_cartpole_kernel_on_the_host_model(binaries, build, nb):
     tab = np.random.default_rng(3).uniform(-0.5, 0.5, (2, t + 2, 4))
     ids = np.arange(nb) % 2
     for kw, r in ((dict(ref_t=0.4), np.tile([0.4, 0.0, 0.0, 0.0], (nb, 1))), (dict(ref_tab=tab, ref_id=ids, philox=(t, 0, 0, None)), tab[ids, t])):
-        out = plantstep_case.run_step(binaries[build], fam, x, u, hold=hold, err2_phys=before, env=SAN_ENV, **kw)
-        assert_clean(out["stderr"])
+        out = plantstep_case.run_step(binaries[build], fam, x, u, hold=hold, err2_phys=before, env=hostsim.SAN_ENV, **kw)
+        hostsim.assert_clean(out["stderr"])
         exp = before + ((tr - r[None]) ** 2).sum(axis=(0, 2))
         live = hold == 0
         # every state behind the sum is the twin's within CARTPOLE_ATOL, so the sum of the (y - r)^2 moves by at most 2 atol sum |y - r| (+ atol^2
@@ -262,16 +248,16 @@ def test_linear_kernel_on_the_host_model(binaries, build, nx, nu):
     hold[3] = 1
     for kw, w in ((dict(), None), (dict(w=w_arr), w_arr), (dict(philox=(t, seed, first, w_bound)), wp[:, t])):
         for hd in (None, hold):
-            out = plantstep_case.run_step(binaries[build], fam, x, u, hold=hd, env=SAN_ENV, **kw)
-            assert_clean(out["stderr"])
+            out = plantstep_case.run_step(binaries[build], fam, x, u, hold=hd, env=hostsim.SAN_ENV, **kw)
+            hostsim.assert_clean(out["stderr"])
             exp = fam(x, u) if w is None else fam(x, u) + w
             bound = linear_bound(fam, x, u, w)
             if hd is not None:
                 exp[3], bound[3] = x[3], 0.0
             assert np.all(np.abs(out["x_plus"] - exp) <= bound), float(np.max(np.abs(out["x_plus"] - exp) - bound))
     zero = montecarlo.plant_family("linear", A=np.zeros((nb, nx, nx)), B=np.zeros((nb, nx, nu)))
-    out = plantstep_case.run_step(binaries[build], zero, x, u, philox=(t, seed, first, w_bound), env=SAN_ENV)
-    assert_clean(out["stderr"])
+    out = plantstep_case.run_step(binaries[build], zero, x, u, philox=(t, seed, first, w_bound), env=hostsim.SAN_ENV)
+    hostsim.assert_clean(out["stderr"])
     assert out["x_plus"].tobytes() == np.ascontiguousarray(wp[:, t]).tobytes()
 
 

@@ -3,7 +3,6 @@ reference's Results/estimate_W_for_Cartpole.py on its own scenario, the initial-
 (csrc/tmpc_west.hip) on the host execution model of tests/wavesim under ASan + UBSan and under MSan.  CPU only."""
 import importlib.util
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,32 +13,23 @@ import w_cases
 from LinearMPCOverNetworks import montecarlo, workloads
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "wavesim"))
+import hostsim  # noqa: E402
 import west_case  # noqa: E402
 
-SAN_ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
-           "MSAN_OPTIONS": "halt_on_error=1"}
-CLEAN_MARKERS = ("ERROR: AddressSanitizer", "runtime error:", "WARNING: MemorySanitizer", "ERROR: LeakSanitizer")
+SAN_ENV = hostsim.SAN_ENV
+assert_clean = hostsim.assert_clean
 BOX = montecarlo.W_REFERENCE_X0_BOX
 
 
 @pytest.fixture(scope="module")
-def binaries():
-    """needs a host clang++ with the x86-64 sanitizer runtimes, like tests/test_wavesim.py: a toolchain without them skips"""
-    try:
-        return west_case.build_all()
-    except (subprocess.CalledProcessError, OSError) as e:
-        pytest.skip(f"tests/wavesim/westsim.mk does not build on this host: {e}")
+def binaries(tmp_path_factory):
+    return hostsim.binaries_or_skip(tmp_path_factory, "westsim")
 
 
 @pytest.fixture(scope="module")
 def twin():
     A, B, K = w_cases.scenario()
     return montecarlo.estimate_disturbance_box_host(A, B, K, montecarlo.reference_initial_states(), 400)
-
-
-def assert_clean(stderr):
-    for m in CLEAN_MARKERS:
-        assert m not in stderr, stderr[-4000:]
 
 
 # ---------------------------------------------------------------- initial states

@@ -32,6 +32,8 @@ import common
 import sensitivity_reference as sr
 import test_wave_swap_reduce as host_model
 
+import hostsim  # noqa: E402  (tests/wavesim: test_wave_swap_reduce puts it on sys.path)
+
 pytestmark = pytest.mark.gpu
 
 LD = np.longdouble
@@ -158,10 +160,7 @@ def sums(tmp_path_factory):
     np.concatenate([s.ravel() for s in sets]).astype(np.float64).tofile(inp)
     # built on demand like there, plain (no sanitizer) and without optimisation: 3 s instead of 45, and the same bits -- the order of
     # the additions is in the lane maps (test_swap_reduce_is_deterministic_across_builds)
-    exe = os.path.join(d, "swapsum_plain_O0")
-    subprocess.run([host_model.CXX, "-std=c++20", "-O0", "-DTMPC_HOST_SIM", "-I", host_model.WAVESIM, "-I", host_model.CSRC,
-                    "-Wno-unused-function", "-Wno-unknown-attributes", "-Wno-psabi", os.path.join(host_model.WAVESIM, "swapsum_main.cpp"),
-                    "-o", exe], check=True, capture_output=True, text=True)
+    exe = hostsim.build("swapsum", ["O0"])["swapsum_O0"]
     res = subprocess.run([exe, inp, os.path.join(d, "out.bin")], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-4000:]
     model = host_model._split(np.fromfile(os.path.join(d, "out.bin"), dtype=np.float64), len(sets))

@@ -1,7 +1,7 @@
 """The register wave sums of csrc/tmpc_wave.hpp (wv::swap_reduce_to_lds: v_permlane32_swap / v_permlane16_swap halvings, then one
 round of the transposition tile; wv::wave_sum2) on the host execution model of tests/wavesim/hip_sim.hpp.  CPU only.
 
-What runs here is the project's MODEL of the instructions, not the instructions: under TMPC_HOST_SIM wv::permlane_swap is an emulation
+What runs here is the project's MODEL of the instructions, not the instructions: in a host-model build wv::permlane_swap is an emulation
 written from the manual and the DPP moves are hip_sim.hpp's.  This file checks the routine's lane maps and arithmetic on that model (and
 its memory safety under the sanitizers); that the model and the hardware agree is tests/test_wave_primitives_gpu.py, which runs the same
 cases on the device and compares the totals with this program's bit for bit.
@@ -14,28 +14,16 @@ plain and, where the host toolchain has the runtimes, under ASan + UBSan and MSa
 import math
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WAVESIM = os.path.join(ROOT, "tests", "wavesim")
-CSRC = os.path.join(ROOT, "robust-tracking-mpc-over-lossy-networks_amd", "csrc")
-CXX = "/opt/rocm/lib/llvm/bin/clang++"
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "wavesim"))
+import hostsim  # noqa: E402
+
 MAXC, L = 52, 64
-FLAGS = {"plain": ["-O2"],
-         "asan": ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
-         "msan": ["-O1", "-fsanitize=memory", "-fsanitize-memory-track-origins"]}
-SAN_ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
-           "MSAN_OPTIONS": "halt_on_error=1"}
-
-
-def _build(kind, out_dir):
-    exe = os.path.join(out_dir, f"swapsum_{kind}")
-    cmd = [CXX, "-std=c++20", "-g", "-DTMPC_HOST_SIM", "-I", WAVESIM, "-I", CSRC, "-Wno-unused-function", "-Wno-unknown-attributes",
-           "-Wno-psabi", *FLAGS[kind], os.path.join(WAVESIM, "swapsum_main.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return exe
+KINDS = ("plain", "asan", "msan")
 
 
 def _data_sets():
@@ -51,20 +39,17 @@ def results(tmp_path_factory):
     sets = _data_sets()
     inp = os.path.join(d, "in.bin")
     np.concatenate([s.ravel() for s in sets]).astype(np.float64).tofile(inp)
+    exes = hostsim.binaries_or_skip(tmp_path_factory, "swapsum", KINDS, per_variant=True)
     out = {}
-    for kind in FLAGS:
-        try:
-            exe = _build(kind, str(d))
-        except (subprocess.CalledProcessError, OSError) as e:
-            if kind == "plain":
-                raise
-            out[kind] = e          # the host toolchain lacks this sanitizer's runtime
+    for kind in KINDS:
+        exe = exes.get(hostsim.names("swapsum", [kind])[0])
+        if exe is None:          # the host toolchain lacks this sanitizer's runtime
+            out[kind] = None
             continue
         res = subprocess.run([exe, inp, os.path.join(d, f"out_{kind}.bin")], capture_output=True, text=True, timeout=600,
-                             env=dict(os.environ, **SAN_ENV))
+                             env=dict(os.environ, **hostsim.SAN_ENV))
         assert res.returncode == 0, res.stderr[-4000:]
-        for m in ("ERROR: AddressSanitizer", "runtime error:", "WARNING: MemorySanitizer", "ERROR: LeakSanitizer"):
-            assert m not in res.stderr, res.stderr[-4000:]
+        hostsim.assert_clean(res.stderr)
         out[kind] = np.fromfile(os.path.join(d, f"out_{kind}.bin"), dtype=np.float64)
     return sets, out
 
@@ -97,11 +82,11 @@ def _check(vals, got):
         assert abs(got[0, c] - exact) <= bound, (c, got[0, c], exact, bound)
 
 
-@pytest.mark.parametrize("kind", list(FLAGS))
+@pytest.mark.parametrize("kind", list(KINDS))
 def test_swap_reduce_totals_on_the_host_model(results, kind):
     sets, out = results
-    if isinstance(out[kind], Exception):
-        pytest.skip(f"{kind} build unavailable on this host: {out[kind]}")
+    if out[kind] is None:
+        pytest.skip(f"the host toolchain has no {kind} runtime")
     for vals, (red, s2) in zip(sets, _split(out[kind], len(sets))):
         for (rr, cnt), got in red.items():
             _check(vals[:cnt], got)
@@ -111,6 +96,6 @@ def test_swap_reduce_totals_on_the_host_model(results, kind):
 def test_swap_reduce_is_deterministic_across_builds(results):
     """the order of the additions is fixed by the lane maps, not by the compiler: every build gives the same bits"""
     _, out = results
-    built = [v for v in out.values() if not isinstance(v, Exception)]
+    built = [v for v in out.values() if v is not None]
     for v in built[1:]:
         assert np.array_equal(v, built[0])

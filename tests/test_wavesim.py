@@ -21,28 +21,18 @@ import pytest
 import common
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "wavesim"))
+import hostsim  # noqa: E402
 import run_case  # noqa: E402
 
 S = np.load(os.path.join(common.GOLDEN, "cartpole_N10_states.npy"))
-SAN_ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
-           "MSAN_OPTIONS": "halt_on_error=1"}
-CLEAN_MARKERS = ("ERROR: AddressSanitizer", "runtime error:", "WARNING: MemorySanitizer", "ERROR: LeakSanitizer")
-
-
-def _build_or_skip():
-    """The harness needs a host clang++ with the x86-64 sanitizer runtimes (ASan / UBSan / MSan); a toolchain without them
-    skips these tests instead of failing the suite (the product build does not depend on them)."""
-    import subprocess
-    try:
-        return run_case.build_all()
-    except (subprocess.CalledProcessError, OSError) as e:
-        pytest.skip(f"tests/wavesim does not build on this host: {e}")
+SAN_ENV = hostsim.SAN_ENV
 
 
 @pytest.fixture(scope="module")
-def binaries():
-    # (also built by __graft_entry__.build(); make leaves them alone when they are up to date)
-    return _build_or_skip()
+def binaries(tmp_path_factory):
+    # (also built by __graft_entry__.build(); make leaves them alone when they are up to date.  A host without the sanitizer runtimes
+    # skips; a driver that does not build on a sound toolchain fails)
+    return hostsim.binaries_or_skip(tmp_path_factory, "all", extra=run_case.EXTRA)
 
 
 @pytest.fixture(scope="module")
@@ -52,8 +42,7 @@ def cartpole():
 
 
 def assert_clean(out):
-    for m in CLEAN_MARKERS:
-        assert m not in out["stderr"], out["stderr"][-4000:]
+    hostsim.assert_clean(out["stderr"])
 
 
 def test_all_fixture_instances_through_the_kernel_source(binaries, cartpole, oracle_lib):
@@ -192,8 +181,8 @@ def test_extended_closed_loop_source_under_sanitizers(binaries, oracle_lib):
 
 
 @pytest.fixture(scope="module")
-def block_binaries():
-    return _build_or_skip()
+def block_binaries(binaries):
+    return binaries
 
 
 def test_block_kernel_source_under_sanitizers(block_binaries, cartpole, oracle_lib):

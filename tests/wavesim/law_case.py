@@ -1,16 +1,9 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/lawsim_* (the explicit-law kernel of csrc/tmpc_law.hip on the host execution model; the
+"""TEST INFRASTRUCTURE: drives tests/wavesim/lawsim_* (the explicit-law kernel of csrc/tmpc_law.hip on the host execution model; the
 file format is described in lawsim_main.cpp)."""
-import os
-import subprocess
 
 import numpy as np
 
-from plant_case import BIN, CXX, HERE, _run  # noqa: F401  (CXX: the compiler of law.mk, for the tests' probe)
-
-
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "law.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("lawsim_asan", "lawsim_msan")}
+from hostsim import run_files
 
 
 def pack_table(table, npar, ny, nrow):
@@ -38,7 +31,7 @@ def run(binary, table, P, hint=None, order=None, max_tries=0, env=None):
     payload = [np.array([npar, ny, nrow, R, len(order), B, max_tries, int(hint is not None)], dtype=np.int64), S, K, order, P]
     if hint is not None:
         payload.append(np.ascontiguousarray(np.broadcast_to(np.asarray(hint, dtype=np.int32).reshape(-1), (B,))))
-    raw, err = _run(binary, "run", payload, env)
+    raw, err = run_files(binary, "run", payload, env)
     y = np.frombuffer(raw, dtype=np.float64, count=B * ny).reshape(B, ny).copy()
     off = 8 * B * ny
     region = np.frombuffer(raw, dtype=np.int32, count=B, offset=off).copy()

@@ -1,17 +1,10 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/lawhop_* (the explicit-law kernel of csrc/tmpc_law.hip with the hops of its search on the
+"""TEST INFRASTRUCTURE: drives tests/wavesim/lawhop_* (the explicit-law kernel of csrc/tmpc_law.hip with the hops of its search on the
 host execution model; the file format is described in lawhop_main.cpp)."""
-import os
-import subprocess
 
 import numpy as np
 
 from law_case import pack_table
-from plant_case import BIN, CXX, HERE, _run  # noqa: F401  (CXX: the compiler of lawhop.mk, for the tests' probe)
-
-
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "lawhop.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("lawhop_asan", "lawhop_msan")}
+from hostsim import run_files
 
 
 def keys_of(table):
@@ -35,7 +28,7 @@ def run(binary, table, P, hint=None, order=None, max_tries=0, max_hops=0, nc=Non
     if hint is not None:
         payload.append(np.ascontiguousarray(np.broadcast_to(np.asarray(hint, dtype=np.int32).reshape(-1), (B,))))
     payload += [keys, slot]
-    raw, err = _run(binary, "run", payload, env)
+    raw, err = run_files(binary, "run", payload, env)
     y = np.frombuffer(raw, dtype=np.float64, count=B * ny).reshape(B, ny).copy()
     off = 8 * B * ny
     region = np.frombuffer(raw, dtype=np.int32, count=B, offset=off).copy()

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/lawloop_* (the fused closed loop through the explicit law, closed_loop_law of
+"""TEST INFRASTRUCTURE: drives tests/wavesim/lawloop_* (the fused closed loop through the explicit law, closed_loop_law of
 csrc/tmpc_kernels.hip, on the host execution model; the file formats are described in lawloop_main.cpp and wavesim_main.cpp)."""
 import ctypes as C
 import os
@@ -8,12 +8,6 @@ import tempfile
 import numpy as np
 
 from law_case import pack_table
-from plant_case import BIN, CXX, HERE  # noqa: F401  (CXX: the compiler of lawloop.mk, for the tests' probe)
-
-
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "lawloop.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("lawloop_asan", "lawloop_msan")}
 
 
 def run(binary, d, K, K_anc, Z, p_loss, ref, th_u, ga_u, w, table, shape, order=None, max_tries=0, miss_capacity=0, warm=False, env=None, timeout=3600):

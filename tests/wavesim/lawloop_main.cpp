@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE (not product code): the fused closed loop through the explicit law -- closed_loop_law, csrc/tmpc_kernels.hip with
 // FUSED = 3, the source text the GPU build compiles in csrc/tmpc_fused_law.hip -- on the host execution model of hip_sim.hpp, for the
 // sanitizers.  One workgroup; a wave keeps its trajectory for all T steps.  Device memory is exact-size heap blocks, what the kernel must
-// write itself uninitialised.  Built with -DTMPC_SIM_LAW_LOOP (lawloop.mk), the only binaries that hold this kernel.
+// write itself uninitialised.  Built with -DTMPC_SIM_LAW_LOOP (the lawloop line of the Makefile), the only binaries that hold this kernel.
 //
 //   lawloop <layout file> <loop file> <table file> <output file>
 // layout file, loop file: as wavesim --loop (wavesim_main.cpp), one problem

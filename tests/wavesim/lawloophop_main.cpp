@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE (not product code): the fused closed loop through the explicit law -- closed_loop_law, csrc/tmpc_kernels.hip with
 // FUSED = 3, the source text the GPU build compiles in csrc/tmpc_fused_law.hip -- on the host execution model of hip_sim.hpp, for the
 // sanitizers.  One workgroup; a wave keeps its trajectory for all T steps.  Device memory is exact-size heap blocks, what the kernel must
-// write itself uninitialised.  Built with -DTMPC_SIM_LAW_LOOP (lawloophop.mk).  This driver runs the search with hops (tmpc_law_set_hops):
+// write itself uninitialised.  Built with -DTMPC_SIM_LAW_LOOP (the lawloophop line of the Makefile).  This driver runs the search with hops (tmpc_law_set_hops):
 // the table comes with its keys and their hash, the six counters come back.
 //
 //   lawloophop <layout file> <loop file> <table file> <output file>

@@ -1,35 +1,9 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/plantsim_* (the W estimate's rollout with a plant per trajectory on the host execution
+"""TEST INFRASTRUCTURE: drives tests/wavesim/plantsim_* (the W estimate's rollout with a plant per trajectory on the host execution
 model; the file formats are described in plantsim_main.cpp)."""
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-BIN = os.path.join(HERE, "_build")
-CXX = "/opt/rocm/lib/llvm/bin/clang++"      # the compiler of plantsim.mk (and of Makefile)
-
-
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "plantsim.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("plantsim_asan", "plantsim_msan")}
-
-
-def _run(binary, mode, payload, env):
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in"), os.path.join(d, "out")
-        with open(fin, "wb") as f:
-            for a in payload:
-                f.write(np.ascontiguousarray(a).tobytes())
-        e = dict(os.environ)
-        e.update(env or {})
-        p = subprocess.run([binary, mode, fin, fout], capture_output=True, text=True, env=e)
-        if p.returncode != 0:
-            raise RuntimeError(f"{os.path.basename(binary)} {mode} failed ({p.returncode}):\n{p.stderr[-4000:]}")
-        with open(fout, "rb") as f:
-            raw = f.read()
-    return raw, p.stderr
+from hostsim import run_files
 
 
 def run_rollout(binary, Acl, K, par7, par_traj, T, substeps=10, x0=None, box=None, n_traj=None, seed=0, first=0, env=None):
@@ -44,7 +18,7 @@ def run_rollout(binary, Acl, K, par7, par_traj, T, substeps=10, x0=None, box=Non
     if not draw:
         payload.append(np.asarray(x0, dtype=np.float64).reshape(-1, 4))
     payload.append(np.asarray(par_traj, dtype=np.float64).reshape(n, 7))
-    raw, err = _run(binary, "rollout", payload, env)
+    raw, err = run_files(binary, "rollout", payload, env)
     o = np.frombuffer(raw, dtype=np.float64)
     ns = 4 * (T - 1) * n
     return dict(x0_used=o[:4 * n].reshape(n, 4).copy(), samples=o[4 * n:4 * n + ns].reshape(4, T - 1, n).copy(),

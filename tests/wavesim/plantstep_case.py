@@ -1,18 +1,11 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/plantstep_* (the plant kernels of csrc/tmpc_plant.hip on the host execution model;
+"""TEST INFRASTRUCTURE: drives tests/wavesim/plantstep_* (the plant kernels of csrc/tmpc_plant.hip on the host execution model;
 the file format is described in plantstep_main.cpp)."""
-import os
-import subprocess
 
 import numpy as np
 
-from plant_case import BIN, CXX, HERE, _run  # noqa: F401  (CXX: the compiler of plantstep.mk, for the tests' probe)
+from hostsim import run_files
 
 KIND = {"linear": 0, "cartpole": 1}         # include/tmpc.h: TMPC_PLANT_*
-
-
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "plantstep.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("plantstep_asan", "plantstep_msan")}
 
 
 def run_step(binary, family, x, u, w=None, philox=None, hold=None, err2_phys=None, ref_t=0.0, ref_tab=None, ref_id=None, env=None):
@@ -39,7 +32,7 @@ def run_step(binary, family, x, u, w=None, philox=None, hold=None, err2_phys=Non
         payload += [np.asarray(err2_phys, dtype=np.float64).reshape(nb), np.array([ref_t], dtype=np.float64)]
     if phys == 2:
         payload += [tab, np.asarray(ref_id, dtype=np.int32).reshape(nb)]
-    raw, err = _run(binary, "step", payload, env)
+    raw, err = run_files(binary, "step", payload, env)
     o = np.frombuffer(raw, dtype=np.float64)
     out = dict(x_plus=o[:nb * nx].reshape(nb, nx).copy(), stderr=err)
     if phys:

@@ -8,15 +8,14 @@ import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "_build")
+import hostsim
+
+EXTRA = "-DTMPC_SIM_SHAPES"         # the shape set of the tests' binaries
 
 
-def build_all(extra="-DTMPC_SIM_SHAPES"):
-    """every binary of the Makefile in one parallel make (what __graft_entry__.build() runs as well); up to date -> no-op"""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HERE, "all", f"EXTRA={extra}"])
-    return {t: os.path.join(BUILD, t) for t in ("wavesim", "wavesim_asan", "wavesim_msan", "wavesim_ext_asan", "blocksim", "blocksim_asan", "blocksim_msan",
-                                                 "lpsim_asan", "lpsim_msan")}
+def build_all(extra=EXTRA):
+    """every binary of the Makefile's `all` in one parallel make (what __graft_entry__.build() runs as well); up to date -> no-op"""
+    return hostsim.build("all", extra=extra)
 
 
 def run(binary, d, X, R, variant=None, env=None, timeout=1800, block=False):

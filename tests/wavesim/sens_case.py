@@ -1,16 +1,9 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/senssim_* (the sensitivity kernel of csrc/tmpc_sens.hip on the host execution model;
+"""TEST INFRASTRUCTURE: drives tests/wavesim/senssim_* (the sensitivity kernel of csrc/tmpc_sens.hip on the host execution model;
 the file format is described in senssim_main.cpp)."""
-import os
-import subprocess
 
 import numpy as np
 
-from plant_case import BIN, CXX, HERE, _run  # noqa: F401  (CXX: the compiler of sens.mk, for the tests' probe)
-
-
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "sens.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("senssim_asan", "senssim_msan")}
+from hostsim import run_files
 
 
 def run(binary, H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol=1e-7, mode="jacobian", ybar=None, env=None):
@@ -26,7 +19,7 @@ def run(binary, H, F, G, g0, Ebar, Y, Yp, P, Z, status=None, act_tol=1e-7, mode=
     st = np.zeros(B, np.int32) if status is None else np.asarray(status, dtype=np.int32)
     payload = [np.array([nv, nc, npar, ny, B, int(vjp)], dtype=np.int64), np.array([act_tol]), H, Hinv, F, Hinv @ F, G.reshape(nc, nv), G.reshape(nc, nv) @ Hinv,
                g0, Ebar.reshape(nc, npar), Y, Yp, P, Z, st] + ([np.asarray(ybar, dtype=np.float64).reshape(B, ny)] if vjp else [])
-    raw, err = _run(binary, "run", payload, env)
+    raw, err = run_files(binary, "run", payload, env)
     nout, nw = (npar if vjp else ny * npar), (nc + 31) // 32
     out = np.frombuffer(raw, dtype=np.float64, count=B * nout).reshape((B, npar) if vjp else (B, ny, npar)).copy()
     off = 8 * B * nout

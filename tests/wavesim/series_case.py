@@ -1,11 +1,9 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/seriessim_* (the reduction kernel of csrc/tmpc_series.hip on the host execution model;
+"""TEST INFRASTRUCTURE: drives tests/wavesim/seriessim_* (the reduction kernel of csrc/tmpc_series.hip on the host execution model;
 the file format is described in seriessim_main.cpp), and the edge-shape record both the host-model test and the GPU test reduce."""
-import os
-import subprocess
 
 import numpy as np
 
-from plant_case import BIN, CXX, HERE, _run  # noqa: F401  (CXX: the compiler of series.mk, for the tests' probe)
+from hostsim import run_files
 
 INT_TABLES = ("n_alive", "n_nan", "lost_up", "lost_down", "adopted", "tube", "not_optimal", "overrun", "age_max", "iters_max")
 LONG_TABLES = ("age_sum", "iters_sum")
@@ -15,18 +13,13 @@ SIZES = (0, 1, 2, 63, 64, 65, 255, 256, 257, 2049)             # the groups of t
 QUANTILES = (0.0, 1.0, 0.5, 0.95, 0.25)                        # 0.25 (n - 1) is an integer for n = 1, 65, 257, 2049; 0.5 (n - 1) for the odd n
 
 
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "series.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("seriessim_asan", "seriessim_msan")}
-
-
 def run_stats(binary, e, word, group, q, G, env=None):
     """One launch of the reduction on e, word (T, B) with group (B,) (None: everybody in group 0) -> the tables of montecarlo.series_stats, stderr."""
     e, word = np.asarray(e, dtype=np.float64), np.asarray(word, dtype=np.uint32)
     T, B = word.shape
     q = np.asarray(q, dtype=np.float64).reshape(-1)
     g = np.zeros(B, np.int32) if group is None else np.asarray(group, dtype=np.int32)
-    raw, err = _run(binary, "stats", [np.array([B, T, G, q.size], dtype=np.int64), q, g, e, word], env)
+    raw, err = run_files(binary, "stats", [np.array([B, T, G, q.size], dtype=np.int64), q, g, e, word], env)
     n, off, out = T * G, 0, {}
     for names, dt in ((INT_TABLES, np.int32), (LONG_TABLES, np.int64), (REAL_TABLES, np.float64)):
         for k in names:

@@ -1,34 +1,9 @@
-"""TEST INFRASTRUCTURE: builds and drives tests/wavesim/westsim_* (csrc/tmpc_west.hip on the host execution model; the file formats are
+"""TEST INFRASTRUCTURE: drives tests/wavesim/westsim_* (csrc/tmpc_west.hip on the host execution model; the file formats are
 described in westsim_main.cpp)."""
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-BIN = os.path.join(HERE, "_build")
-
-
-def build_all():
-    subprocess.run(["make", "-j2", "-s", "-f", "westsim.mk", "-C", HERE, "all"], check=True, capture_output=True)
-    return {t: os.path.join(BIN, t) for t in ("westsim_asan", "westsim_msan")}
-
-
-def _run(binary, mode, payload, env):
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in"), os.path.join(d, "out")
-        with open(fin, "wb") as f:
-            for a in payload:
-                f.write(np.ascontiguousarray(a).tobytes())
-        e = dict(os.environ)
-        e.update(env or {})
-        p = subprocess.run([binary, mode, fin, fout], capture_output=True, text=True, env=e)
-        if p.returncode != 0:
-            raise RuntimeError(f"{os.path.basename(binary)} {mode} failed ({p.returncode}):\n{p.stderr[-4000:]}")
-        with open(fout, "rb") as f:
-            raw = f.read()
-    return raw, p.stderr
+from hostsim import run_files
 
 
 def run_select(binary, data, ranks, env=None):
@@ -37,7 +12,7 @@ def run_select(binary, data, ranks, env=None):
     d = d.reshape(-1, 1) if d.ndim == 1 else d
     n, ncol = d.shape
     rk = np.asarray(ranks, dtype=np.int64).reshape(-1)
-    raw, err = _run(binary, "select", [np.array([n, ncol, rk.size], dtype=np.int64), rk, d.T], env)
+    raw, err = run_files(binary, "select", [np.array([n, ncol, rk.size], dtype=np.int64), rk, d.T], env)
     k = ncol * rk.size
     return dict(order_stats=np.frombuffer(raw, dtype=np.float64, count=k).reshape(ncol, rk.size).copy(),
                 n_nonfinite=np.frombuffer(raw, dtype=np.int64, count=ncol, offset=8 * k).copy(),
@@ -54,7 +29,7 @@ def run_rollout(binary, Acl, K, par7, T, substeps=10, x0=None, box=None, n_traj=
                np.array([substeps, T, int(draw), n, first, seed], dtype=np.int64)]
     if not draw:
         payload.append(np.asarray(x0, dtype=np.float64).reshape(-1, 4))
-    raw, err = _run(binary, "rollout", payload, env)
+    raw, err = run_files(binary, "rollout", payload, env)
     o = np.frombuffer(raw, dtype=np.float64)
     ns = 4 * (T - 1) * n
     return dict(x0_used=o[:4 * n].reshape(n, 4).copy(), samples=o[4 * n:4 * n + ns].reshape(4, T - 1, n).copy(),
